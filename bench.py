@@ -10,8 +10,13 @@ steps: every step draws new trial indices.  Trials are independent, so N GPUs ta
 data-path collective ("weak" scaling: B per GPU is fixed); the only exchange is the final sum of the run counters (one
 RCCL all-reduce of 9 int64, outside the timed region except for the closing barrier).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config C2|C3|C4|C5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config C2|C3|C4|C5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times K steps and prints its line; `--full` adds what takes time of its own beyond the timed
+steps (the CPU baseline).  `--dump-outputs DIR`: after the timed steps rank 0 writes what the timed path returned in its last
+step as DIR/<name>.npy, float64 (exact for these integer counters), at most 64 MB in all; the inputs are a pure function of
+the arguments (fixed seed, trial indices by step), so two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line.  Extra objects:
   roofline     HBM roofline of the step's memory-bound kernel, the decoder: `achieved` = its share of the algorithmic bytes
@@ -25,7 +30,7 @@ Rank 0 prints ONE JSON line.  Extra objects:
   cpu_baseline the REAL reference (oracle/_ref/ref_*: the reference's own C source compiled by oracle/Makefile, kind
                "reference") timed on this box's host cores on a bounded sample of the same workload, one single-threaded
                process per core as the reference is run on clusters (NB cell 35:21); kind "port" where only the oracle's
-               restatement can run (config C3: the reference path is Python).  Rank 0, N=1 only.  A reported baseline.
+               restatement can run (config C3: the reference path is Python).  Rank 0, N=1, --full only.  A reported baseline.
 Other configs (`--config`): the same line for BASELINE.json's configs 3-5 with SURVEY.md §8d's formula for each.
 """
 import argparse
@@ -153,7 +158,11 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="trials (streams for C5) per GPU per step; 0 = the config's default")
     ap.add_argument("--config", default="C2", choices=("C2", "C3", "C4", "C5"))
     ap.add_argument("--eps", type=float, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the config's CPU baseline (rank 0, N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
     ap.add_argument("--flooding", action="store_true",
                     help="C2: decode one flooding iteration per barrier round (scldpc_full_bp_device_cn16; with --gen1 the "
                          "16-bit-CN-word kernel): reports the iteration count and the literal-flooding figure")
@@ -264,6 +273,26 @@ def _events(n, k):
     return [tuple(torch.cuda.Event(enable_timing=True) for _ in range(k)) for _ in range(n)]
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(a, rank, arrays):
+    """--dump-outputs: rank 0 writes each tensor as DIR/<name>.npy in float64.  An array over its share of DUMP_BYTES keeps a
+    fixed, seeded sample of its rows (first axis), in order, so that two runs with the same arguments write the same files."""
+    if not a.dump_outputs or rank != 0:
+        return
+    import numpy as np
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        x = t.cpu().numpy().astype(np.float64)
+        row = x[0].nbytes if x.ndim > 1 else 8
+        if x.nbytes > share:
+            keep = np.sort(np.random.default_rng(SEED).choice(len(x), share // row, replace=False))
+            x = x[keep]
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), x)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # C2 (headline): (4,8) L=50 N=1000 eps=0.48 full BP, unlimited iterations
 # ------------------------------------------------------------------------------------------------------------------
@@ -294,6 +323,7 @@ def run_c2(a, E, dev, rank, world, dist, fence, finish):
     sampled = [torch.cuda.Event() for _ in range(nbuf)]
     decoded = [torch.cuda.Event() for _ in range(nbuf)]
     ev = _events(a.steps, 4)
+    res = [None] * nbuf                                 # what the decoder returned for buffer b (--dump-outputs)
 
     def step(k, timed_idx=None):
         trial0 = (k * world + rank) * B                 # global trial index: step-major, then rank — disjoint ranges
@@ -315,15 +345,15 @@ def run_c2(a, E, dev, rank, world, dist, fence, finish):
             if e:
                 e[2].record(s_dec)
             if a.traj and gen2:
-                E.full_bp_cn16(p, d_adj[b], d_cn[b], d_ch[b], counters=d_cnt[b], rows_cap=TRAJ_ROWS)
+                res[b] = E.full_bp_cn16(p, d_adj[b], d_cn[b], d_ch[b], counters=d_cnt[b], rows_cap=TRAJ_ROWS)
             elif a.flooding and gen2:
-                E.full_bp_cn16(p, d_adj[b], d_cn[b], d_ch[b], counters=d_cnt[b])
+                res[b] = E.full_bp_cn16(p, d_adj[b], d_cn[b], d_ch[b], counters=d_cnt[b])
             elif a.flooding:
-                E.full_bp(p, d_adj[b], d_ch[b], counters=d_cnt[b])
+                res[b] = E.full_bp(p, d_adj[b], d_ch[b], counters=d_cnt[b])
             elif gen2:
-                E.full_bp_fixpoint_cn16(p, d_adj[b], d_cn[b], d_ch[b], counters=d_cnt[b])
+                res[b] = E.full_bp_fixpoint_cn16(p, d_adj[b], d_cn[b], d_ch[b], counters=d_cnt[b])
             else:
-                E.full_bp_fixpoint(p, d_adj[b], d_ch[b], counters=d_cnt[b])
+                res[b] = E.full_bp_fixpoint(p, d_adj[b], d_ch[b], counters=d_cnt[b])
             if e:
                 e[3].record(s_dec)
             E.accumulate_run(d_cnt[b], run, 0)
@@ -411,8 +441,20 @@ def run_c2(a, E, dev, rank, world, dist, fence, finish):
                     "BER": r["users_err"] / p.n / r["frames"], "FER_exp": r["frame_err_exp"] / r["frames"],
                     ("mean_iterations" if a.flooding else "mean_barrier_rounds"): r["iterations"] / r["frames"]},
     }
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c2(EPS)
+    last = res[(a.warmup + a.steps - 1) % nbuf]
+    if a.flooding:
+        dump = {"counters": last["counters"], "run": run}
+    else:
+        # the fixpoint decoders' `iterations` column counts barrier rounds of a work queue whose order the waves' atomics
+        # decide: not an output of decodeBP (see "decoder" above), left out so that two builds compare output for output
+        keep = [i for i, n in enumerate(E.COUNTER_NAMES) if n != "iterations"]
+        dump = {"counters": last["counters"][:, keep], "run": run[[i for i, n in enumerate(E.RUN_NAMES) if n != "iterations"]]}
+    if last["rows"] is not None:                        # --traj: the rows past a trial's iteration count are not written
+        live = torch.arange(TRAJ_ROWS, device=dev)[None, :] < last["counters"][:, 5:6]
+        dump["rows"] = last["rows"] * live[:, :, None]
+    dump_outputs(a, rank, dump)
     emit(out)
 
 
@@ -499,8 +541,9 @@ def run_c3(a, E, dev, rank, world, dist, fence, finish):
                                 "fraction of the HBM roofline is reported, not expected to be high"},
            "kernels_ms": {"sample_philox_big": ms_s, "peel_pick": ms_p},
            "results": {"mean_r1_at_step_0": float(m[1][0]) / max(1.0, float(m[0][0])), "trials_in_moments": int(m[0][0])}}
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c3(EPS)
+    dump_outputs(a, rank, {"moments": mom})           # (count, sum r1, sum r1^2) per step over the timed trials
     emit(out)
 
 
@@ -595,8 +638,9 @@ def run_c4(a, E, dev, rank, world, dist, fence, finish):
            "kernels_ms": {"sample_philox": ms_s, "sw_bp": ms_w},
            "results": {"FER": r["frame_err"] / r["frames"], "BLER": r["block_err"] / p.L / r["frames"],
                        "BER": r["users_err"] / p.n / r["frames"], "mean_window_iterations": r["iterations"] / r["frames"]}}
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c4(EPS, W, IT)
+    dump_outputs(a, rank, {"counters": d_cnt[(a.warmup + a.steps - 1) % nbuf], "run": run})
     emit(out)
 
 
@@ -673,8 +717,9 @@ def run_c5(a, E, dev, rank, world, dist, fence, finish):
                                 "decoded; `traffic` sums both kernels' launches of a step"},
            "results": {"BLER": float(c[1]) / max(1.0, float(c[5])), "BLER_exp": float(c[3]) / max(1.0, float(c[7])),
                        "BER": float(c[0]) / max(1.0, float(c[4])), "blocks": int(c[5])}}
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c5(EPS, W, DOPED)
+    dump_outputs(a, rank, {"counters": torch.cat([st.counters for st in sts])})   # per stream, since its start
     emit(out)
 
 
