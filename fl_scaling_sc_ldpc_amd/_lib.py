@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("SCLDPC_LIB_PATH") or os.path.join(HERE, "libscldpc_hi
 
 NCOUNTERS = 8
 NRUN = 9
+MAX_CAPS = 16                   # SCLDPC_MAX_CAPS
 NPEELRUN = 8
 PEELRUN_NAMES = ("trials", "fuckups", "lost", "fuckups_exp", "lost_exp", "blocks_exp")     # SCLDPC_PR_*
 COUNTER_NAMES = ("num_erasures", "num_blocks_err", "num_erasures_exp", "num_blocks_err_exp",
@@ -43,6 +44,7 @@ EXPORTS = (
     "scldpc_stream_glibc_next_host", "scldpc_stream_run_device_inputs_at",
     "scldpc_full_bp_sock16_supported", "scldpc_full_bp_fixpoint_device_sock16", "scldpc_full_bp_device_sock16",
     "scldpc_full_bp_traj_device_cn16", "scldpc_full_bp_traj_device_sock16",
+    "scldpc_full_bp_caps_device_cn16", "scldpc_full_bp_caps_device_sock16",
 )
 
 
@@ -119,6 +121,8 @@ def lib():
     L.scldpc_full_bp_device_sock16.argtypes = L.scldpc_full_bp_device_cn16.argtypes
     L.scldpc_full_bp_traj_device_cn16.argtypes = [pp, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp]
     L.scldpc_full_bp_traj_device_sock16.argtypes = L.scldpc_full_bp_traj_device_cn16.argtypes
+    L.scldpc_full_bp_caps_device_cn16.argtypes = [pp, i32, vp, vp, vp, i32, vp, i32, vp, vp]
+    L.scldpc_full_bp_caps_device_sock16.argtypes = L.scldpc_full_bp_caps_device_cn16.argtypes
     L.scldpc_full_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, u64, vp]
     L.scldpc_sw_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_sample_philox_device_adj16.argtypes = L.scldpc_sample_philox_device.argtypes

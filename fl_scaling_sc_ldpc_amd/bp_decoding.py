@@ -28,9 +28,15 @@ Two sampling modes:
     reference seeds from gettimeofday, BPF:2059-2062; pass --seed to pin it).  Sampling is then a
     sequential host loop (as in the reference); decoding still runs on the device.  Single rank only.
 
+`bp_lim_iter … --caps 175,200,250` writes the files of several MAX_IT from one run: one file per cap, each the file that
+`bp_lim_iter` with that MAX_IT writes.  Where that is exact and the level-synchronous decoder takes the ensemble (Philox
+sampling, NUM_DOPED = 0) the frames are sampled and decoded once, with a checkpoint at every cap
+(engine.full_bp_caps_cn16); otherwise the caps run one after another.
+
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
+import copy
 import os
 import sys
 import time
@@ -129,8 +135,12 @@ class Simulator:
 
     def __init__(self, p, decoder="full", W=0, max_it=0, init_it=0, is_term=True, doped=(), batch=2048,
                  rng="philox", seed=1, device=None, rows_cap=0, schedule="flooding", shard_frames=True, index=0,
-                 verbose=False):
+                 verbose=False, caps=None):
         self.p, self.decoder, self.W, self.max_it, self.init_it = p, decoder, W, max_it, init_it
+        # caps: several MaxNumIt from one decode (run_point_caps; the level-synchronous 4-bit decoder only)
+        self.caps = E.check_caps(caps) if caps is not None else None
+        if self.caps is not None:
+            self.max_it = self.caps[-1]
         self.index = index              # replica (the executables' INDEX): part of the Philox key
         self.schedule = schedule        # "fixpoint": unlimited full BP without the iteration count (1.2x faster)
         self.is_term, self.doped, self.batch, self.rng, self.seed = is_term, tuple(doped), batch, rng, seed
@@ -171,6 +181,11 @@ class Simulator:
                       and E.sock16_supported(p) and E.sw_ring_supported(p, self.W))
         self.d_cn = (torch.empty((batch, p.nk, p.dc), dtype=torch.int16, device=self.device)
                      if (self.gen2 or self.lvl2 or self.ring2) else None)
+        if self.caps is not None:
+            if not (self.lvl2 and self.rows_cap == 0 and not self.doped):
+                raise ValueError("caps: the fused decode takes Philox sampling, no doping and an ensemble of the "
+                                 "level-synchronous 4-bit decoder (caps_sequential_reason)")
+            self.d_cnt_caps = torch.empty(len(self.caps) * batch * NCOUNTERS, dtype=torch.int32, device=self.device)
         if self.verbose:
             print("[scldpc] kernels: " + self.kernel_choice(), file=sys.stderr, flush=True)
 
@@ -185,6 +200,8 @@ class Simulator:
             else "sampler (first generation)"
         if self.gen2:
             return samp + " + full_bp_small fixpoint (4-bit CN counts)"
+        if self.lvl2 and self.caps is not None:
+            return samp + " + full_bp_small level-synchronous with %d cap checkpoints per decode (4-bit CN counts)" % len(self.caps)
         if self.lvl2:
             return samp + " + full_bp_small level-synchronous (4-bit CN counts" + (", trajectory rows)" if self.rows_cap else ")")
         return samp + " + full_bp (16-bit CN words" + (", trajectory rows)" if self.rows_cap else ")") + \
@@ -211,6 +228,12 @@ class Simulator:
             return E.full_bp_fixpoint(self.p, adj, ch, is_term=self.is_term, counters=cnt)    # no iteration counts
         return E.full_bp(self.p, adj, ch, max_it=self.max_it, is_term=self.is_term,
                          rows_cap=self.rows_cap if want_rows else 0, counters=cnt)
+
+    def decode_batch_caps(self, nb):
+        """The counters [K, nb, 8] of every cap of self.caps for the batch in place (one decode)."""
+        cnt = self.d_cnt_caps[:len(self.caps) * nb * NCOUNTERS].view(len(self.caps), nb, NCOUNTERS)
+        return E.full_bp_caps_cn16(self.p, self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb], self.caps, is_term=self.is_term,
+                                   counters=cnt, sockets=self.sock)
 
     def fill_batch(self, sim, eps, frame0, nb):
         if self.rng == "philox" and (self.gen2 or self.lvl2) and self.sock:
@@ -301,11 +324,181 @@ class Simulator:
             abort_invariant()
         return PointResult(eps, p.n, p.L, run.cpu().numpy(), bad=bool(bad))
 
+    def run_point_caps(self, sim, eps, min_frame_err, max_frames):
+        """run_point for every cap of self.caps from one sampling pass and one decode per batch: one PointResult per cap,
+        each what run_point with max_it = that cap returns.  Every cap keeps its own ordered stop (its own frame_err; frames
+        past its tripping frame are not counted for it); the point ends when every cap has stopped.  Rounds, batches and
+        the frame split over the ranks are run_point's, so each cap sees the frames a single-cap run sees.  A cap whose
+        frames broke decodeBP's invariant comes back with .bad set (the caller decides when to abort: the other caps go on)."""
+        p, B, W, K = self.p, self.batch, self.world, len(self.caps)
+        i_frames, i_ferr, i_status = RUN_NAMES.index("frames"), RUN_NAMES.index("frame_err"), \
+            E.COUNTER_NAMES.index("status")
+        runs = [self._new_run() for _ in range(K)]
+        bad = torch.zeros(K, dtype=torch.bool, device=runs[0].device)
+        stopped = [False] * K
+        consumed = [0] * K
+        frame0 = 0
+        while frame0 < max_frames and not all(stopped):
+            R, sizes, offs = self.split_round(max_frames - frame0, B, W)
+            nb, off = sizes[self.rank], offs[self.rank]
+            cnt = None
+            if nb:
+                self.fill_batch(sim, eps, frame0 + off, nb)
+                cnt = self.decode_batch_caps(nb)
+            if W > 1:
+                m = max(sizes)
+                mine = torch.zeros((K, m, NCOUNTERS), dtype=torch.int32, device=self.d_cnt.device)
+                if nb:
+                    mine[:, :nb] = cnt
+                gathered = [torch.empty_like(mine) for _ in range(W)]
+                self.dist.all_gather(gathered, mine)
+                allcnt = torch.cat([g[:, :s] for g, s in zip(gathered, sizes)], dim=1)
+            else:
+                allcnt = cnt
+            can_trip = min_frame_err > 0 and frame0 + R >= min_frame_err
+            live = [k for k in range(K) if not stopped[k]]
+            for k in live:
+                self._accumulate(allcnt[k].contiguous(), runs[k], min_frame_err)
+            for k in live:
+                if can_trip:
+                    r = runs[k].cpu().numpy()
+                    used_round = int(r[i_frames]) - consumed[k]
+                    consumed[k] = int(r[i_frames])
+                    stopped[k] = bool(r[i_ferr] >= min_frame_err)
+                else:
+                    used_round = R
+                    consumed[k] += R
+                bad[k] |= (allcnt[k, :used_round, i_status] != 0).any()
+            frame0 += R
+        bad = bad.cpu().tolist()
+        return [PointResult(eps, p.n, p.L, runs[k].cpu().numpy(), bad=bad[k]) for k in range(K)]
+
+
+def caps_sequential_reason(p, rng, num_doped, schedule):
+    """Why `bp_lim_iter --caps` runs its caps one after another instead of from one decode, or None.  The fused decode is
+    used only where each cap's file is exactly the single-cap file and the level-synchronous 4-bit decoder takes the ensemble."""
+    if rng != "philox":
+        return "--rng %s: each cap's run replays srandom(seed) from the start and stops drawing at its own frame" % rng
+    if num_doped > 0:
+        return "NUM_DOPED > 0: the first doped position is MAX_IT (BPF:2083-2091), so every cap is a different experiment"
+    if schedule != "flooding":
+        return "--schedule %s has no iteration caps" % schedule
+    if not (E.cn16_supported(p) or E.full_bp_sock16_supported(p)):
+        return "the level-synchronous 4-bit decoder takes dv = 4, dc = 8 and at most 65536 CNs per trial"
+    return None
+
+
+def _caps_list(text):
+    """--caps 175,200,250 → [175, 200, 250]"""
+    try:
+        return [int(x) for x in text.split(",") if x.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError("--caps takes a comma-separated list of integers: %r" % text)
+
 
 def abort_invariant():
     """The reference aborts the process at a frame that recovers more VNs than it had degree-1 CNs (BPF:1035-1039)."""
     print("ARGH! RECOVERED MORE VNs THAN deg-1 CNs! Aborting!", flush=True)
     raise SystemExit(-1)
+
+
+def _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, shard, by_points):
+    """`bp_lim_iter … --caps`: the files of MAX_IT and of every --caps value, each what `bp_lim_iter` with that MAX_IT
+    writes — from one decode per batch with a checkpoint at every cap where that is exact, else one run per cap."""
+    dist, rank, world = _dist()
+    file_its = sorted(set(opts.caps) | {max_it})                  # the MAX_IT of each file
+    reason = caps_sequential_reason(p, opts.rng, num_doped, getattr(opts, "schedule", "flooding"))
+    verbose = rank == 0 and not opts.quiet
+    if reason is not None:
+        if verbose:
+            print("[scldpc] kernels: --caps runs %d single-cap passes one after another (%s)" % (len(file_its), reason),
+                  file=sys.stderr, flush=True)
+        one = copy.copy(opts)
+        one.caps = None
+        aborted = False
+        for v in file_its:
+            try:
+                run_program(prog, index, W, num_doped, v, extra, one)
+            except SystemExit as e:                               # abort_invariant: the other caps go on
+                if e.code != -1:
+                    raise
+                aborted = True
+        if aborted:
+            raise SystemExit(-1)
+        return 0
+    caps = sorted(set(max(1, v) for v in file_its))               # at least one iteration runs (BPF:1065), as run_program
+    if len(caps) > E.MAX_CAPS:
+        raise SystemExit("--caps: at most %d distinct caps per run (%d given)" % (E.MAX_CAPS, len(caps)))
+    slot = {v: caps.index(max(1, v)) for v in file_its}
+    sim_obj = Simulator(p, decoder="full", W=W, max_it=caps[-1], is_term=True, doped=doped, batch=opts.batch, rng=opts.rng,
+                        seed=opts.seed, schedule="flooding", shard_frames=shard == "frames",
+                        device=getattr(opts, "device", None), index=index, verbose=verbose, caps=caps)
+    outdir = opts.outdir
+    os.makedirs(outdir, exist_ok=True)
+    paths = {v: os.path.join(outdir, result_filename(prog, p, W, v, 0, index)) for v in file_its}
+    t0 = time.time()
+
+    def report(v, point):
+        if verbose:
+            r = point.run
+            print("[%dit] %f %e %e %e   (f=%d, %.1fs)" % (v, point.eps, r["users_err"] / p.n / point.f, r["frame_err"] / point.f,
+                                                         r["block_err"] / p.L / point.f, point.f, time.time() - t0), flush=True)
+
+    K = len(caps)
+    if by_points:
+        # run_program's points mode with a cap axis: table [points][K][NRUN counters + abort flag], one all-reduce at the
+        # end, rank 0 writes the K files in grid order, each up to its own first broken point
+        parts = {v: paths[v] + ".rank%d.part" % rank for v in file_its}
+        table = torch.zeros((grid.num_points, K, NRUN + 1), dtype=torch.int64, device=sim_obj.device)
+        gone = [False] * K                                        # this rank's single-cap process of that cap has aborted
+        for sim in range(rank, grid.num_points, world):
+            points = sim_obj.run_point_caps(sim, grid.eps(sim), grid.min_frame_err, grid.max_frames)
+            for k, point in enumerate(points):
+                if not gone[k]:
+                    table[sim, k, :NRUN] = torch.tensor([point.run[n] for n in RUN_NAMES], dtype=torch.int64,
+                                                        device=sim_obj.device)
+                    table[sim, k, NRUN] = int(point.bad)
+            for v in file_its:
+                if not gone[slot[v]]:
+                    with open(parts[v], "a" if sim != rank else "w") as f:
+                        f.write("%d %s" % (sim, points[slot[v]].row()))
+            gone = [g or pt.bad for g, pt in zip(gone, points)]
+            if all(gone):
+                break
+        dist.all_reduce(table)
+        rows = table.cpu().numpy()
+        any_bad = False
+        for v in file_its:
+            k = slot[v]
+            first_bad = next((s for s in range(grid.num_points) if rows[s, k, NRUN]), None)
+            any_bad = any_bad or first_bad is not None
+            if rank == 0:
+                for sim in range(grid.num_points if first_bad is None else first_bad):
+                    pt = PointResult(grid.eps(sim), p.n, p.L, rows[sim, k, :NRUN])
+                    if pt.f == 0:
+                        break
+                    write_risultati(paths[v], sim, pt)
+                    report(v, pt)
+        dist.barrier()
+        for v in file_its:
+            if os.path.exists(parts[v]):
+                os.remove(parts[v])
+        if any_bad:
+            abort_invariant()
+        return 0
+
+    gone = [False] * K                                            # the single-cap run of that cap has aborted
+    for sim in range(grid.num_points):
+        points = sim_obj.run_point_caps(sim, grid.eps(sim), grid.min_frame_err, grid.max_frames)
+        for k, point in enumerate(points):
+            gone[k] = gone[k] or point.bad
+        for v in file_its:
+            if not gone[slot[v]] and rank == 0:
+                write_risultati(paths[v], sim, points[slot[v]])
+                report(v, points[slot[v]])
+    if any(gone):
+        abort_invariant()
+    return 0
 
 
 def _write_traj_rows(fh, rows, counters, nb, cols=4):
@@ -368,6 +561,8 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
         shard = "points" if (world > 1 and grid.num_points >= world) else "frames"
     by_points = shard == "points" and world > 1
     replica = index + rank if shard == "replicas" else index
+    if getattr(opts, "caps", None) and prog == "bp_lim_iter":
+        return _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, shard, by_points)
     # the decoders' loop is do { … } while (iter < MaxNumIt) (BPF:1065, BPT:1076): at least one iteration runs
     cap = max(1, max_it)
     sim_obj = Simulator(p, decoder=decoder, W=W, max_it=cap, init_it=init_it,
@@ -472,6 +667,10 @@ def _parser(prog):
     ap.add_argument("--schedule", choices=("flooding", "fixpoint"), default="flooding",
                     help="bp_lim_iter with MAX_IT >= 10^6: 'fixpoint' decodes to the same residual without walking "
                          "the flooding iterations (same files; no iteration statistics)")
+    if prog == "bp_lim_iter":
+        ap.add_argument("--caps", type=_caps_list, default=None, metavar="K1,K2,…",
+                        help="also write the files of these MAX_IT (one file per cap, each the file of a run with that "
+                             "MAX_IT); from one decode per frame where that is exact, else one run per cap")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")

@@ -52,6 +52,8 @@ struct SmArgs {
     const uint32_t *chan;
     int32_t *counters;
     uint32_t *erased_out;
+    int ncaps;                                      // CAPS: caps[0] < caps[1] < … (>= 1); counters [ncaps][ntrials][8]
+    int caps[SCLDPC_MAX_CAPS];
 };
 
 // Seven 4-wave workgroups per CU are 7 waves per SIMD: at most 96 SGPRs and 72 VGPRs per wave (MI355X_MICROARCH.md).
@@ -59,7 +61,11 @@ struct SmArgs {
 // table, any chain length) instead of global VN ids (which need n < 65535).
 // TRAJ (with LEVEL): the trajectory rows of the BPT build — per iteration deg_1_iter, the VNs recovered and the position of
 // the first erased VN (BPT:988, 1037-1038, 1051), incl. iteration 0's count of degree-1 CNs whose only VN is known (BPF:973).
-template <int BLOCK, bool LEVEL, bool PERSIST, bool SOCK, bool TRAJ = false>
+// CAPS (with LEVEL): several MaxNumIt at once.  On the BEC the flooding iterations do not depend on the cap, which only ends
+// the loop (BPF:1065): where a single-cap decode tests it, the decoder takes a checkpoint instead — the counters that decode
+// would report, written to that cap's block of counters [ncaps][ntrials][8] — and goes on to the next cap.  Caps the decode
+// does not reach (a stop test or a broken invariant ended it first) get its final state.
+template <int BLOCK, bool LEVEL, bool PERSIST, bool SOCK, bool TRAJ = false, bool CAPS = false>
 __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_sgpr(96))) void full_bp_small_kernel(const SmArgs a)
 {
     constexpr int kWaves = BLOCK / 64;
@@ -189,7 +195,80 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
         }
     };
 
-    int rounds = 0, ne = 0, status = 0;
+    int rounds = 0, ne = 0, status = 0, be = 0, ee = 0, bee = 0;
+    // ---- what decodeBP reports after its loop (BPF:1067-1138), from U and the counts as they stand: be, ee, bee --------
+    // erased VNs per position into pos_cnt (zero on entry), the blocks in error, the size-2 stopping sets of the first
+    // failing position.  It reads pos_cnt up to its end: a caller that clears it again puts a barrier in between.
+    auto residual = [&]() {
+    if (ne > 0) {
+        // ---- erased VNs per position (word w of U may straddle two positions) ----------------------------------------
+        for (int w = tid; w < nw; w += BLOCK) {
+            uint32_t x = U[w];
+            int p0 = (int)__umulhi((uint32_t)(w * 32), a.magic_v);
+            int room = (p0 + 1) * V - w * 32;                            // bits of this word left in position p0
+            while (x) {
+                const uint32_t lo = room >= 32 ? x : (x & ((1u << room) - 1u));
+                if (lo) atomicAdd(&pos_cnt[p0], __popc(lo));
+                x = room >= 32 ? 0u : (x >> room);
+                p0++;
+                room = V;
+            }
+        }
+        __syncthreads();
+        // ---- size-2 stopping sets (BPF:1067-1133) of the first failing position(s) only ----------------------------
+        int q0 = 0;
+        for (;;) {
+            while (q0 < L && pos_cnt[q0] == 0) q0++;
+            if (q0 >= L) break;
+            for (int t = tid; t < V; t += BLOCK) {
+                const int j = q0 * V + t;
+                if (!((U[j >> 5] >> (j & 31)) & 1u)) continue;
+                const uint2 r = vrow[j];
+                const int base = q0 * C;
+                const int cc[4] = {base + (int)(r.x & 0xFFFFu), base + C + (int)(r.x >> 16),
+                                   base + 2 * C + (int)(r.y & 0xFFFFu), base + 3 * C + (int)(r.y >> 16)};
+                bool pair = true;
+#pragma unroll
+                for (int i = 0; i < 4; i++) pair = pair && ((cnt[cc[i] >> 3] >> ((cc[i] & 7) * 4)) & 15u) == 2u;
+                if (!pair) continue;
+                int partner = -1;
+                for (int i = 0; i < 4 && pair; i++) {                    // the other erased neighbour of each CN
+                    const uint4 s4 = crow[cc[i]];
+                    const uint32_t jk[8] = {s4.x & 0xFFFFu, s4.x >> 16, s4.y & 0xFFFFu, s4.y >> 16,
+                                            s4.z & 0xFFFFu, s4.z >> 16, s4.w & 0xFFFFu, s4.w >> 16};
+                    int other = -1;
+                    for (int k = 0; k < 8; k++) {
+                        if (jk[k] == 0xFFFFu) continue;
+                        // (cc[i] lies in CN position q0 + i)
+                        const int j2 = SOCK ? (q0 + i - (int)(jk[k] & 3u)) * V + (int)(jk[k] >> 2) : (int)jk[k];
+                        if (j2 != j && ((U[j2 >> 5] >> (j2 & 31)) & 1u)) other = j2;
+                    }
+                    if (other < 0 || (i > 0 && other != partner)) pair = false;
+                    partner = other;
+                }
+                if (pair && (int)__umulhi((uint32_t)partner, a.magic_v) == q0) atomicAdd(&pos_ss[q0], 1);
+            }
+            __syncthreads();
+            const int e = pos_cnt[q0] - pos_ss[q0];
+            if (e > 0) { ee = e; bee = 1; break; }                       // only the FIRST such position (BPF:1126-1132)
+            q0++;
+        }
+        for (int pos = 0; pos < L; pos++) be += pos_cnt[pos] > 0;
+    }
+    };
+    auto put = [&](int32_t *o, int ne, int be, int ee, int bee, int rounds, int status) {
+        o[SCLDPC_C_NUM_ERASURES] = ne;
+        o[SCLDPC_C_NUM_BLOCKS_ERR] = be;
+        o[SCLDPC_C_NUM_ERASURES_EXP] = ee;
+        o[SCLDPC_C_NUM_BLOCKS_ERR_EXP] = bee;
+        o[SCLDPC_C_NUM_ERASURES_P1] = 0;
+        o[SCLDPC_C_ITERATIONS] = rounds;                                 // LEVEL: flooding iterations; else barrier rounds
+        o[SCLDPC_C_STATUS] = status;
+        o[SCLDPC_C_CHANNEL_ERASURES] = nch;
+    };
+    auto cap_counters = [&](int k) { return a.counters + ((size_t)k * a.ntrials + trial) * SCLDPC_NCOUNTERS; };
+
+    int ci = 0;                                                          // CAPS: the next cap to reach
     if constexpr (LEVEL) {
         // ---- one flooding iteration per barrier round (decodeBP's do-while, BPF:927-1065) ------------------------------
         uint8_t *fb = reinterpret_cast<uint8_t *>(lds + a.off_fb);       // snapshot of a scan round: one byte per count word
@@ -329,7 +408,17 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
             scan = scal[LV_OVF + g] != 0;
             ncur = scan ? 0 : scal[LV_PUSH + g];
             iter++;
-            if (a.max_it > 0 && iter >= a.max_it) break;                 // BPF:1065
+            if (!CAPS && a.max_it > 0 && iter >= a.max_it) break;        // BPF:1065
+            if constexpr (CAPS) {
+                if (iter >= a.caps[ci]) {                                // checkpoint: a decode with MaxNumIt = caps[ci] ends here
+                    be = ee = bee = 0;
+                    residual();
+                    if (tid == 0) put(cap_counters(ci), ne, be, ee, bee, rounds, 0);
+                    __syncthreads();                                     // U, the counts and pos_cnt read: releases may go on
+                    for (int i = tid; i < 2 * L; i += BLOCK) pos_cnt[i] = 0;     // (the next checkpoint is behind a barrier)
+                    if (++ci == a.ncaps) break;
+                }
+            }
             STAMP(7);                                                    // bookkeeping
         }
         __syncthreads();
@@ -420,76 +509,20 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
         ne = nch - scal[SC_REM];
     }
 
-    // ---- erased VNs per position (word w of U may straddle two positions) --------------------------------------------
-    int be = 0, ee = 0, bee = 0;
-    if (ne > 0) {
-        for (int w = tid; w < nw; w += BLOCK) {
-            uint32_t x = U[w];
-            int p0 = (int)__umulhi((uint32_t)(w * 32), a.magic_v);
-            int room = (p0 + 1) * V - w * 32;                            // bits of this word left in position p0
-            while (x) {
-                const uint32_t lo = room >= 32 ? x : (x & ((1u << room) - 1u));
-                if (lo) atomicAdd(&pos_cnt[p0], __popc(lo));
-                x = room >= 32 ? 0u : (x >> room);
-                p0++;
-                room = V;
-            }
-        }
-        __syncthreads();
-        // ---- size-2 stopping sets (BPF:1067-1133) of the first failing position(s) only ----------------------------
-        int q0 = 0;
-        for (;;) {
-            while (q0 < L && pos_cnt[q0] == 0) q0++;
-            if (q0 >= L) break;
-            for (int t = tid; t < V; t += BLOCK) {
-                const int j = q0 * V + t;
-                if (!((U[j >> 5] >> (j & 31)) & 1u)) continue;
-                const uint2 r = vrow[j];
-                const int base = q0 * C;
-                const int cc[4] = {base + (int)(r.x & 0xFFFFu), base + C + (int)(r.x >> 16),
-                                   base + 2 * C + (int)(r.y & 0xFFFFu), base + 3 * C + (int)(r.y >> 16)};
-                bool pair = true;
-#pragma unroll
-                for (int i = 0; i < 4; i++) pair = pair && ((cnt[cc[i] >> 3] >> ((cc[i] & 7) * 4)) & 15u) == 2u;
-                if (!pair) continue;
-                int partner = -1;
-                for (int i = 0; i < 4 && pair; i++) {                    // the other erased neighbour of each CN
-                    const uint4 s4 = crow[cc[i]];
-                    const uint32_t jk[8] = {s4.x & 0xFFFFu, s4.x >> 16, s4.y & 0xFFFFu, s4.y >> 16,
-                                            s4.z & 0xFFFFu, s4.z >> 16, s4.w & 0xFFFFu, s4.w >> 16};
-                    int other = -1;
-                    for (int k = 0; k < 8; k++) {
-                        if (jk[k] == 0xFFFFu) continue;
-                        // (cc[i] lies in CN position q0 + i)
-                        const int j2 = SOCK ? (q0 + i - (int)(jk[k] & 3u)) * V + (int)(jk[k] >> 2) : (int)jk[k];
-                        if (j2 != j && ((U[j2 >> 5] >> (j2 & 31)) & 1u)) other = j2;
-                    }
-                    if (other < 0 || (i > 0 && other != partner)) pair = false;
-                    partner = other;
-                }
-                if (pair && (int)__umulhi((uint32_t)partner, a.magic_v) == q0) atomicAdd(&pos_ss[q0], 1);
-            }
-            __syncthreads();
-            const int e = pos_cnt[q0] - pos_ss[q0];
-            if (e > 0) { ee = e; bee = 1; break; }                       // only the FIRST such position (BPF:1126-1132)
-            q0++;
-        }
-        for (int pos = 0; pos < L; pos++) be += pos_cnt[pos] > 0;
+    if (!CAPS || ci < a.ncaps) {
+        be = ee = bee = 0;
+        residual();
     }
     STAMP(2);                                                            // per-position counts + expurgation
     STAMP_FLUSH();
     if (a.erased_out)
         for (int w = tid; w < nw; w += BLOCK) a.erased_out[(size_t)trial * nw + w] = U[w];
     if (tid == 0) {
-        int32_t *o = a.counters + (size_t)trial * SCLDPC_NCOUNTERS;
-        o[SCLDPC_C_NUM_ERASURES] = ne;
-        o[SCLDPC_C_NUM_BLOCKS_ERR] = be;
-        o[SCLDPC_C_NUM_ERASURES_EXP] = ee;
-        o[SCLDPC_C_NUM_BLOCKS_ERR_EXP] = bee;
-        o[SCLDPC_C_NUM_ERASURES_P1] = 0;
-        o[SCLDPC_C_ITERATIONS] = rounds;                                 // LEVEL: flooding iterations; else barrier rounds
-        o[SCLDPC_C_STATUS] = status;
-        o[SCLDPC_C_CHANNEL_ERASURES] = nch;
+        if constexpr (CAPS) {
+            for (int k = ci; k < a.ncaps; k++) put(cap_counters(k), ne, be, ee, bee, rounds, status);    // not reached
+        } else {
+            put(a.counters + (size_t)trial * SCLDPC_NCOUNTERS, ne, be, ee, bee, rounds, status);
+        }
     }
     };
     // PERSIST: workgroup b decodes trials b, b + gridDim.x, …; otherwise exactly one
@@ -603,6 +636,47 @@ int launch_small(const char *who, bool level, bool sock, const scldpc_code_param
     return SCLDPC_OK;
 }
 
+// the level-synchronous decoder with checkpoints at several caps (CAPS): one workgroup per trial, the LDS carve of the level form
+int launch_caps(const char *who, bool sock, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t ncaps, const int32_t *caps, int32_t is_term,
+                int32_t *d_counters, void *stream)
+{
+    if (ncaps < 1 || ncaps > SCLDPC_MAX_CAPS || !caps)
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: takes 1 .. %d caps (ncaps = %d%s)", who, SCLDPC_MAX_CAPS, ncaps,
+                                 caps ? "" : ", caps NULL");
+    for (int k = 0; k < ncaps; k++)
+        if (caps[k] < 1 || (k > 0 && caps[k] <= caps[k - 1]))
+            return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: caps must be strictly increasing and >= 1 (caps[%d] = %d)", who, k,
+                                     caps[k]);
+    if (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj16 || !d_cn_adj16 || !d_chan_bits)))
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
+    if (int rc = scldpc::check_params(p)) return rc;
+    if (!(sock ? scldpc_full_bp_sock16_supported(p) : scldpc_full_bp_cn16_supported(p)))
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: takes dv = 4, dc = 8, at most 65536 CNs per trial%s", who,
+                                 sock ? " and 16-bit sockets" : " and fewer than 65535 VNs (use the _sock16 form beyond)");
+    if (ntrials == 0) return SCLDPC_OK;
+    SmArgs a{};
+    int per_cu = kPerCu;                                               // the carve of launch_small's level form
+    while (per_cu > 1 && make_args(p, is_term, &a, per_cu, true) != 0) per_cu--;
+    if (make_args(p, is_term, &a, per_cu, true) != 0)
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: the CN counts and VN bits do not fit the LDS", who);
+    scldpc::magic_of(p->vns_pos, a.n + 32, &a.magic_v);
+    scldpc::magic_of(p->cns_pos, a.nk, &a.magic_c);
+    a.vn_adj16 = d_vn_adj16; a.cn_adj16 = d_cn_adj16; a.chan = d_chan_bits;
+    a.counters = d_counters;
+    a.kswitch = kSwitchWidth;
+    a.ntrials = ntrials;
+    a.ncaps = ncaps;
+    for (int k = 0; k < ncaps; k++) a.caps[k] = caps[k];
+    void (*kern)(const SmArgs) = sock ? full_bp_small_kernel<kBlockSmall, true, false, true, false, true>
+                                      : full_bp_small_kernel<kBlockSmall, true, false, false, false, true>;
+    const size_t lds_bytes = 4u * (size_t)a.total;
+    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
+    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(kBlockSmall), lds_bytes, static_cast<hipStream_t>(stream), a);
+    SCLDPC_HIP_CHECK(hipGetLastError());
+    return SCLDPC_OK;
+}
+
 }  // namespace
 
 extern "C" int scldpc_full_bp_fixpoint_device_cn16(const scldpc_code_params *p, int32_t ntrials,
@@ -662,4 +736,22 @@ extern "C" int scldpc_full_bp_traj_device_sock16(const scldpc_code_params *p, in
     if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_sock16: null d_rows");
     return launch_small("scldpc_full_bp_traj_device_sock16", true, true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it,
                         is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap);
+}
+
+// Several caps from one decode: block k of d_counters [ncaps][ntrials][8] is what scldpc_full_bp_device_*(max_it = caps[k])
+// writes (include/scldpc.h)
+extern "C" int scldpc_full_bp_caps_device_cn16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                               const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                               const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream)
+{
+    return launch_caps("scldpc_full_bp_caps_device_cn16", false, p, ntrials, d_vn_adj16, d_cn_adj16, d_chan_bits, ncaps, caps,
+                       is_term, d_counters, stream);
+}
+
+extern "C" int scldpc_full_bp_caps_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                                 const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                                 const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream)
+{
+    return launch_caps("scldpc_full_bp_caps_device_sock16", true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, ncaps, caps,
+                       is_term, d_counters, stream);
 }

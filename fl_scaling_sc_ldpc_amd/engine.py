@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (CodeParams, NCOUNTERS, NRUN, NPEELRUN, COUNTER_NAMES, RUN_NAMES, PEELRUN_NAMES, ScldpcError,  # noqa: F401
+from ._lib import (CodeParams, MAX_CAPS, NCOUNTERS, NRUN, NPEELRUN, COUNTER_NAMES, RUN_NAMES, PEELRUN_NAMES, ScldpcError,  # noqa: F401
                    check, lib)
 
 
@@ -350,6 +350,37 @@ def full_bp_cn16(p, d_adj16, d_cn16, d_chan, max_it=0, is_term=True, want_erased
     check(fn(C.byref(p), T, d_adj16.data_ptr(), d_cn16.data_ptr(), d_chan.data_ptr(), int(max_it), 1 if is_term else 0,
              counters.data_ptr(), erased.data_ptr() if erased is not None else None, _stream_ptr(dev)))
     return {"counters": counters, "rows": None, "erased": erased}
+
+
+def check_caps(caps):
+    """The cap list of full_bp_caps_cn16 as a tuple, with the C side's rules: 1 .. MAX_CAPS strictly increasing caps >= 1."""
+    caps = tuple(int(k) for k in caps)
+    if not 1 <= len(caps) <= MAX_CAPS:
+        raise ValueError("takes 1 .. %d caps, got %d" % (MAX_CAPS, len(caps)))
+    if caps[0] < 1 or any(b <= a for a, b in zip(caps, caps[1:])):
+        raise ValueError("caps must be strictly increasing and >= 1: %r" % (caps,))
+    return caps
+
+
+def full_bp_caps_cn16(p, d_adj16, d_cn16, d_chan, caps, is_term=True, counters=None, sockets=False):
+    """scldpc_full_bp_caps_device_cn16 (sockets=True: _sock16): one decode, the counters of several iteration caps —
+    counters [K, T, 8], where counters[k] == full_bp_cn16(..., max_it=caps[k])["counters"] on all eight columns."""
+    caps = check_caps(caps)
+    _require_gpu()
+    T = d_adj16.shape[0]
+    assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous()
+    assert d_cn16.is_cuda and d_cn16.dtype == torch.int16 and d_cn16.is_contiguous()
+    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
+    assert tuple(d_adj16.shape[1:]) == (p.n, p.dv) and tuple(d_cn16.shape) == (T, p.nk, p.dc) and tuple(d_chan.shape) == (T, p.nw)
+    dev = d_adj16.device
+    if counters is None:
+        counters = torch.empty((len(caps), T, NCOUNTERS), dtype=torch.int32, device=dev)
+    assert counters.is_contiguous() and counters.dtype == torch.int32 and tuple(counters.shape) == (len(caps), T, NCOUNTERS)
+    arr = (C.c_int32 * len(caps))(*caps)
+    fn = lib().scldpc_full_bp_caps_device_sock16 if sockets else lib().scldpc_full_bp_caps_device_cn16
+    check(fn(C.byref(p), T, d_adj16.data_ptr(), d_cn16.data_ptr(), d_chan.data_ptr(), len(caps), arr, 1 if is_term else 0,
+             counters.data_ptr(), _stream_ptr(dev)))
+    return counters
 
 
 def cn_sockets(p, d_adj16, out=None):

@@ -213,6 +213,20 @@ int scldpc_full_bp_fixpoint_device_sock16(const scldpc_code_params *p, int32_t n
 int scldpc_full_bp_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                  const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
                                  int32_t *d_counters, uint32_t *d_erased_bits, void *stream);
+/* Several iteration caps from one decode: d_counters int32 [ncaps][ntrials][SCLDPC_NCOUNTERS] (cap-major: each cap's block
+ * is a [ntrials][SCLDPC_NCOUNTERS] array that scldpc_accumulate_run_device takes as it is).  Block k holds, on all eight
+ * counters, exactly what scldpc_full_bp_device_cn16 / _sock16 write with max_it = caps[k] on the same tables: on the BEC
+ * the flooding iterations do not depend on MaxNumIt, which only ends decodeBP's loop (BPF:1065), so one decode walked to
+ * the largest cap passes every smaller cap's end on the way.  caps is a HOST array of 1 .. SCLDPC_MAX_CAPS strictly
+ * increasing values >= 1 (0 = unlimited is not taken; a cap beyond reach, e.g. 1000000, is).  Same shapes as the
+ * *_supported queries above; no erased bitmap. */
+#define SCLDPC_MAX_CAPS 16
+int scldpc_full_bp_caps_device_cn16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                    const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                    const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream);
+int scldpc_full_bp_caps_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                      const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                      const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream);
 /* decodeBP of the trajectory build (BPT:900-1140) on the same tables: the iterations WITH their rows — per iteration
  * deg_1_iter, the VNs recovered and the position of the first erased VN (BPT:988, 1037-1038, 1051): d_rows int32
  * [ntrials][rows_cap][3]; d_counters[SCLDPC_C_ITERATIONS] says how many rows a trial wrote (rows beyond rows_cap are dropped).
