@@ -31,7 +31,7 @@ constexpr int kMaxDoped = 32;
 constexpr int kWorkCap = 1024;          // keys of buckets that span two CNs, per position (expected: 0.03 * S <= 250)
 
 struct S2Args {
-    int L, cns_pos, vns_pos, n, S, D, nb, shift, sbits, nw;
+    int L, cns_pos, vns_pos, n, S, D, nb, nw;
     int ntrials;                        // workgroup b samples trials b, b + gridDim.x, … (gridDim.x == ntrials unless persistent)
     int force_exact;                    // diagnostics: rank this CN position by the exact fallback (-1: none, -2: every position)
     int ndoped;
@@ -53,6 +53,15 @@ template <int KMAX, int ROWS, int CNMODE, bool PERSIST = false>
 __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_num_sgpr(72))) void sample_philox_v2_kernel(const S2Args a)
 {
     constexpr int DV = 4, DC_SHIFT = 3, E = 4 * KMAX;
+    // the bucket geometry follows from ROWS (nb = 1024 * ROWS histogram words of four fine buckets): shifts and masks are
+    // immediates, so no vector instruction takes a scalar operand for them (an SGPR source doubles a two-operand op's price)
+    constexpr int LG = ROWS == 1 ? 10 : ROWS == 2 ? 11 : ROWS == 4 ? 12 : 13;        // log2(nb) = socket bits
+    constexpr int KSHIFT = 32 - LG - 2;                                 // key >> KSHIFT = fine bucket
+    // One Philox call per thread (at most 4096 sockets per position): the scan leaves INCLUSIVE nibble prefixes in the
+    // word, so a key's first rank and its bucket's end are right shifts and masks, and the histogram's overflow is found
+    // from the scan's grand total instead of a per-key check.  Two calls per thread (KMAX = 2) keep the exclusive form.
+    constexpr bool INCL = KMAX == 1;
+    static_assert(ROWS * kThreads == (1 << LG) && (INCL ? ROWS <= 4 : ROWS == 8), "ROWS is 1, 2, 4 (KMAX 1) or 8 (KMAX 2)");
     extern __shared__ uint32_t lds[];
     uint32_t *hist = lds;                                               // nb words of four nibble-wide bucket counters
     uint32_t *gpk = lds + a.off_gpk;                                    // S words: packed keys of straddling buckets
@@ -64,8 +73,6 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int S = a.S, nb = a.nb;
     const int ncalls = S >> 2;                                          // S % 4 == 0 (checked on the host)
-    const int kshift = a.shift - 2;                                     // key >> kshift = fine bucket
-    const uint32_t lowmask = (1u << kshift) - 1u;
     bool own[KMAX];                                                     // call k of this thread: sockets 4*(tid + 1024 k) .. +3
 #pragma unroll
     for (int k = 0; k < KMAX; k++) own[k] = tid + k * kThreads < ncalls;
@@ -77,9 +84,12 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
         return CNMODE == 1 ? (uint16_t)((p - u) * a.vns_pos + t) : (uint16_t)sck;
     };
 
-    // hist word = [exclusive prefix:16 | n3:4 | n2:4 | n1:4 | n0:4]: four nibble-wide bucket counters in the low half
-    // (the atomic's return value is the key's arrival slot), the scan's prefix ORed into the high half.  Thread t owns
-    // words t*ROWS .. t*ROWS+ROWS-1 (wide LDS accesses).
+    // hist word while counting = [0:16 | n3:4 | n2:4 | n1:4 | n0:4]: four nibble-wide bucket counters (the atomic's return
+    // value is the key's arrival slot).  After the scan:
+    //   INCL:  [exclusive prefix:12 | i3:4 | i2:4 | i1:4 | i0:4 | 0:4] with ik = n0 + .. + nk, so bucket k's ranks are
+    //          [prefix + (word >> 4k & 15), prefix + (word >> 4k+4 & 15)) — valid while the word holds at most 15 keys;
+    //   else:  [exclusive prefix:16 | n3 n2 n1 n0], the lower buckets' counts summed at look-up time.
+    // Thread t owns words t*ROWS .. t*ROWS+ROWS-1 (wide LDS accesses).
     auto nib_sum = [](uint32_t x) {                                     // sum of the four nibbles of the low half
         const uint32_t v = (x & 0x0F0Fu) + ((x >> 4) & 0x0F0Fu);
         return (v + (v >> 8)) & 0xFFu;
@@ -129,23 +139,58 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
         STAMP(0);
         // ---- bucket histogram of this position's keys
         uint32_t key[E], slot[E], crowded = 0;
+        // byte address of a key's word = (bucket >> 2) * 4, nibble shift = (bucket & 3) * 4: right shifts and masks only
+        auto word_of = [](uint32_t k) { return (k >> KSHIFT) & ~3u; };
+        auto nib_of = [](uint32_t k) { return (k >> (KSHIFT - 2)) & 12u; };
 #pragma unroll
         for (int e = 0; e < E; e++) {
             key[e] = nxt[e];                                            // (threads without sockets hold zero keys and add zero)
-            const uint32_t b = key[e] >> kshift, sh = (b & 3u) * 4u;
-            slot[e] = (atomicAdd(&hist[b >> 2], (own[e >> 2] ? 1u : 0u) << sh) >> sh) & 0xFu;
-            crowded = max(crowded, slot[e]);
+            const uint32_t sh = nib_of(key[e]);
+            uint32_t *w = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(hist) + word_of(key[e]));
+            slot[e] = (atomicAdd(w, (own[e >> 2] ? 1u : 0u) << sh) >> sh) & 0xFu;
+            if constexpr (!INCL) crowded = max(crowded, slot[e]);
         }
         // A bucket count must fit its nibble (0.24 keys per bucket on average: 15 in one never happens in practice) and the
         // straddlers their worklist: when either fails the position is ranked again by the exact fallback below — same
-        // CN ids by construction, only slower — instead of trapping the process.
-        if (crowded >= 15u) wsum[kWaves + 1] = 1u;
+        // CN ids by construction, only slower — instead of trapping the process.  (INCL: a word of more than 15 keys,
+        // which includes a wrapped nibble, makes that word's scanned total smaller than its true count, so the scan's
+        // grand total falls short of S: one uniform compare for the whole position.)
+        if (!INCL && crowded >= 15u) wsum[kWaves + 1] = 1u;
         __syncthreads();
         STAMP(1);
 
         // ---- exclusive scan of the bucket counts: every thread scans its ROWS words, the wave scans the thread totals
         //      (DPP), the 16 wave totals meet in wsum; the global prefix goes into the words' high halves
-        {
+        bool ranked;                                                    // the histogram's ranks hold (else: exact fallback)
+        if constexpr (INCL) {
+            // one multiply per word: nibble k+1 of x * 0x111110 is n0 + .. + nk, nibble 5 the word's total again (no carries
+            // while the word holds at most 15 keys; else nibble 5 is below the true count and the grand total shows it)
+            uint32_t x[ROWS], t20[ROWS], tot20 = 0;
+            load_words(x);
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) {
+                x[r] *= 0x111110u;
+                t20[r] = x[r] & 0xF00000u;                              // the word's total << 20
+                tot20 += t20[r];
+            }
+            const uint32_t tot = tot20 >> 20, inc = wave_inclusive_scan(tot);
+            if (lane == 63) wsum[wave] = inc;
+            __syncthreads();
+            uint32_t winc = lane < kWaves ? wsum[lane] : 0u;          // the 16 wave totals: a scan within DPP row 0
+            const uint32_t wt = winc;
+            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x111, 0xF, 0xF, false);
+            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x112, 0xF, 0xF, false);
+            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x114, 0xF, 0xF, false);
+            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x118, 0xF, 0xF, false);
+            ranked = __builtin_amdgcn_readlane((int)winc, kWaves - 1) == S;
+            uint32_t pre20 = (inc - tot + (uint32_t)__builtin_amdgcn_readlane((int)(winc - wt), wave)) << 20;
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) {
+                x[r] = (x[r] & 0xFFFF0u) | pre20;
+                pre20 += t20[r];
+            }
+            store_words(x);
+        } else {
             uint32_t x[ROWS], v[ROWS], tot = 0;
             load_words(x);
 #pragma unroll
@@ -175,35 +220,86 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
             store_words(x);
         }
         __syncthreads();
+        if constexpr (!INCL) ranked = wsum[kWaves + 1] == 0u;
         STAMP(2);
 
         // ---- classify: every key gets rank g0 + arrival slot — any bijection onto its bucket's ranks gives the right CN
         //      (g0 / dc) when the bucket lies inside one block of dc ranks.  CN ids go into the ring, sockets into the
         //      rank-ordered stage.  Keys of buckets that span two CNs (3 %) are also put on a worklist for their true rank.
-        if (wsum[kWaves + 1] == 0u) {                                    // (an overflowed histogram has no ranks worth scattering by)
-            uint32_t h[E], rk[E], g0a[E], cnta[E], smask = 0;
+        // Worklist entry of a straddler: [bucket's end rank:16 | bucket's first rank:16], then its packed key
+        // pk = key << LG | socket (also stored at its provisional rank in gpk, where its bucket mates meet it): bucket mates
+        // share the key's top LG + 2 bits, so the shift drops none of the bits that order them.
+        if (ranked) {                                                   // (an overflowed histogram has no ranks worth scattering by)
+            uint32_t rk[E], g0a[E], g1a[E];
+            bool st[E];
+            if constexpr (INCL) {
+                uint32_t h[E];
 #pragma unroll
-            for (int e = 0; e < E; e++) h[e] = hist[own[e >> 2] ? (key[e] >> kshift) >> 2 : 0u];
+                for (int e = 0; e < E; e++) h[e] = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(hist) + word_of(key[e]));
 #pragma unroll
-            for (int e = 0; e < E; e++) {
-                const uint32_t k4 = ((key[e] >> kshift) & 3u) * 4u, x = h[e];
-                const uint32_t below = x & ((1u << k4) - 1u);            // the counters of the word's lower buckets
-                g0a[e] = (x >> 16) + (below & 0xFu) + ((below >> 4) & 0xFu) + ((below >> 8) & 0xFu);
-                cnta[e] = (x >> k4) & 0xFu;
-                rk[e] = g0a[e] + slot[e];
-                if (own[e >> 2] && ((g0a[e] + cnta[e] - 1u) >> DC_SHIFT) != (g0a[e] >> DC_SHIFT)) smask |= 1u << e;
+                for (int e = 0; e < E; e++) {
+                    const uint32_t t = h[e] >> nib_of(key[e]), pre = h[e] >> 20;
+                    g0a[e] = pre + (t & 0xFu);
+                    g1a[e] = pre + ((t >> 4) & 0xFu);
+                    rk[e] = g0a[e] + slot[e];
+                    st[e] = own[e >> 2] && ((g0a[e] ^ (g1a[e] - 1u)) >> DC_SHIFT) != 0u;
+                }
+            } else {
+                uint32_t h[E];
+#pragma unroll
+                for (int e = 0; e < E; e++) h[e] = hist[own[e >> 2] ? (key[e] >> KSHIFT) >> 2 : 0u];
+#pragma unroll
+                for (int e = 0; e < E; e++) {
+                    const uint32_t k4 = ((key[e] >> KSHIFT) & 3u) * 4u, x = h[e];
+                    const uint32_t below = x & ((1u << k4) - 1u);        // the counters of the word's lower buckets
+                    g0a[e] = (x >> 16) + (below & 0xFu) + ((below >> 4) & 0xFu) + ((below >> 8) & 0xFu);
+                    g1a[e] = g0a[e] + ((x >> k4) & 0xFu);
+                    rk[e] = g0a[e] + slot[e];
+                    st[e] = own[e >> 2] && ((g1a[e] - 1u) >> DC_SHIFT) != (g0a[e] >> DC_SHIFT);
+                }
             }
-            while (smask) {                                             // rare (3 % of the keys): one short divergent loop
-                const uint32_t e = (uint32_t)__ffs((int)smask) - 1u;
-                smask &= smask - 1u;
-                uint32_t ky = key[0], sl = slot[0], g0 = g0a[0], cnt = cnta[0];
+            if constexpr (INCL) {
+                // the wave's straddlers (3 % of the keys) take consecutive worklist entries: ballots and one LDS atomic per
+                // wave, no divergent loop
+                unsigned long long vote[E], anyv = 0;
+                int total = 0;
 #pragma unroll
-                for (int f = 1; f < E; f++)
-                    if (e == (uint32_t)f) { ky = key[f]; sl = slot[f]; g0 = g0a[f]; cnt = cnta[f]; }
-                const uint32_t pk = ((ky & lowmask) << a.sbits) | (uint32_t)((tid + (int)(e >> 2) * kThreads) * 4 + (int)(e & 3u));
-                gpk[g0 + sl] = pk;
-                const int w = atomicAdd(reinterpret_cast<int *>(&wsum[kWaves]), 1);
-                if (w < kWorkCap) { wl[2 * w] = g0 | (cnt << 16) | (sl << 20); wl[2 * w + 1] = pk; }
+                for (int e = 0; e < E; e++) { vote[e] = __builtin_amdgcn_ballot_w64(st[e]); anyv |= vote[e]; total += __builtin_popcountll(vote[e]); }
+                if (anyv) {
+                    int base = 0;
+                    if (lane == 0) base = atomicAdd(reinterpret_cast<int *>(&wsum[kWaves]), total);
+                    base = __builtin_amdgcn_readfirstlane(base);
+                    // past the list's end the entries are not written: the count still grows, and the exact fallback ranks
+                    // the position
+                    const bool fits = base + total <= kWorkCap;
+#pragma unroll
+                    for (int e = 0; e < E; e++) {
+                        if (st[e]) {
+                            const uint32_t w = __builtin_amdgcn_mbcnt_hi((uint32_t)(vote[e] >> 32),
+                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)vote[e], (uint32_t)base));
+                            const uint32_t pk = (key[e] << LG) | sock(e);
+                            gpk[rk[e]] = pk;
+                            if (fits) { wl[2 * w] = g0a[e] | (g1a[e] << 16); wl[2 * w + 1] = pk; }
+                        }
+                        base += __builtin_popcountll(vote[e]);
+                    }
+                }
+            } else {
+                uint32_t smask = 0;
+#pragma unroll
+                for (int e = 0; e < E; e++) smask |= (st[e] ? 1u : 0u) << e;
+                while (smask) {                                         // rare (3 % of the keys): one short divergent loop
+                    const uint32_t e = (uint32_t)__ffs((int)smask) - 1u;
+                    smask &= smask - 1u;
+                    uint32_t ky = key[0], r0 = rk[0], g0 = g0a[0], g1 = g1a[0];
+#pragma unroll
+                    for (int f = 1; f < E; f++)
+                        if (e == (uint32_t)f) { ky = key[f]; r0 = rk[f]; g0 = g0a[f]; g1 = g1a[f]; }
+                    const uint32_t pk = (ky << LG) | (uint32_t)((tid + (int)(e >> 2) * kThreads) * 4 + (int)(e & 3u));
+                    gpk[r0] = pk;
+                    const int w = atomicAdd(reinterpret_cast<int *>(&wsum[kWaves]), 1);
+                    if (w < kWorkCap) { wl[2 * w] = g0 | (g1 << 16); wl[2 * w + 1] = pk; }
+                }
             }
 #pragma unroll
             for (int k = 0; k < KMAX; k++) {                            // provisional CN ids (final unless on the worklist)
@@ -232,10 +328,11 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
             for (int r = 0; r < ROWS; r++) z[r] = 0;
             store_words(z);
             int nwork = (int)wsum[kWaves];                              // 3 % of S on average (<= 250 keys); the list holds 1024
-            const bool exact = wsum[kWaves + 1] != 0u || nwork > kWorkCap || a.force_exact == p || a.force_exact == -2;
+            const bool exact = !ranked || nwork > kWorkCap || a.force_exact == p || a.force_exact == -2;
             if (exact) {
                 // every key's true rank among all S keys, ties by socket (what the histogram path computes where it matters):
                 // S comparisons per key — never taken in a real run, see above
+                asm volatile("; ledger: cold");                         // (no instruction: tools/isa_ledger.py skips this path)
                 nwork = 0;
 #pragma unroll
                 for (int e = 0; e < E; e++) if (own[e >> 2]) gpk[sock(e)] = key[e];
@@ -263,11 +360,10 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
             }
             for (int w = tid; w < nwork; w += kThreads) {
                 const uint32_t ea = wl[2 * w], pk = wl[2 * w + 1];
-                const uint32_t g0 = ea & 0xFFFFu, cnt = (ea >> 16) & 0xFu, sl = ea >> 20;
-                uint32_t r = g0;
-                for (uint32_t m = 0; m < cnt; m++)
-                    if (m != sl) r += gpk[g0 + m] < pk;
-                const uint32_t sck = pk & ((1u << a.sbits) - 1u);
+                uint32_t r = ea & 0xFFFFu;                              // its rank: the first rank + the mates below it
+#pragma unroll 1
+                for (uint32_t m = ea & 0xFFFFu; m < (ea >> 16); m++) r += gpk[m] < pk;     // (itself included: not below)
+                const uint32_t sck = pk & ((1u << LG) - 1u);
                 if constexpr (CNMODE != 0) stage[r] = stage_entry(p, sck);
                 fix[sck] = (uint16_t)(r >> DC_SHIFT);
             }
@@ -660,7 +756,7 @@ int launch_v2(const char *who, int cnmode, const scldpc_code_params *p, uint64_t
     a.n = scldpc::n_of(p); a.S = p->cns_pos * p->dc; a.D = p->L + p->dv - 1; a.nw = scldpc::nw_of(p);
     int lg = 10;                                    // nb = power of two >= max(S, kThreads): the histogram of sampler.hip
     while ((1 << lg) < a.S) lg++;
-    a.nb = 1 << lg; a.shift = 32 - lg; a.sbits = lg;
+    a.nb = 1 << lg;
     a.ndoped = ndoped;
     for (int d = 0; d < ndoped; d++) {
         if (doped_positions[d] < 0 || doped_positions[d] >= p->L)
