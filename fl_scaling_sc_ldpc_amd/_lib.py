@@ -45,6 +45,7 @@ EXPORTS = (
     "scldpc_full_bp_sock16_supported", "scldpc_full_bp_fixpoint_device_sock16", "scldpc_full_bp_device_sock16",
     "scldpc_full_bp_traj_device_cn16", "scldpc_full_bp_traj_device_sock16",
     "scldpc_full_bp_caps_device_cn16", "scldpc_full_bp_caps_device_sock16",
+    "scldpc_full_bp_wide_supported", "scldpc_full_bp_device_wide", "scldpc_full_bp_traj_device_wide",
 )
 
 
@@ -123,6 +124,9 @@ def lib():
     L.scldpc_full_bp_traj_device_sock16.argtypes = L.scldpc_full_bp_traj_device_cn16.argtypes
     L.scldpc_full_bp_caps_device_cn16.argtypes = [pp, i32, vp, vp, vp, i32, vp, i32, vp, vp]
     L.scldpc_full_bp_caps_device_sock16.argtypes = L.scldpc_full_bp_caps_device_cn16.argtypes
+    L.scldpc_full_bp_wide_supported.argtypes = [pp]
+    L.scldpc_full_bp_device_wide.argtypes = L.scldpc_full_bp_device_cn16.argtypes
+    L.scldpc_full_bp_traj_device_wide.argtypes = L.scldpc_full_bp_traj_device_cn16.argtypes
     L.scldpc_full_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, u64, vp]
     L.scldpc_sw_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_sample_philox_device_adj16.argtypes = L.scldpc_sample_philox_device.argtypes

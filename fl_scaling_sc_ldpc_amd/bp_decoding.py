@@ -130,12 +130,21 @@ def write_risultati(path, sim, point):
         f.write(point.row())
 
 
+# Whether Simulator(wide=None) takes the wide 4-bit level decoder where it applies: decided by the end-to-end A/B of
+# tools/traj_wide_speedup.py against the first-generation path — 1.62x and 1.78x at N = 5000, spread below 0.3 %
+# (profiles/traj_wide_speedup.json)
+WIDE_BY_DEFAULT = True
+
+
 class Simulator:
     """Batched Monte-Carlo driver around the device decoders."""
 
     def __init__(self, p, decoder="full", W=0, max_it=0, init_it=0, is_term=True, doped=(), batch=2048,
                  rng="philox", seed=1, device=None, rows_cap=0, schedule="flooding", shard_frames=True, index=0,
-                 verbose=False, caps=None):
+                 verbose=False, caps=None, wide=None):
+        # wide: the 1024-thread 4-bit level decoder for trials of more than 65536 CNs (full_bp_small wide).  None = where
+        # WIDE_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path, for A/B and tests)
+        self.want_wide = wide
         self.p, self.decoder, self.W, self.max_it, self.init_it = p, decoder, W, max_it, init_it
         # caps: several MaxNumIt from one decode (run_point_caps; the level-synchronous 4-bit decoder only)
         self.caps = E.check_caps(caps) if caps is not None else None
@@ -160,13 +169,12 @@ class Simulator:
             raise ValueError("rng must be 'philox' or 'glibc'")
         self._alloc()
 
-    def _alloc(self):
-        p, batch = self.p, self.batch
+    def _select(self):
+        """Which kernels take this configuration (no device work): sock, gen2, lvl2, ring2, wide.  Returns the dtype of the
+        VN -> CN table."""
+        p = self.p
         # compact 2-byte position-local ids for device-sampled codes; the reference's int32 VNdegree for host replays
         adj_dtype = torch.int16 if (self.rng == "philox" and p.cns_pos <= 65536) else torch.int32
-        self.d_adj = torch.empty((batch, p.n, p.dv), dtype=adj_dtype, device=self.device)
-        self.d_ch = torch.empty((batch, p.nw), dtype=torch.int32, device=self.device)
-        self.d_cnt = torch.empty((batch, NCOUNTERS), dtype=torch.int32, device=self.device)
         # full BP on the BASELINE ensemble family: the second-generation pair (sampler_v2 + the 4-bits-per-CN decoder) needs
         # the CN -> VN table next to the VN -> CN one.  gen2: unlimited, no iteration statistics (fixpoint); lvl2: the same
         # decoder walked one flooding iteration per round — iteration caps (the published ..._500it_... tables) and counts
@@ -179,18 +187,33 @@ class Simulator:
         # second-generation sampler takes the ensemble (else E.sw_bp builds it in a pass of its own)
         self.ring2 = (self.rng == "philox" and self.decoder == "sw" and adj_dtype == torch.int16
                       and E.sock16_supported(p) and E.sw_ring_supported(p, self.W))
+        # more than 65536 CNs per trial (bp_traj's default N = 5000; L = 100, N = 2000): the wide form of the level decoder,
+        # on the CN -> socket table.  An unlimited fixpoint run keeps full_bp_fixpoint (there is no wide fixpoint kernel).
+        fix = self.schedule == "fixpoint" and self.rows_cap == 0 and (self.max_it <= 0 or self.max_it >= 1000000)
+        use = WIDE_BY_DEFAULT if self.want_wide is None else bool(self.want_wide)
+        self.wide = bool(use and small and adj_dtype == torch.int16 and not cn16 and not fix and self.caps is None
+                         and E.full_bp_wide_supported(p))
+        self.wide_sock = self.wide and E.sock16_supported(p)      # the second-generation sampler emits the socket table
+        if self.caps is not None and not (self.lvl2 and self.rows_cap == 0 and not self.doped):
+            raise ValueError("caps: the fused decode takes Philox sampling, no doping and an ensemble of the "
+                             "level-synchronous 4-bit decoder (caps_sequential_reason)")
+        return adj_dtype
+
+    def _alloc(self):
+        p, batch = self.p, self.batch
+        adj_dtype = self._select()
+        self.d_adj = torch.empty((batch, p.n, p.dv), dtype=adj_dtype, device=self.device)
+        self.d_ch = torch.empty((batch, p.nw), dtype=torch.int32, device=self.device)
+        self.d_cnt = torch.empty((batch, NCOUNTERS), dtype=torch.int32, device=self.device)
         self.d_cn = (torch.empty((batch, p.nk, p.dc), dtype=torch.int16, device=self.device)
-                     if (self.gen2 or self.lvl2 or self.ring2) else None)
+                     if (self.gen2 or self.lvl2 or self.ring2 or self.wide) else None)
         if self.caps is not None:
-            if not (self.lvl2 and self.rows_cap == 0 and not self.doped):
-                raise ValueError("caps: the fused decode takes Philox sampling, no doping and an ensemble of the "
-                                 "level-synchronous 4-bit decoder (caps_sequential_reason)")
             self.d_cnt_caps = torch.empty(len(self.caps) * batch * NCOUNTERS, dtype=torch.int32, device=self.device)
         if self.verbose:
             print("[scldpc] kernels: " + self.kernel_choice(), file=sys.stderr, flush=True)
 
     def kernel_choice(self):
-        """Which device kernels this configuration runs (the second-generation ones take dv = 4, dc = 8, N <= 2048)."""
+        """Which device kernels this configuration runs."""
         if self.decoder == "sw":
             return ("sampler_v2 (CN->socket table) + sw_ring (window state in LDS)" if self.ring2 else
                     "sampler (first generation) + " + ("sw_ring + cn_sockets pass" if E.sw_ring_supported(self.p, self.W)
@@ -204,8 +227,13 @@ class Simulator:
             return samp + " + full_bp_small level-synchronous with %d cap checkpoints per decode (4-bit CN counts)" % len(self.caps)
         if self.lvl2:
             return samp + " + full_bp_small level-synchronous (4-bit CN counts" + (", trajectory rows)" if self.rows_cap else ")")
+        if self.wide:
+            return ("sampler_v3 (CN->socket table)" if self.wide_sock else samp + " + cn_sockets pass") + \
+                " + full_bp_small wide level-synchronous (4-bit CN counts, 32-bit queue entries" + \
+                (", trajectory rows)" if self.rows_cap else ")")
         return samp + " + full_bp (16-bit CN words" + (", trajectory rows)" if self.rows_cap else ")") + \
-            ": the second-generation decoder takes dv = 4, dc = 8, N <= 2048 with device sampling"
+            ": the 4-bit decoders take dv = 4, dc = 8 with device sampling and at most 65536 CNs per trial, or (the wide " \
+            "form, unless switched off) a state that leaves 1024 queue entries in one CU's LDS"
 
     def _accumulate(self, allcnt, run, stop_frame_err):
         return E.accumulate_run(allcnt, run, stop_frame_err)
@@ -226,6 +254,9 @@ class Simulator:
                                   sockets=self.sock, rows_cap=self.rows_cap if want_rows else 0)
         if self.schedule == "fixpoint" and not want_rows and (self.max_it <= 0 or self.max_it >= 1000000):
             return E.full_bp_fixpoint(self.p, adj, ch, is_term=self.is_term, counters=cnt)    # no iteration counts
+        if self.wide:
+            return E.full_bp_wide(self.p, adj, self.d_cn[:nb], ch, max_it=self.max_it, is_term=self.is_term,
+                                  rows_cap=self.rows_cap if want_rows else 0, counters=cnt)
         return E.full_bp(self.p, adj, ch, max_it=self.max_it, is_term=self.is_term,
                          rows_cap=self.rows_cap if want_rows else 0, counters=cnt)
 
@@ -242,12 +273,14 @@ class Simulator:
         elif self.rng == "philox" and (self.gen2 or self.lvl2):
             E.sample_philox_cn16(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
                                  out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
-        elif self.rng == "philox" and self.ring2:
+        elif self.rng == "philox" and (self.ring2 or self.wide_sock):
             E.sample_philox_sock16(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
                                    out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
         elif self.rng == "philox":
             E.sample_philox(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
                             out=(self.d_adj[:nb], self.d_ch[:nb]))
+            if self.wide:                          # more sockets per position than the second-generation sampler takes
+                E.cn_sockets(self.p, self.d_adj[:nb], out=self.d_cn[:nb])
         else:
             adj, ch = self.glibc.next_frames(nb, eps, self.doped)
             self.d_adj[:nb].copy_(torch.from_numpy(adj))
@@ -384,6 +417,9 @@ def caps_sequential_reason(p, rng, num_doped, schedule):
     if schedule != "flooding":
         return "--schedule %s has no iteration caps" % schedule
     if not (E.cn16_supported(p) or E.full_bp_sock16_supported(p)):
+        if E.full_bp_wide_supported(p):
+            return ("more than 65536 CNs per trial: the wide form of the level-synchronous 4-bit decoder has no cap "
+                    "checkpoints")
         return "the level-synchronous 4-bit decoder takes dv = 4, dc = 8 and at most 65536 CNs per trial"
     return None
 
@@ -569,7 +605,8 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                         is_term=is_term, doped=doped, batch=opts.batch, rng=opts.rng, seed=opts.seed,
                         rows_cap=opts.rows_cap if prog == "bp_traj" else 0, schedule=getattr(opts, "schedule", "flooding"),
                         shard_frames=shard == "frames", device=getattr(opts, "device", None), index=replica,
-                        verbose=rank == 0 and not opts.quiet)
+                        verbose=rank == 0 and not opts.quiet,
+                        wide={"auto": None, "on": True, "off": False}[getattr(opts, "wide", "auto")])
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     t0 = time.time()
@@ -671,6 +708,9 @@ def _parser(prog):
         ap.add_argument("--caps", type=_caps_list, default=None, metavar="K1,K2,…",
                         help="also write the files of these MAX_IT (one file per cap, each the file of a run with that "
                              "MAX_IT); from one decode per frame where that is exact, else one run per cap")
+    ap.add_argument("--wide", choices=("auto", "on", "off"), default="auto",
+                    help="full BP of trials with more than 65536 CNs (e.g. the default N = 5000): the wide 4-bit level "
+                         "decoder (on), the first-generation decoder (off), or the measured default (auto); same files")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")

@@ -21,6 +21,11 @@
 // queue (the first one or two) take it from a snapshot bitmap, one queue-full at a time; that bitmap costs a seventh trial
 // per CU (six fit).
 //
+// WIDE is the LEVEL machine (with or without the trajectory rows) for trials of more than 65536 CNs — bp_traj's shipped N = 5000,
+// L = 50 has 132 500: queue entries are 32-bit CN ids, one 1024-thread workgroup takes a CU and all of its 160 KiB, and the CN ->
+// socket table comes from scldpc_cn_sockets_device where the second-generation sampler stops (8192 sockets per position).
+// Socket table only; the fixpoint form (its private-queue carve assumes four waves), PERSIST and CAPS have no wide form.
+//
 // Outputs: the counters of scldpc_full_bp_fixpoint_device (everything decodeBP reports except the iteration count), or
 // with LEVEL all of scldpc_full_bp_device's counters.
 // The size-2 stopping-set expurgation only looks at what the reference reports: the FIRST position with a positive
@@ -29,6 +34,7 @@
 #include "kernel_util.h"
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -46,7 +52,7 @@ struct SmArgs {
     int max_it;                                     // LEVEL: MaxNumIt, <= 0 = unlimited
     int rows_cap;                                   // TRAJ: rows kept per trial
     int32_t *rows;                                  // TRAJ: [T][rows_cap][3] = deg_1_iter, recovered, first erased position
-    int off_U, off_q0, off_q1, off_pos, off_scal, off_fb, total, qcap;      // LDS offsets in 32-bit words; qcap in entries (u16)
+    int off_U, off_q0, off_q1, off_pos, off_scal, off_fb, total, qcap;      // LDS offsets in 32-bit words; qcap in entries (u16; WIDE: u32)
     const uint16_t *vn_adj16;                       // [T][n][4]   CN index local to its position
     const uint16_t *cn_adj16;                       // [T][nk][8]  VNs of every CN (0xFFFF: none); SOCK: their sockets dv*t + i instead
     const uint32_t *chan;
@@ -65,14 +71,20 @@ struct SmArgs {
 // the loop (BPF:1065): where a single-cap decode tests it, the decoder takes a checkpoint instead — the counters that decode
 // would report, written to that cap's block of counters [ncaps][ntrials][8] — and goes on to the next cap.  Caps the decode
 // does not reach (a stop test or a broken invariant ended it first) get its final state.
-template <int BLOCK, bool LEVEL, bool PERSIST, bool SOCK, bool TRAJ = false, bool CAPS = false>
-__global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_sgpr(96))) void full_bp_small_kernel(const SmArgs a)
+// WIDE (LEVEL or LEVEL + TRAJ with SOCK, nothing else): queue entries are 32-bit CN ids and ONE 1024-thread workgroup owns
+// the CU and all of its LDS (four waves per SIMD, at most 128 VGPRs) — trials of more than 65536 CNs, e.g. bp_traj's default
+// N = 5000, L = 50 (nk = 132 500).  There is no wide fixpoint form (the private-queue carve below assumes four waves), no wide
+// PERSIST and no wide CAPS form.
+template <int BLOCK, bool LEVEL, bool PERSIST, bool SOCK, bool TRAJ = false, bool CAPS = false, bool WIDE = false>
+__global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((amdgpu_num_sgpr(96))) void full_bp_small_kernel(const SmArgs a)
 {
+    static_assert(!WIDE || (BLOCK == 1024 && LEVEL && SOCK && !PERSIST && !CAPS), "the wide form: LEVEL [+ TRAJ], socket table");
+    using QT = std::conditional_t<WIDE, uint32_t, uint16_t>;             // a queue entry: a CN id
     constexpr int kWaves = BLOCK / 64;
     extern __shared__ uint32_t lds[];
     uint32_t *cnt = lds;                                                 // nk nibbles
     uint32_t *U = lds + a.off_U;
-    uint16_t *q[2] = {reinterpret_cast<uint16_t *>(lds + a.off_q0), reinterpret_cast<uint16_t *>(lds + a.off_q1)};
+    QT *q[2] = {reinterpret_cast<QT *>(lds + a.off_q0), reinterpret_cast<QT *>(lds + a.off_q1)};
     int *pos_cnt = reinterpret_cast<int *>(lds + a.off_pos);
     int *pos_ss = pos_cnt + a.L;
     int *scal = reinterpret_cast<int *>(lds + a.off_scal);
@@ -181,7 +193,7 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
         return z;
     };
     // a wave appends its lanes' out[] entries to queue qn behind *push (one prefix scan + one LDS atomic per wave)
-    auto append = [&](const uint32_t (&out)[4], int *push, uint16_t *qn, bool &overflow) {
+    auto append = [&](const uint32_t (&out)[4], int *push, QT *qn, bool &overflow) {
         const int mine = (out[0] != 0u) + (out[1] != 0u) + (out[2] != 0u) + (out[3] != 0u);
         const int incl = (int)wave_inclusive_scan((uint32_t)mine);
         const int tot = __builtin_amdgcn_readlane(incl, 63);
@@ -191,7 +203,7 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
             int idx = __builtin_amdgcn_readfirstlane(base) + incl - mine;
 #pragma unroll
             for (int i = 0; i < 4; i++)
-                if (out[i]) { if (idx < qcap) qn[idx] = (uint16_t)(out[i] - 1u); else overflow = true; idx++; }
+                if (out[i]) { if (idx < qcap) qn[idx] = (QT)(out[i] - 1u); else overflow = true; idx++; }
         }
     };
 
@@ -294,7 +306,7 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
         ne = nch;
         for (;;) {
             const int g = iter % 3, gn = (iter + 1) % 3;
-            uint16_t *qc = q[iter & 1], *qn = q[(iter + 1) & 1];
+            QT *qc = q[iter & 1], *qn = q[(iter + 1) & 1];
             if (tid == 0) { scal[LV_PUSH + gn] = 0; scal[LV_DROP + gn] = 0; scal[LV_REM + gn] = 0; scal[LV_OVF + gn] = 0; }
             int *push = &scal[LV_PUSH + g];                              // counts every 2 -> 1, queued or not
             bool overflow = false;
@@ -340,7 +352,7 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
                         while (y) {
                             const int k = __ffs((int)y) - 1;
                             y &= y - 1;
-                            if (idx < qcap) qc[idx] = (uint16_t)(w * 8 + k); else left |= 1u << k;
+                            if (idx < qcap) qc[idx] = (QT)(w * 8 + k); else left |= 1u << k;
                             idx++;
                         }
                         if (mine) fb[w] = (uint8_t)left;
@@ -359,7 +371,12 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
             STAMP(4);                                                    // (LEVEL) this wave's releases of the iteration
             {   // one reduction for both counts: a CN is queued once in its life and an iteration's entries are dealt to the four
                 // waves, so a wave releases at most nk / 4 + 64 <= 16 448 VNs per iteration (15 bits) and zeroes at most four
-                // times as many CNs (17 bits)
+                // times as many CNs (17 bits).
+                // WIDE: 16 waves, and a scan round runs several queue-fulls.  A queue-full of m entries gives a wave at most
+                // m / 16 + 64 of them; an iteration's queue-fulls hold each CN at most once (sum of m <= nk) and all but the
+                // last are full (at most nk / qcap + 1 of them), so a wave releases at most nk / 16 + 64 (nk / qcap + 1) VNs
+                // per iteration.  wide_shape() refuses shapes where that exceeds 32 767 (with qcap >= 1024 and the LDS's
+                // nk < 190 000 it is below 23 900), and four times as many zeroed CNs still fit the upper 17 bits.
                 const uint32_t both = (uint32_t)wave_sum((int)((uint32_t)removed | ((uint32_t)drops << 15)));
                 removed = (int)(both & 0x7FFFu); drops = (int)(both >> 15);
             }
@@ -431,7 +448,7 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
         int ncur = 0;
         bool scan = true;
         for (;;) {
-            uint16_t *qc = q[rounds & 1], *qn = q[(rounds + 1) & 1];
+            QT *qc = q[rounds & 1], *qn = q[(rounds + 1) & 1];
             if (scan) {
                 // every CN < cn_lim whose count is one right now, compacted into qc
                 for (int w0 = wave * 64; w0 < a.ncw; w0 += BLOCK) {
@@ -448,7 +465,7 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
                     while (z) {
                         const int k = (__ffs((int)z) - 1) >> 2;
                         z &= z - 1;
-                        if (idx < qcap) qc[idx] = (uint16_t)(w * 8 + k);
+                        if (idx < qcap) qc[idx] = (QT)(w * 8 + k);
                         idx++;
                     }
                 }
@@ -468,12 +485,12 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
                 }
             } else {
                 // private phase: wave w takes entries w, w + kWaves, … into its own part of qn and runs to exhaustion
-                uint16_t *mine = qn + wave * wcap;
+                QT *mine = qn + wave * wcap;
                 int cntw = (ncur - wave + kWaves - 1) / kWaves, cur = 0;
                 if (cntw < 0) cntw = 0;
                 if (lane < cntw) mine[lane] = qc[wave + lane * kWaves];
                 while (cntw > 0) {
-                    uint16_t *src = mine + cur * half_cap, *dst = mine + (cur ^ 1) * half_cap;
+                    QT *src = mine + cur * half_cap, *dst = mine + (cur ^ 1) * half_cap;
                     int ncnt = 0;
                     for (int b0 = 0; b0 < cntw; b0 += 64) {
                         uint32_t out[4] = {0, 0, 0, 0};
@@ -484,7 +501,7 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
                             int idx = ncnt + incl - mine_n;
     #pragma unroll
                             for (int i = 0; i < 4; i++)
-                                if (out[i]) { if (idx < half_cap) dst[idx] = (uint16_t)(out[i] - 1u); else overflow = true; idx++; }
+                                if (out[i]) { if (idx < half_cap) dst[idx] = (QT)(out[i] - 1u); else overflow = true; idx++; }
                             ncnt += __builtin_amdgcn_readlane(incl, 63);
                         }
                     }
@@ -536,7 +553,9 @@ __global__ __launch_bounds__(BLOCK, PERSIST ? 8 : 7) __attribute__((amdgpu_num_s
     }
 }
 
-int make_args(const scldpc_code_params *p, int32_t is_term, SmArgs *a, int per_cu, bool level = false)
+// wide: the carve of the 1024-thread form — 32-bit queue entries (one per word), and no 2048-word cap on a queue: that cap was
+// tuned for seven workgroups per CU, the wide form's one workgroup takes what the state leaves
+int make_args(const scldpc_code_params *p, int32_t is_term, SmArgs *a, int per_cu, bool level = false, bool wide = false)
 {
     const int n = scldpc::n_of(p), nk = scldpc::nk_of(p);
     a->L = p->L; a->V = p->vns_pos; a->C = p->cns_pos; a->n = n; a->nk = nk;
@@ -551,9 +570,9 @@ int make_args(const scldpc_code_params *p, int32_t is_term, SmArgs *a, int per_c
     a->off_fb = level ? take((a->ncw + 3) / 4) : 0;                      // snapshot bytes of the scan rounds
     const int budget = scldpc::kMaxLdsBytes / per_cu / 4 - 128;           // words per workgroup
     int qwords = ((budget - off) / 2) & ~3;                              // per queue; two uint16 entries per word
-    if (qwords > 2048) qwords = 2048;
+    if (qwords > 2048 && !wide) qwords = 2048;
     if (qwords < 128) return -1;
-    a->qcap = 2 * qwords;
+    a->qcap = wide ? qwords : 2 * qwords;
     a->off_q0 = take(qwords);
     a->off_q1 = take(qwords);
     a->total = off;
@@ -563,6 +582,8 @@ int make_args(const scldpc_code_params *p, int32_t is_term, SmArgs *a, int per_c
 constexpr int kBlockSmall = 256;        // threads per trial
 constexpr int kPerCu = 7;               // workgroups per CU the LDS carve aims at (SGPRs <= 96, VGPRs <= 72)
 constexpr int kSwitchWidth = 128;       // frontier entries below which the waves go private
+constexpr int kBlockWide = 1024;        // the wide form: one workgroup per CU, four waves per SIMD
+constexpr int kWideMinQueue = 1024;     // entries per queue below which the wide form is not worth selecting
 static_assert(kSwitchWidth <= 64 * (kBlockSmall / 64), "a wave takes at most one frontier entry per lane into its private queue");
 
 }  // namespace
@@ -579,6 +600,35 @@ bool small_shape(const scldpc_code_params *p)
            scldpc::magic_of(p->cns_pos, scldpc::nk_of(p), &m);
 }
 }  // namespace
+
+namespace {
+// Which limit keeps the wide form from this ensemble (nullptr: none).  The LEVEL carve at one workgroup per CU must leave
+// kWideMinQueue entries per queue (a shorter queue would still decode correctly — overflow falls back to scan rounds — but is
+// no fast path), and the packed reduction of the kernel needs nk / 16 + 64 (nk / qcap + 1) <= 32 767 (see there).
+const char *wide_limit(const scldpc_code_params *p)
+{
+    if (scldpc::check_params(p)) return "invalid code parameters";
+    if (p->dv != 4 || p->dc != 8) return "takes dv = 4, dc = 8 only";
+    if ((int64_t)p->vns_pos * p->dv > 65535) return "sockets: vns_pos * dv must fit 16 bits (at most 65535)";
+    if (p->cns_pos > 65536) return "sockets: at most 65536 CNs per position (16-bit position-local CN ids)";
+    const int64_t n64 = (int64_t)p->L * p->vns_pos, nk64 = (int64_t)(p->L + p->dv - 1) * p->cns_pos;
+    if (n64 / 8 + nk64 / 2 > scldpc::kMaxLdsBytes) return "LDS: the CN counts and VN bits of a trial exceed 160 KiB";
+    SmArgs a{};
+    uint32_t m;
+    if (!scldpc::magic_of(p->vns_pos, scldpc::n_of(p) + 32, &m) || !scldpc::magic_of(p->cns_pos, scldpc::nk_of(p), &m))
+        return "no exact multiply-high division for this vns_pos / cns_pos";
+    if (make_args(p, 1, &a, 1, true, true) != 0) return "LDS: the CN counts and VN bits of a trial leave no room for the queues";
+    if (a.qcap < kWideMinQueue) return "queue: the LDS left by the state holds fewer than 1024 entries per queue";
+    if (a.nk / 16 + 64 * (a.nk / a.qcap + 1) > 32767) return "queue: a wave's releases per iteration could exceed 15 bits";
+    return nullptr;
+}
+}  // namespace
+
+// 1 when the _wide forms take this ensemble: 32-bit queue entries, one 1024-thread workgroup per CU
+extern "C" int scldpc_full_bp_wide_supported(const scldpc_code_params *p)
+{
+    return wide_limit(p) == nullptr;
+}
 
 // 1 when scldpc_full_bp_fixpoint_device_cn16 takes this ensemble (global VN ids in the CN -> VN table: n < 65535)
 extern "C" int scldpc_full_bp_cn16_supported(const scldpc_code_params *p)
@@ -677,7 +727,58 @@ int launch_caps(const char *who, bool sock, const scldpc_code_params *p, int32_t
     return SCLDPC_OK;
 }
 
+// the wide level-synchronous decoder (LEVEL or LEVEL + TRAJ, socket table): one workgroup per trial, one per CU
+int launch_wide(const char *who, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
+                int32_t *d_counters, uint32_t *d_erased_bits, void *stream, int32_t *d_rows, int32_t rows_cap)
+{
+    if (d_rows && rows_cap <= 0) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: d_rows given but rows_cap <= 0", who);
+    if (int rc = scldpc::check_params(p)) return rc;
+    if (const char *why = wide_limit(p)) return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
+    if (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj16 || !d_cn_sock16 || !d_chan_bits)))
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
+    if (ntrials == 0) return SCLDPC_OK;
+    SmArgs a{};
+    if (make_args(p, is_term, &a, 1, true, true) != 0 || 4u * (size_t)a.total > (size_t)scldpc::kMaxLdsBytes)
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: LDS: the CN counts and VN bits do not fit", who);
+    scldpc::magic_of(p->vns_pos, a.n + 32, &a.magic_v);
+    scldpc::magic_of(p->cns_pos, a.nk, &a.magic_c);
+    a.vn_adj16 = d_vn_adj16; a.cn_adj16 = d_cn_sock16; a.chan = d_chan_bits;
+    a.counters = d_counters; a.erased_out = d_erased_bits;
+    a.kswitch = kSwitchWidth;
+    a.ntrials = ntrials;
+    a.rows = d_rows; a.rows_cap = d_rows ? rows_cap : 0;
+    a.max_it = max_it;
+    void (*kern)(const SmArgs) = d_rows ? full_bp_small_kernel<kBlockWide, true, false, true, true, false, true>
+                                        : full_bp_small_kernel<kBlockWide, true, false, true, false, false, true>;
+    const size_t lds_bytes = 4u * (size_t)a.total;
+    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
+    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(kBlockWide), lds_bytes, static_cast<hipStream_t>(stream), a);
+    SCLDPC_HIP_CHECK(hipGetLastError());
+    return SCLDPC_OK;
+}
+
 }  // namespace
+
+// The level-synchronous decoder for trials of more than 65536 CNs (32-bit queue entries, a 1024-thread workgroup per CU):
+// arguments, counters and rows exactly as scldpc_full_bp_device_sock16 / scldpc_full_bp_traj_device_sock16
+extern "C" int scldpc_full_bp_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                          const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
+                                          int32_t is_term, int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
+{
+    return launch_wide("scldpc_full_bp_device_wide", p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term,
+                       d_counters, d_erased_bits, stream, nullptr, 0);
+}
+
+extern "C" int scldpc_full_bp_traj_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                               const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
+                                               int32_t is_term, int32_t *d_counters, int32_t *d_rows, int32_t rows_cap,
+                                               uint32_t *d_erased_bits, void *stream)
+{
+    if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_wide: null d_rows");
+    return launch_wide("scldpc_full_bp_traj_device_wide", p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term,
+                       d_counters, d_erased_bits, stream, d_rows, rows_cap);
+}
 
 extern "C" int scldpc_full_bp_fixpoint_device_cn16(const scldpc_code_params *p, int32_t ntrials,
                                                    const uint16_t *d_vn_adj16, const uint16_t *d_cn_adj16,

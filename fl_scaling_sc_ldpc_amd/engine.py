@@ -352,6 +352,39 @@ def full_bp_cn16(p, d_adj16, d_cn16, d_chan, max_it=0, is_term=True, want_erased
     return {"counters": counters, "rows": None, "erased": erased}
 
 
+def full_bp_wide_supported(p):
+    """The (4,8) chain whose 4-bit state leaves at least 1024 32-bit queue entries per queue in one CU's LDS (e.g. L = 50,
+    N = 5000; L = 100, N = 2000): scldpc_full_bp_device_wide takes it."""
+    return bool(lib().scldpc_full_bp_wide_supported(C.byref(p)))
+
+
+def full_bp_wide(p, d_adj16, d_cn_sock, d_chan, max_it=0, is_term=True, rows_cap=0, want_erased=False, counters=None):
+    """scldpc_full_bp_device_wide / scldpc_full_bp_traj_device_wide (rows_cap > 0): full_bp_cn16(sockets=True) for trials of
+    more than 65536 CNs — the same dict: counters int32 [T,8], rows int32 [T,rows_cap,3] | None, erased int32 [T,nw] | None.
+    d_cn_sock: cn_sockets(p, d_adj16) or sample_philox_sock16's table."""
+    _require_gpu()
+    T = d_adj16.shape[0]
+    assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous()
+    assert d_cn_sock.is_cuda and d_cn_sock.dtype == torch.int16 and d_cn_sock.is_contiguous()
+    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
+    assert tuple(d_adj16.shape[1:]) == (p.n, p.dv) and tuple(d_cn_sock.shape) == (T, p.nk, p.dc) and tuple(d_chan.shape) == (T, p.nw)
+    dev = d_adj16.device
+    if counters is None:
+        counters = torch.empty((T, NCOUNTERS), dtype=torch.int32, device=dev)
+    erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
+    if rows_cap > 0:
+        rows = torch.zeros((T, rows_cap, 3), dtype=torch.int32, device=dev)         # zeros, as full_bp's
+        check(lib().scldpc_full_bp_traj_device_wide(C.byref(p), T, d_adj16.data_ptr(), d_cn_sock.data_ptr(), d_chan.data_ptr(),
+                                                    int(max_it), 1 if is_term else 0, counters.data_ptr(), rows.data_ptr(),
+                                                    int(rows_cap), erased.data_ptr() if erased is not None else None,
+                                                    _stream_ptr(dev)))
+        return {"counters": counters, "rows": rows, "erased": erased}
+    check(lib().scldpc_full_bp_device_wide(C.byref(p), T, d_adj16.data_ptr(), d_cn_sock.data_ptr(), d_chan.data_ptr(), int(max_it),
+                                           1 if is_term else 0, counters.data_ptr(),
+                                           erased.data_ptr() if erased is not None else None, _stream_ptr(dev)))
+    return {"counters": counters, "rows": None, "erased": erased}
+
+
 def check_caps(caps):
     """The cap list of full_bp_caps_cn16 as a tuple, with the C side's rules: 1 .. MAX_CAPS strictly increasing caps >= 1."""
     caps = tuple(int(k) for k in caps)

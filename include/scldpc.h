@@ -237,6 +237,20 @@ int scldpc_full_bp_traj_device_cn16(const scldpc_code_params *p, int32_t ntrials
 int scldpc_full_bp_traj_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                       const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
                                       int32_t *d_counters, int32_t *d_rows, int32_t rows_cap, uint32_t *d_erased_bits, void *stream);
+/* The WIDE form of the two level-synchronous decoders above (with and without trajectory rows), for trials of more than
+ * 65536 CNs — e.g. bp_traj's default N = 5000, L = 50 (132 500 CNs): 32-bit queue entries, one 1024-thread workgroup per
+ * CU.  Arguments, counters, rows and error codes exactly as scldpc_full_bp_device_sock16 / scldpc_full_bp_traj_device_sock16;
+ * the CN -> socket table comes from scldpc_cn_sockets_device (or scldpc_sample_philox_device_sock16 where that sampler takes
+ * the ensemble).  Takes dv = 4, dc = 8, vns_pos * dv <= 65535, cns_pos <= 65536 and a per-trial state (4 bits per CN, a bit
+ * per VN) that leaves at least 1024 entries per queue in the CU's 160 KiB: SCLDPC_ERR_TOO_LARGE names the limit otherwise.
+ * It also takes every smaller (4,8) shape (bit for bit the _sock16 result).  No wide fixpoint or caps form. */
+int scldpc_full_bp_wide_supported(const scldpc_code_params *p);
+int scldpc_full_bp_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                               const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
+                               int32_t *d_counters, uint32_t *d_erased_bits, void *stream);
+int scldpc_full_bp_traj_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                    const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
+                                    int32_t *d_counters, int32_t *d_rows, int32_t rows_cap, uint32_t *d_erased_bits, void *stream);
 
 /* decodeBP_SW, square window (BPW:628-912): window of W positions, init_it iterations for the
  * first window and max_it for the others (init_it == 0 ⇒ max_it, BPW:2101-2102). */
