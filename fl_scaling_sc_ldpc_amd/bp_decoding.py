@@ -36,6 +36,7 @@ sampling, NUM_DOPED = 0) the frames are sampled and decoded once, with a checkpo
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
+import collections
 import copy
 import os
 import sys
@@ -136,6 +137,23 @@ def write_risultati(path, sim, point):
 WIDE_BY_DEFAULT = True
 
 
+# The path of a Simulator, decided once in Simulator._select:
+#   adj_dtype    VN -> CN table: torch.int16 (position-local ids) or torch.int32 (the reference's VNdegree)
+#   sampler      what fills a batch: "glibc" (host replay), "first" (first-generation sampler), "cn16" / "sock16" (second
+#                generation, with the CN -> VN / CN -> socket table)
+#   cn_table     the CN table kept next to the VN -> CN one: None, "vn" or "sock"
+#   cn_pass      that table comes from the cn_sockets pass (the sampler does not emit it)
+#   decoder      "sw_ring" / "sw_chain" (E.sw_bp), or the full-BP call that walks the iterations: "level16", "wide", "full_bp"
+#   fix_decoder  the fixpoint kernel an unlimited fixpoint run takes for calls without rows: "fixpoint16", "fixpoint" or None
+Path = collections.namedtuple("Path", "adj_dtype sampler cn_table cn_pass decoder fix_decoder")
+
+
+def _cn16_table(p):
+    """The CN table from which the 16-bit forms of the 4-bit decoder take this ensemble with device sampling: "vn", "sock"
+    (n >= 65535) or None (they do not)."""
+    return "vn" if E.cn16_supported(p) else "sock" if E.full_bp_sock16_supported(p) else None
+
+
 class Simulator:
     """Batched Monte-Carlo driver around the device decoders."""
 
@@ -170,30 +188,52 @@ class Simulator:
         self._alloc()
 
     def _select(self):
-        """Which kernels take this configuration (no device work): sock, gen2, lvl2, ring2, wide.  Returns the dtype of the
-        VN -> CN table."""
-        p = self.p
+        """Decides the path of this configuration, once (no device work): self.path, which _alloc, fill_batch, decode_batch,
+        decode_batch_caps and kernel_choice read.  Returns the dtype of the VN -> CN table."""
+        p, philox = self.p, self.rng == "philox"
+        first = "first" if philox else "glibc"
         # compact 2-byte position-local ids for device-sampled codes; the reference's int32 VNdegree for host replays
-        adj_dtype = torch.int16 if (self.rng == "philox" and p.cns_pos <= 65536) else torch.int32
-        # full BP on the BASELINE ensemble family: the second-generation pair (sampler_v2 + the 4-bits-per-CN decoder) needs
-        # the CN -> VN table next to the VN -> CN one.  gen2: unlimited, no iteration statistics (fixpoint); lvl2: the same
-        # decoder walked one flooding iteration per round — iteration caps (the published ..._500it_... tables) and counts
-        small = self.rng == "philox" and self.decoder == "full"
-        self.sock = small and not E.cn16_supported(p) and E.full_bp_sock16_supported(p)    # n >= 65535: CN -> socket table
-        cn16 = small and (E.cn16_supported(p) or self.sock)
-        self.gen2 = cn16 and self.rows_cap == 0 and self.schedule == "fixpoint" and (self.max_it <= 0 or self.max_it >= 1000000)
-        self.lvl2 = cn16 and not self.gen2
-        # square-window decoding with the window's state in LDS reads a CN -> socket table: sampled with the code where the
-        # second-generation sampler takes the ensemble (else E.sw_bp builds it in a pass of its own)
-        self.ring2 = (self.rng == "philox" and self.decoder == "sw" and adj_dtype == torch.int16
-                      and E.sock16_supported(p) and E.sw_ring_supported(p, self.W))
-        # more than 65536 CNs per trial (bp_traj's default N = 5000; L = 100, N = 2000): the wide form of the level decoder,
-        # on the CN -> socket table.  An unlimited fixpoint run keeps full_bp_fixpoint (there is no wide fixpoint kernel).
-        fix = self.schedule == "fixpoint" and self.rows_cap == 0 and (self.max_it <= 0 or self.max_it >= 1000000)
-        use = WIDE_BY_DEFAULT if self.want_wide is None else bool(self.want_wide)
-        self.wide = bool(use and small and adj_dtype == torch.int16 and not cn16 and not fix and self.caps is None
-                         and E.full_bp_wide_supported(p))
-        self.wide_sock = self.wide and E.sock16_supported(p)      # the second-generation sampler emits the socket table
+        adj_dtype = torch.int16 if (philox and p.cns_pos <= 65536) else torch.int32
+        # the one place that knows an unlimited fixpoint run: no iteration cap to honour, no iteration statistics.  Without
+        # rows it takes a fixpoint kernel (decided per call in decode_batch: a call that wants rows walks the iterations)
+        unlimited_fix = self.schedule == "fixpoint" and (self.max_it <= 0 or self.max_it >= 1000000)
+        table = _cn16_table(p) if (philox and self.decoder == "full") else None
+        if self.decoder == "sw":
+            # square-window decoding with the window's state in LDS reads a CN -> socket table: sampled with the code where the
+            # second-generation sampler takes the ensemble (else E.sw_bp builds it in a pass of its own)
+            ring = adj_dtype == torch.int16 and E.sw_ring_supported(p, self.W)
+            if ring and E.sock16_supported(p):
+                self.path = Path(adj_dtype, "sock16", "sock", False, "sw_ring", None)
+            else:
+                self.path = Path(adj_dtype, first, None, False, "sw_ring" if ring else "sw_chain", None)
+        elif table is not None:
+            # full BP on the BASELINE ensemble family: the second-generation pair (sampler_v2 + the 4-bits-per-CN decoder) needs
+            # the CN -> VN table (n >= 65535: the CN -> socket table) next to the VN -> CN one.  Unlimited, no iteration
+            # statistics: its fixpoint form; else the same decoder walked one flooding iteration per round — iteration caps
+            # (the published ..._500it_... tables), counts and rows
+            sampler = "cn16" if table == "vn" else "sock16"
+            if unlimited_fix and self.rows_cap == 0:       # (a call that wants rows all the same gets full_bp's iterations)
+                self.path = Path(adj_dtype, sampler, table, False, "full_bp", "fixpoint16")
+            else:
+                self.path = Path(adj_dtype, sampler, table, False, "level16", None)
+        else:
+            # more than 65536 CNs per trial (bp_traj's default N = 5000; L = 100, N = 2000): the wide form of the level decoder,
+            # on the CN -> socket table — from the second-generation sampler where it takes the ensemble, else from the
+            # cn_sockets pass.  An unlimited fixpoint run keeps full_bp_fixpoint (there is no wide fixpoint kernel).
+            use = WIDE_BY_DEFAULT if self.want_wide is None else bool(self.want_wide)
+            fix = "fixpoint" if unlimited_fix else None
+            if (use and philox and self.decoder == "full" and adj_dtype == torch.int16 and not (unlimited_fix and self.rows_cap == 0)
+                    and self.caps is None and E.full_bp_wide_supported(p)):
+                sampled = E.sock16_supported(p)
+                self.path = Path(adj_dtype, "sock16" if sampled else first, "sock", not sampled, "wide", fix)
+            else:
+                self.path = Path(adj_dtype, first, None, False, "full_bp", fix)
+        path = self.path
+        # the path as the flags it used to be kept in
+        self.gen2, self.lvl2, self.wide = path.fix_decoder == "fixpoint16", path.decoder == "level16", path.decoder == "wide"
+        self.sock = (self.gen2 or self.lvl2) and path.cn_table == "sock"
+        self.ring2 = path.decoder == "sw_ring" and path.cn_table == "sock"
+        self.wide_sock = self.wide and not path.cn_pass
         if self.caps is not None and not (self.lvl2 and self.rows_cap == 0 and not self.doped):
             raise ValueError("caps: the fused decode takes Philox sampling, no doping and an ensemble of the "
                              "level-synchronous 4-bit decoder (caps_sequential_reason)")
@@ -206,7 +246,7 @@ class Simulator:
         self.d_ch = torch.empty((batch, p.nw), dtype=torch.int32, device=self.device)
         self.d_cnt = torch.empty((batch, NCOUNTERS), dtype=torch.int32, device=self.device)
         self.d_cn = (torch.empty((batch, p.nk, p.dc), dtype=torch.int16, device=self.device)
-                     if (self.gen2 or self.lvl2 or self.ring2 or self.wide) else None)
+                     if self.path.cn_table is not None else None)
         if self.caps is not None:
             self.d_cnt_caps = torch.empty(len(self.caps) * batch * NCOUNTERS, dtype=torch.int32, device=self.device)
         if self.verbose:
@@ -214,24 +254,24 @@ class Simulator:
 
     def kernel_choice(self):
         """Which device kernels this configuration runs."""
-        if self.decoder == "sw":
-            return ("sampler_v2 (CN->socket table) + sw_ring (window state in LDS)" if self.ring2 else
-                    "sampler (first generation) + " + ("sw_ring + cn_sockets pass" if E.sw_ring_supported(self.p, self.W)
-                                                       and self.d_adj.dtype == torch.int16 else "sw_bp (whole chain)"))
-        samp = "glibc replay on the host" if self.rng == "glibc" else \
-            ("sampler_v3 (CN->socket table)" if self.sock else "sampler_v3 (CN->VN table)") if (self.gen2 or self.lvl2) \
-            else "sampler (first generation)"
-        if self.gen2:
+        path = self.path
+        if path.decoder == "sw_ring":
+            return ("sampler_v2 (CN->socket table) + sw_ring (window state in LDS)" if path.cn_table is not None else
+                    "sampler (first generation) + sw_ring + cn_sockets pass")
+        if path.decoder == "sw_chain":
+            return "sampler (first generation) + sw_bp (whole chain)"
+        samp = {"glibc": "glibc replay on the host", "first": "sampler (first generation)", "cn16": "sampler_v3 (CN->VN table)",
+                "sock16": "sampler_v3 (CN->socket table)"}[path.sampler] + (" + cn_sockets pass" if path.cn_pass else "")
+        rows = ", trajectory rows)" if self.rows_cap else ")"
+        if path.fix_decoder == "fixpoint16":
             return samp + " + full_bp_small fixpoint (4-bit CN counts)"
-        if self.lvl2 and self.caps is not None:
+        if path.decoder == "level16" and self.caps is not None:
             return samp + " + full_bp_small level-synchronous with %d cap checkpoints per decode (4-bit CN counts)" % len(self.caps)
-        if self.lvl2:
-            return samp + " + full_bp_small level-synchronous (4-bit CN counts" + (", trajectory rows)" if self.rows_cap else ")")
-        if self.wide:
-            return ("sampler_v3 (CN->socket table)" if self.wide_sock else samp + " + cn_sockets pass") + \
-                " + full_bp_small wide level-synchronous (4-bit CN counts, 32-bit queue entries" + \
-                (", trajectory rows)" if self.rows_cap else ")")
-        return samp + " + full_bp (16-bit CN words" + (", trajectory rows)" if self.rows_cap else ")") + \
+        if path.decoder == "level16":
+            return samp + " + full_bp_small level-synchronous (4-bit CN counts" + rows
+        if path.decoder == "wide":
+            return samp + " + full_bp_small wide level-synchronous (4-bit CN counts, 32-bit queue entries" + rows
+        return samp + " + full_bp (16-bit CN words" + rows + \
             ": the 4-bit decoders take dv = 4, dc = 8 with device sampling and at most 65536 CNs per trial, or (the wide " \
             "form, unless switched off) a state that leaves 1024 queue entries in one CU's LDS"
 
@@ -243,48 +283,46 @@ class Simulator:
 
     # -- one device batch ------------------------------------------------------------------------
     def decode_batch(self, nb, want_rows=False):
-        adj, ch, cnt = self.d_adj[:nb], self.d_ch[:nb], self.d_cnt[:nb]
-        if self.decoder == "sw":
+        path, adj, ch, cnt = self.path, self.d_adj[:nb], self.d_ch[:nb], self.d_cnt[:nb]
+        if path.decoder in ("sw_ring", "sw_chain"):
             return E.sw_bp(self.p, adj, ch, self.W, self.max_it, self.init_it, counters=cnt,
-                           d_cn_sock=self.d_cn[:nb] if self.ring2 else None)
-        if self.gen2 and not want_rows:
-            return E.full_bp_fixpoint_cn16(self.p, adj, self.d_cn[:nb], ch, is_term=self.is_term, counters=cnt, sockets=self.sock)
-        if self.lvl2:
+                           d_cn_sock=self.d_cn[:nb] if path.cn_table is not None else None)
+        # the fixpoint kernels report neither iteration counts nor rows: a call that wants rows walks the iterations
+        decoder = path.fix_decoder if (path.fix_decoder is not None and not want_rows) else path.decoder
+        sockets, rows_cap = path.cn_table == "sock", self.rows_cap if want_rows else 0
+        if decoder == "fixpoint16":
+            return E.full_bp_fixpoint_cn16(self.p, adj, self.d_cn[:nb], ch, is_term=self.is_term, counters=cnt, sockets=sockets)
+        if decoder == "level16":
             return E.full_bp_cn16(self.p, adj, self.d_cn[:nb], ch, max_it=self.max_it, is_term=self.is_term, counters=cnt,
-                                  sockets=self.sock, rows_cap=self.rows_cap if want_rows else 0)
-        if self.schedule == "fixpoint" and not want_rows and (self.max_it <= 0 or self.max_it >= 1000000):
+                                  sockets=sockets, rows_cap=rows_cap)
+        if decoder == "fixpoint":
             return E.full_bp_fixpoint(self.p, adj, ch, is_term=self.is_term, counters=cnt)    # no iteration counts
-        if self.wide:
+        if decoder == "wide":
             return E.full_bp_wide(self.p, adj, self.d_cn[:nb], ch, max_it=self.max_it, is_term=self.is_term,
-                                  rows_cap=self.rows_cap if want_rows else 0, counters=cnt)
-        return E.full_bp(self.p, adj, ch, max_it=self.max_it, is_term=self.is_term,
-                         rows_cap=self.rows_cap if want_rows else 0, counters=cnt)
+                                  rows_cap=rows_cap, counters=cnt)
+        return E.full_bp(self.p, adj, ch, max_it=self.max_it, is_term=self.is_term, rows_cap=rows_cap, counters=cnt)
 
     def decode_batch_caps(self, nb):
         """The counters [K, nb, 8] of every cap of self.caps for the batch in place (one decode)."""
         cnt = self.d_cnt_caps[:len(self.caps) * nb * NCOUNTERS].view(len(self.caps), nb, NCOUNTERS)
         return E.full_bp_caps_cn16(self.p, self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb], self.caps, is_term=self.is_term,
-                                   counters=cnt, sockets=self.sock)
+                                   counters=cnt, sockets=self.path.cn_table == "sock")
 
     def fill_batch(self, sim, eps, frame0, nb):
-        if self.rng == "philox" and (self.gen2 or self.lvl2) and self.sock:
-            E.sample_philox_sock16(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
-                                   out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
-        elif self.rng == "philox" and (self.gen2 or self.lvl2):
-            E.sample_philox_cn16(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
-                                 out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
-        elif self.rng == "philox" and (self.ring2 or self.wide_sock):
-            E.sample_philox_sock16(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
-                                   out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
-        elif self.rng == "philox":
-            E.sample_philox(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
-                            out=(self.d_adj[:nb], self.d_ch[:nb]))
-            if self.wide:                          # more sockets per position than the second-generation sampler takes
-                E.cn_sockets(self.p, self.d_adj[:nb], out=self.d_cn[:nb])
-        else:
+        path = self.path
+        if path.sampler == "glibc":
             adj, ch = self.glibc.next_frames(nb, eps, self.doped)
             self.d_adj[:nb].copy_(torch.from_numpy(adj))
             self.d_ch[:nb].copy_(torch.from_numpy(ch.view(np.int32)))
+        elif path.sampler == "first":
+            E.sample_philox(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
+                            out=(self.d_adj[:nb], self.d_ch[:nb]))
+            if path.cn_pass:                       # more sockets per position than the second-generation sampler takes
+                E.cn_sockets(self.p, self.d_adj[:nb], out=self.d_cn[:nb])
+        else:
+            sample = E.sample_philox_cn16 if path.sampler == "cn16" else E.sample_philox_sock16
+            sample(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
+                   out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
 
     # -- one ε point -------------------------------------------------------------------------------
     @staticmethod
@@ -416,7 +454,7 @@ def caps_sequential_reason(p, rng, num_doped, schedule):
         return "NUM_DOPED > 0: the first doped position is MAX_IT (BPF:2083-2091), so every cap is a different experiment"
     if schedule != "flooding":
         return "--schedule %s has no iteration caps" % schedule
-    if not (E.cn16_supported(p) or E.full_bp_sock16_supported(p)):
+    if _cn16_table(p) is None:
         if E.full_bp_wide_supported(p):
             return ("more than 65536 CNs per trial: the wide form of the level-synchronous 4-bit decoder has no cap "
                     "checkpoints")

@@ -553,8 +553,8 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
     }
 }
 
-// wide: the carve of the 1024-thread form — 32-bit queue entries (one per word), and no 2048-word cap on a queue: that cap was
-// tuned for seven workgroups per CU, the wide form's one workgroup takes what the state leaves
+// The one LDS carve.  wide: 32-bit queue entries (one per word), and no 2048-word cap on a queue: that cap was tuned for seven
+// workgroups per CU, the wide form's one workgroup takes what the state leaves
 int make_args(const scldpc_code_params *p, int32_t is_term, SmArgs *a, int per_cu, bool level = false, bool wide = false)
 {
     const int n = scldpc::n_of(p), nk = scldpc::nk_of(p);
@@ -586,207 +586,159 @@ constexpr int kBlockWide = 1024;        // the wide form: one workgroup per CU, 
 constexpr int kWideMinQueue = 1024;     // entries per queue below which the wide form is not worth selecting
 static_assert(kSwitchWidth <= 64 * (kBlockSmall / 64), "a wave takes at most one frontier entry per lane into its private queue");
 
-}  // namespace
-
-namespace {
-bool small_shape(const scldpc_code_params *p)
-{
-    if (scldpc::check_params(p)) return false;
-    SmArgs a{};
-    uint32_t m;
-    // queue entries are 16-bit CN ids; the per-trial state (4 bits per CN, one bit per VN) must fit the LDS
-    return p->dv == 4 && p->dc == 8 && p->cns_pos <= 65536 && scldpc::nk_of(p) <= 65536 &&
-           make_args(p, 1, &a, 1) == 0 && scldpc::magic_of(p->vns_pos, scldpc::n_of(p) + 32, &m) &&
-           scldpc::magic_of(p->cns_pos, scldpc::nk_of(p), &m);
-}
-}  // namespace
-
-namespace {
-// Which limit keeps the wide form from this ensemble (nullptr: none).  The LEVEL carve at one workgroup per CU must leave
+// Which limit keeps this ensemble from the forms with 16-bit (wide = false) or 32-bit queue entries, reading the CN -> VN
+// (sock = false) or the CN -> socket table; nullptr: none.  The wide forms' LEVEL carve at one workgroup per CU must leave
 // kWideMinQueue entries per queue (a shorter queue would still decode correctly — overflow falls back to scan rounds — but is
 // no fast path), and the packed reduction of the kernel needs nk / 16 + 64 (nk / qcap + 1) <= 32 767 (see there).
-const char *wide_limit(const scldpc_code_params *p)
+const char *shape_limit(const scldpc_code_params *p, bool wide, bool sock)
 {
     if (scldpc::check_params(p)) return "invalid code parameters";
     if (p->dv != 4 || p->dc != 8) return "takes dv = 4, dc = 8 only";
-    if ((int64_t)p->vns_pos * p->dv > 65535) return "sockets: vns_pos * dv must fit 16 bits (at most 65535)";
-    if (p->cns_pos > 65536) return "sockets: at most 65536 CNs per position (16-bit position-local CN ids)";
+    if (sock && (int64_t)p->vns_pos * p->dv > 65535) return "sockets: vns_pos * dv must fit 16 bits (at most 65535)";
+    if (p->cns_pos > 65536) return "at most 65536 CNs per position (16-bit position-local CN ids)";
     const int64_t n64 = (int64_t)p->L * p->vns_pos, nk64 = (int64_t)(p->L + p->dv - 1) * p->cns_pos;
+    if (!wide && nk64 > 65536) return "at most 65536 CNs per trial (16-bit queue entries; the _wide forms take more)";
+    if (!sock && n64 >= 65535) return "global VN ids in the CN -> VN table: fewer than 65535 VNs (use the _sock16 form beyond)";
     if (n64 / 8 + nk64 / 2 > scldpc::kMaxLdsBytes) return "LDS: the CN counts and VN bits of a trial exceed 160 KiB";
     SmArgs a{};
     uint32_t m;
     if (!scldpc::magic_of(p->vns_pos, scldpc::n_of(p) + 32, &m) || !scldpc::magic_of(p->cns_pos, scldpc::nk_of(p), &m))
         return "no exact multiply-high division for this vns_pos / cns_pos";
-    if (make_args(p, 1, &a, 1, true, true) != 0) return "LDS: the CN counts and VN bits of a trial leave no room for the queues";
-    if (a.qcap < kWideMinQueue) return "queue: the LDS left by the state holds fewer than 1024 entries per queue";
-    if (a.nk / 16 + 64 * (a.nk / a.qcap + 1) > 32767) return "queue: a wave's releases per iteration could exceed 15 bits";
+    if (make_args(p, 1, &a, 1, wide, wide) != 0) return "LDS: the CN counts and VN bits of a trial leave no room for the queues";
+    if (wide && a.qcap < kWideMinQueue) return "queue: the LDS left by the state holds fewer than 1024 entries per queue";
+    if (wide && a.nk / 16 + 64 * (a.nk / a.qcap + 1) > 32767) return "queue: a wave's releases per iteration could exceed 15 bits";
     return nullptr;
 }
+
 }  // namespace
 
 // 1 when the _wide forms take this ensemble: 32-bit queue entries, one 1024-thread workgroup per CU
-extern "C" int scldpc_full_bp_wide_supported(const scldpc_code_params *p)
-{
-    return wide_limit(p) == nullptr;
-}
+extern "C" int scldpc_full_bp_wide_supported(const scldpc_code_params *p) { return shape_limit(p, true, true) == nullptr; }
 
-// 1 when scldpc_full_bp_fixpoint_device_cn16 takes this ensemble (global VN ids in the CN -> VN table: n < 65535)
-extern "C" int scldpc_full_bp_cn16_supported(const scldpc_code_params *p)
-{
-    return small_shape(p) && scldpc::n_of(p) < 65535;
-}
+// 1 when the _cn16 forms take this ensemble (global VN ids in the CN -> VN table: n < 65535)
+extern "C" int scldpc_full_bp_cn16_supported(const scldpc_code_params *p) { return shape_limit(p, false, false) == nullptr; }
 
 // 1 when the _sock16 forms take this ensemble (sockets in the CN -> VN table: any n whose state fits the LDS)
-extern "C" int scldpc_full_bp_sock16_supported(const scldpc_code_params *p)
-{
-    return small_shape(p) && (int64_t)p->vns_pos * p->dv <= 65535;
-}
+extern "C" int scldpc_full_bp_sock16_supported(const scldpc_code_params *p) { return shape_limit(p, false, true) == nullptr; }
 
 namespace {
 
-int launch_small(const char *who, bool level, bool sock, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
-                 const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
-                 int32_t *d_counters, uint32_t *d_erased_bits, void *stream, int32_t *d_rows = nullptr, int32_t rows_cap = 0)
+// What an entry point asks of the kernel.  M_FIX: the fixpoint; M_LEVEL: one flooding iteration per barrier round; M_TRAJ: the
+// same with the trajectory rows; M_CAPS: the same with a checkpoint at every cap.
+enum Mode { M_FIX, M_LEVEL, M_TRAJ, M_CAPS };
+constexpr bool kCnTable = false, kSockTable = true, kNarrow = false, kWide = true;
+struct Form {
+    Mode mode;
+    bool sock;          // the CN table holds sockets instead of global VN ids
+    bool wide;          // 32-bit queue entries, one 1024-thread workgroup per CU (LEVEL or TRAJ with sockets only)
+    // the A/B knobs SCLDPC_DEBUG_DECODER_KSWITCH, SCLDPC_DEBUG_GRID_DECODER and SCLDPC_DEBUG_LDS_PAD_DECODER act on these forms only
+    bool knobs() const { return mode != M_CAPS && !wide; }
+};
+
+// the arguments of a call; an entry point leaves what it does not have at zero
+struct Call {
+    const scldpc_code_params *p;
+    int32_t ntrials;
+    const uint16_t *vn_adj16, *cn_adj16;
+    const uint32_t *chan;
+    int32_t max_it, is_term;
+    int32_t *counters;
+    uint32_t *erased;
+    void *stream;
+    int32_t *rows; int32_t rows_cap;                // TRAJ
+    int32_t ncaps; const int32_t *caps;             // CAPS
+};
+
+using Kernel = void (*)(const SmArgs);
+constexpr int form_key(Mode mode, bool sock, bool wide, bool persist) { return mode * 8 + sock * 4 + wide * 2 + persist; }
+
+// The twelve instances <BLOCK, LEVEL, PERSIST, SOCK, TRAJ, CAPS, WIDE> with their VGPRs / SGPRs at -O3 for gfx950; no scratch
+// except where noted (as found; not looked into here).  persist: workgroup b decodes trials b, b + gridDim.x, … — reached through
+// SCLDPC_DEBUG_GRID_DECODER only, CN -> VN table only.  nullptr: no such instance.
+Kernel kernel_of(const Form &f, bool persist)
 {
-    if (d_rows && (rows_cap <= 0 || !level))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: d_rows given but rows_cap <= 0", who);
-    if (int rc = scldpc::check_params(p)) return rc;
-    if (!(sock ? scldpc_full_bp_sock16_supported(p) : scldpc_full_bp_cn16_supported(p)))
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: takes dv = 4, dc = 8, at most 65536 CNs per trial%s", who,
-                                 sock ? " and 16-bit sockets" : " and fewer than 65535 VNs (use the _sock16 form beyond)");
-    if (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj16 || !d_cn_adj16 || !d_chan_bits)))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
-    if (ntrials == 0) return SCLDPC_OK;
-    SmArgs a{};
-    int per_cu = kPerCu;                                               // workgroups per CU the LDS carve aims at
-    while (per_cu > 1 && make_args(p, is_term, &a, per_cu, level) != 0) per_cu--;
-    if (make_args(p, is_term, &a, per_cu, level) != 0)
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: the CN counts and VN bits do not fit the LDS", who);
-    scldpc::magic_of(p->vns_pos, a.n + 32, &a.magic_v);
-    scldpc::magic_of(p->cns_pos, a.nk, &a.magic_c);
-    a.vn_adj16 = d_vn_adj16; a.cn_adj16 = d_cn_adj16; a.chan = d_chan_bits;
-    a.counters = d_counters; a.erased_out = d_erased_bits;
-    a.kswitch = kSwitchWidth;
-    // A/B only; a wave takes at most one entry per lane into its private queue, so the width is capped at 64 entries per wave
-    if (const char *v = getenv("SCLDPC_DEBUG_DECODER_KSWITCH")) a.kswitch = std::min(atoi(v), 64 * (kBlockSmall / 64));
-    a.ntrials = ntrials;
-    a.rows = d_rows; a.rows_cap = d_rows ? rows_cap : 0;
-    a.max_it = max_it;
-    const int grid = scldpc::debug_grid("DECODER", ntrials);
-    void (*kern)(const SmArgs) = sock ? (level ? full_bp_small_kernel<kBlockSmall, true, false, true> : full_bp_small_kernel<kBlockSmall, false, false, true>)
-        : grid < ntrials ? (level ? full_bp_small_kernel<kBlockSmall, true, true, false> : full_bp_small_kernel<kBlockSmall, false, true, false>)
-                         : (level ? full_bp_small_kernel<kBlockSmall, true, false, false> : full_bp_small_kernel<kBlockSmall, false, false, false>);
-    if (sock && grid < ntrials) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: no persistent form with the socket table", who);
-    if (d_rows) kern = sock ? full_bp_small_kernel<kBlockSmall, true, false, true, true> : full_bp_small_kernel<kBlockSmall, true, false, false, true>;
-    size_t lds_bytes = 4u * (size_t)a.total;
-    lds_bytes = std::min(lds_bytes + scldpc::debug_lds_pad("DECODER"), (size_t)scldpc::kMaxLdsBytes);
-    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlockSmall), lds_bytes, static_cast<hipStream_t>(stream), a);
-    SCLDPC_HIP_CHECK(hipGetLastError());
-    return SCLDPC_OK;
+    constexpr int S = kBlockSmall, W = kBlockWide;
+    switch (form_key(f.mode, f.sock, f.wide, persist)) {
+    case form_key(M_FIX, kCnTable, kNarrow, false):      return full_bp_small_kernel<S, false, false, false>;                   // 64 / 93
+    case form_key(M_FIX, kSockTable, kNarrow, false):    return full_bp_small_kernel<S, false, false, true>;                    // 64 / 94
+    case form_key(M_FIX, kCnTable, kNarrow, true):       return full_bp_small_kernel<S, false, true, false>;                    // 64 / 78, 136 B of scratch
+    case form_key(M_LEVEL, kCnTable, kNarrow, false):    return full_bp_small_kernel<S, true, false, false>;                    // 63 / 94
+    case form_key(M_LEVEL, kSockTable, kNarrow, false):  return full_bp_small_kernel<S, true, false, true>;                     // 63 / 94
+    case form_key(M_LEVEL, kCnTable, kNarrow, true):     return full_bp_small_kernel<S, true, true, false>;                     // 64 / 78, 108 B of scratch
+    case form_key(M_TRAJ, kCnTable, kNarrow, false):     return full_bp_small_kernel<S, true, false, false, true>;              // 67 / 94
+    case form_key(M_TRAJ, kSockTable, kNarrow, false):   return full_bp_small_kernel<S, true, false, true, true>;               // 67 / 94
+    case form_key(M_CAPS, kCnTable, kNarrow, false):     return full_bp_small_kernel<S, true, false, false, false, true>;       // 61 / 94
+    case form_key(M_CAPS, kSockTable, kNarrow, false):   return full_bp_small_kernel<S, true, false, true, false, true>;        // 63 / 94
+    case form_key(M_LEVEL, kSockTable, kWide, false):    return full_bp_small_kernel<W, true, false, true, false, false, true>; // 63 / 94
+    case form_key(M_TRAJ, kSockTable, kWide, false):     return full_bp_small_kernel<W, true, false, true, true, false, true>;  // 67 / 94
+    }
+    return nullptr;
 }
 
-// the level-synchronous decoder with checkpoints at several caps (CAPS): one workgroup per trial, the LDS carve of the level form
-int launch_caps(const char *who, bool sock, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
-                const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t ncaps, const int32_t *caps, int32_t is_term,
-                int32_t *d_counters, void *stream)
+// Every decoder entry point below is one call of this.  The checks come in one fixed order — the parameters, the form's own
+// arguments (rows, caps), the shape, the buffers — so a call with several defects reports the first of these.  The shape is
+// judged even for an empty batch, which needs no buffers.
+int launch(const char *who, const Form &f, const Call &c)
 {
-    if (ncaps < 1 || ncaps > SCLDPC_MAX_CAPS || !caps)
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: takes 1 .. %d caps (ncaps = %d%s)", who, SCLDPC_MAX_CAPS, ncaps,
-                                 caps ? "" : ", caps NULL");
-    for (int k = 0; k < ncaps; k++)
-        if (caps[k] < 1 || (k > 0 && caps[k] <= caps[k - 1]))
-            return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: caps must be strictly increasing and >= 1 (caps[%d] = %d)", who, k,
-                                     caps[k]);
-    if (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj16 || !d_cn_adj16 || !d_chan_bits)))
+    if (int rc = scldpc::check_params(c.p)) return rc;
+    if (c.rows && c.rows_cap <= 0) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: d_rows given but rows_cap <= 0", who);
+    if (f.mode == M_CAPS) {
+        if (c.ncaps < 1 || c.ncaps > SCLDPC_MAX_CAPS || !c.caps)
+            return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: takes 1 .. %d caps (ncaps = %d%s)", who, SCLDPC_MAX_CAPS, c.ncaps,
+                                     c.caps ? "" : ", caps NULL");
+        for (int k = 0; k < c.ncaps; k++)
+            if (c.caps[k] < 1 || (k > 0 && c.caps[k] <= c.caps[k - 1]))
+                return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: caps must be strictly increasing and >= 1 (caps[%d] = %d)", who,
+                                         k, c.caps[k]);
+    }
+    if (const char *why = shape_limit(c.p, f.wide, f.sock)) return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
+    if (c.ntrials < 0 || (c.ntrials > 0 && (!c.counters || !c.vn_adj16 || !c.cn_adj16 || !c.chan)))
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
-    if (int rc = scldpc::check_params(p)) return rc;
-    if (!(sock ? scldpc_full_bp_sock16_supported(p) : scldpc_full_bp_cn16_supported(p)))
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: takes dv = 4, dc = 8, at most 65536 CNs per trial%s", who,
-                                 sock ? " and 16-bit sockets" : " and fewer than 65535 VNs (use the _sock16 form beyond)");
-    if (ntrials == 0) return SCLDPC_OK;
-    SmArgs a{};
-    int per_cu = kPerCu;                                               // the carve of launch_small's level form
-    while (per_cu > 1 && make_args(p, is_term, &a, per_cu, true) != 0) per_cu--;
-    if (make_args(p, is_term, &a, per_cu, true) != 0)
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: the CN counts and VN bits do not fit the LDS", who);
-    scldpc::magic_of(p->vns_pos, a.n + 32, &a.magic_v);
-    scldpc::magic_of(p->cns_pos, a.nk, &a.magic_c);
-    a.vn_adj16 = d_vn_adj16; a.cn_adj16 = d_cn_adj16; a.chan = d_chan_bits;
-    a.counters = d_counters;
-    a.kswitch = kSwitchWidth;
-    a.ntrials = ntrials;
-    a.ncaps = ncaps;
-    for (int k = 0; k < ncaps; k++) a.caps[k] = caps[k];
-    void (*kern)(const SmArgs) = sock ? full_bp_small_kernel<kBlockSmall, true, false, true, false, true>
-                                      : full_bp_small_kernel<kBlockSmall, true, false, false, false, true>;
-    const size_t lds_bytes = 4u * (size_t)a.total;
-    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
-    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(kBlockSmall), lds_bytes, static_cast<hipStream_t>(stream), a);
-    SCLDPC_HIP_CHECK(hipGetLastError());
-    return SCLDPC_OK;
-}
+    if (c.ntrials == 0) return SCLDPC_OK;
 
-// the wide level-synchronous decoder (LEVEL or LEVEL + TRAJ, socket table): one workgroup per trial, one per CU
-int launch_wide(const char *who, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
-                const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
-                int32_t *d_counters, uint32_t *d_erased_bits, void *stream, int32_t *d_rows, int32_t rows_cap)
-{
-    if (d_rows && rows_cap <= 0) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: d_rows given but rows_cap <= 0", who);
-    if (int rc = scldpc::check_params(p)) return rc;
-    if (const char *why = wide_limit(p)) return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
-    if (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj16 || !d_cn_sock16 || !d_chan_bits)))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
-    if (ntrials == 0) return SCLDPC_OK;
     SmArgs a{};
-    if (make_args(p, is_term, &a, 1, true, true) != 0 || 4u * (size_t)a.total > (size_t)scldpc::kMaxLdsBytes)
+    int per_cu = f.wide ? 1 : kPerCu;                                   // workgroups per CU the LDS carve aims at
+    while (per_cu > 1 && make_args(c.p, c.is_term, &a, per_cu, f.mode != M_FIX, f.wide) != 0) per_cu--;
+    if (make_args(c.p, c.is_term, &a, per_cu, f.mode != M_FIX, f.wide) != 0)
         return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: LDS: the CN counts and VN bits do not fit", who);
-    scldpc::magic_of(p->vns_pos, a.n + 32, &a.magic_v);
-    scldpc::magic_of(p->cns_pos, a.nk, &a.magic_c);
-    a.vn_adj16 = d_vn_adj16; a.cn_adj16 = d_cn_sock16; a.chan = d_chan_bits;
-    a.counters = d_counters; a.erased_out = d_erased_bits;
+    scldpc::magic_of(c.p->vns_pos, a.n + 32, &a.magic_v);
+    scldpc::magic_of(c.p->cns_pos, a.nk, &a.magic_c);
+    a.vn_adj16 = c.vn_adj16; a.cn_adj16 = c.cn_adj16; a.chan = c.chan;
+    a.counters = c.counters; a.erased_out = c.erased;
+    a.ntrials = c.ntrials;
+    a.max_it = c.max_it;
+    a.rows = c.rows; a.rows_cap = c.rows ? c.rows_cap : 0;
+    a.ncaps = c.ncaps;
+    for (int k = 0; k < c.ncaps; k++) a.caps[k] = c.caps[k];
     a.kswitch = kSwitchWidth;
-    a.ntrials = ntrials;
-    a.rows = d_rows; a.rows_cap = d_rows ? rows_cap : 0;
-    a.max_it = max_it;
-    void (*kern)(const SmArgs) = d_rows ? full_bp_small_kernel<kBlockWide, true, false, true, true, false, true>
-                                        : full_bp_small_kernel<kBlockWide, true, false, true, false, false, true>;
-    const size_t lds_bytes = 4u * (size_t)a.total;
-    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
-    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(kBlockWide), lds_bytes, static_cast<hipStream_t>(stream), a);
+    int grid = c.ntrials;
+    size_t lds_bytes = 4u * (size_t)a.total;
+    if (f.knobs()) {
+        // A/B only; a wave takes at most one entry per lane into its private queue, so the width is capped at 64 entries per wave
+        if (const char *v = getenv("SCLDPC_DEBUG_DECODER_KSWITCH")) a.kswitch = std::min(atoi(v), 64 * (kBlockSmall / 64));
+        grid = scldpc::debug_grid("DECODER", c.ntrials);
+        lds_bytes = std::min(lds_bytes + scldpc::debug_lds_pad("DECODER"), (size_t)scldpc::kMaxLdsBytes);
+    }
+    if (f.sock && grid < c.ntrials)
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: no persistent form with the socket table", who);
+    // (as found: the rows form has no persistent instance either and takes a debug grid as it is — it then decodes the first
+    // `grid` trials only)
+    const Kernel kern = kernel_of(f, grid < c.ntrials && f.mode != M_TRAJ);
+    if (int rc = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(f.wide ? kBlockWide : kBlockSmall), lds_bytes, static_cast<hipStream_t>(c.stream), a);
     SCLDPC_HIP_CHECK(hipGetLastError());
     return SCLDPC_OK;
 }
 
 }  // namespace
-
-// The level-synchronous decoder for trials of more than 65536 CNs (32-bit queue entries, a 1024-thread workgroup per CU):
-// arguments, counters and rows exactly as scldpc_full_bp_device_sock16 / scldpc_full_bp_traj_device_sock16
-extern "C" int scldpc_full_bp_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
-                                          const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
-                                          int32_t is_term, int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
-{
-    return launch_wide("scldpc_full_bp_device_wide", p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term,
-                       d_counters, d_erased_bits, stream, nullptr, 0);
-}
-
-extern "C" int scldpc_full_bp_traj_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
-                                               const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
-                                               int32_t is_term, int32_t *d_counters, int32_t *d_rows, int32_t rows_cap,
-                                               uint32_t *d_erased_bits, void *stream)
-{
-    if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_wide: null d_rows");
-    return launch_wide("scldpc_full_bp_traj_device_wide", p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term,
-                       d_counters, d_erased_bits, stream, d_rows, rows_cap);
-}
 
 extern "C" int scldpc_full_bp_fixpoint_device_cn16(const scldpc_code_params *p, int32_t ntrials,
                                                    const uint16_t *d_vn_adj16, const uint16_t *d_cn_adj16,
                                                    const uint32_t *d_chan_bits, int32_t is_term, int32_t *d_counters,
                                                    uint32_t *d_erased_bits, void *stream)
 {
-    return launch_small("scldpc_full_bp_fixpoint_device_cn16", false, false, p, ntrials, d_vn_adj16, d_cn_adj16, d_chan_bits, 0,
-                        is_term, d_counters, d_erased_bits, stream);
+    return launch("scldpc_full_bp_fixpoint_device_cn16", {M_FIX, kCnTable, kNarrow},
+                  {p, ntrials, d_vn_adj16, d_cn_adj16, d_chan_bits, 0, is_term, d_counters, d_erased_bits, stream});
 }
 
 // decodeBP with its iterations (count, cap MaxNumIt, stop tests): every counter of scldpc_full_bp_device, from both tables
@@ -794,8 +746,8 @@ extern "C" int scldpc_full_bp_device_cn16(const scldpc_code_params *p, int32_t n
                                           const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t max_it,
                                           int32_t is_term, int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
 {
-    return launch_small("scldpc_full_bp_device_cn16", true, false, p, ntrials, d_vn_adj16, d_cn_adj16, d_chan_bits, max_it,
-                        is_term, d_counters, d_erased_bits, stream);
+    return launch("scldpc_full_bp_device_cn16", {M_LEVEL, kCnTable, kNarrow},
+                  {p, ntrials, d_vn_adj16, d_cn_adj16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream});
 }
 
 // The same two decoders reading the CN -> SOCKET table of scldpc_sample_philox_device_sock16 / scldpc_cn_sockets_device
@@ -805,16 +757,16 @@ extern "C" int scldpc_full_bp_fixpoint_device_sock16(const scldpc_code_params *p
                                                      const uint32_t *d_chan_bits, int32_t is_term, int32_t *d_counters,
                                                      uint32_t *d_erased_bits, void *stream)
 {
-    return launch_small("scldpc_full_bp_fixpoint_device_sock16", false, true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits,
-                        0, is_term, d_counters, d_erased_bits, stream);
+    return launch("scldpc_full_bp_fixpoint_device_sock16", {M_FIX, kSockTable, kNarrow},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, 0, is_term, d_counters, d_erased_bits, stream});
 }
 
 extern "C" int scldpc_full_bp_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                             const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
                                             int32_t is_term, int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
 {
-    return launch_small("scldpc_full_bp_device_sock16", true, true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it,
-                        is_term, d_counters, d_erased_bits, stream);
+    return launch("scldpc_full_bp_device_sock16", {M_LEVEL, kSockTable, kNarrow},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream});
 }
 
 // decodeBP of the trajectory build (BPT:900-1140): the iterations with their rows — deg_1_iter, VNs recovered, position of the
@@ -825,8 +777,8 @@ extern "C" int scldpc_full_bp_traj_device_cn16(const scldpc_code_params *p, int3
                                                uint32_t *d_erased_bits, void *stream)
 {
     if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_cn16: null d_rows");
-    return launch_small("scldpc_full_bp_traj_device_cn16", true, false, p, ntrials, d_vn_adj16, d_cn_adj16, d_chan_bits, max_it,
-                        is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap);
+    return launch("scldpc_full_bp_traj_device_cn16", {M_TRAJ, kCnTable, kNarrow},
+                  {p, ntrials, d_vn_adj16, d_cn_adj16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap});
 }
 
 extern "C" int scldpc_full_bp_traj_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
@@ -835,8 +787,8 @@ extern "C" int scldpc_full_bp_traj_device_sock16(const scldpc_code_params *p, in
                                                  uint32_t *d_erased_bits, void *stream)
 {
     if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_sock16: null d_rows");
-    return launch_small("scldpc_full_bp_traj_device_sock16", true, true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it,
-                        is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap);
+    return launch("scldpc_full_bp_traj_device_sock16", {M_TRAJ, kSockTable, kNarrow},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap});
 }
 
 // Several caps from one decode: block k of d_counters [ncaps][ntrials][8] is what scldpc_full_bp_device_*(max_it = caps[k])
@@ -845,14 +797,34 @@ extern "C" int scldpc_full_bp_caps_device_cn16(const scldpc_code_params *p, int3
                                                const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t ncaps,
                                                const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream)
 {
-    return launch_caps("scldpc_full_bp_caps_device_cn16", false, p, ntrials, d_vn_adj16, d_cn_adj16, d_chan_bits, ncaps, caps,
-                       is_term, d_counters, stream);
+    return launch("scldpc_full_bp_caps_device_cn16", {M_CAPS, kCnTable, kNarrow},
+                  {p, ntrials, d_vn_adj16, d_cn_adj16, d_chan_bits, 0, is_term, d_counters, nullptr, stream, nullptr, 0, ncaps, caps});
 }
 
 extern "C" int scldpc_full_bp_caps_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                                  const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t ncaps,
                                                  const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream)
 {
-    return launch_caps("scldpc_full_bp_caps_device_sock16", true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, ncaps, caps,
-                       is_term, d_counters, stream);
+    return launch("scldpc_full_bp_caps_device_sock16", {M_CAPS, kSockTable, kNarrow},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, 0, is_term, d_counters, nullptr, stream, nullptr, 0, ncaps, caps});
+}
+
+// The level-synchronous decoder for trials of more than 65536 CNs (32-bit queue entries, a 1024-thread workgroup per CU):
+// arguments, counters and rows exactly as scldpc_full_bp_device_sock16 / scldpc_full_bp_traj_device_sock16
+extern "C" int scldpc_full_bp_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                          const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
+                                          int32_t is_term, int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
+{
+    return launch("scldpc_full_bp_device_wide", {M_LEVEL, kSockTable, kWide},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream});
+}
+
+extern "C" int scldpc_full_bp_traj_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                               const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
+                                               int32_t is_term, int32_t *d_counters, int32_t *d_rows, int32_t rows_cap,
+                                               uint32_t *d_erased_bits, void *stream)
+{
+    if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_wide: null d_rows");
+    return launch("scldpc_full_bp_traj_device_wide", {M_TRAJ, kSockTable, kWide},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap});
 }

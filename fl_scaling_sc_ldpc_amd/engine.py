@@ -173,10 +173,8 @@ def cn16_supported(p):
     return bool(lib().scldpc_sample_philox_cn16_supported(C.byref(p))) and bool(lib().scldpc_full_bp_cn16_supported(C.byref(p)))
 
 
-def sample_philox_cn16(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0", out=None, want_cn=True):
-    """scldpc_sample_philox_device_cn16: (vn_adj16 int16 [T,n,4], cn_adj16 int16 [T,nk,8] | None, chan int32 [T,nw]);
-    the first and the last are bit for bit sample_philox(..., adj16=True)'s; cn_adj16 holds the VNs of every CN as
-    uint16 bit patterns (0xFFFF: none), in unspecified order."""
+def _sample_philox_tables(fn, p, seed, trial0, ntrials, eps, doped, device, out, want_cn=True):
+    """The one body of sample_philox_cn16 / sample_philox_sock16: both tables and the channel from the second-generation sampler."""
     _require_gpu()
     if out is None:
         d_adj = torch.empty((ntrials, p.n, p.dv), dtype=torch.int16, device=device)
@@ -185,10 +183,16 @@ def sample_philox_cn16(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0",
     else:
         d_adj, d_cn, d_ch = out
     darr, dptr = _lib.doped_array(doped)
-    check(lib().scldpc_sample_philox_device_cn16(C.byref(p), int(seed), int(trial0), int(ntrials), float(eps), darr.size,
-                                                 dptr, d_adj.data_ptr(), d_cn.data_ptr() if d_cn is not None else None,
-                                                 d_ch.data_ptr(), _stream_ptr(d_adj.device)))
+    check(fn(C.byref(p), int(seed), int(trial0), int(ntrials), float(eps), darr.size, dptr, d_adj.data_ptr(),
+             d_cn.data_ptr() if d_cn is not None else None, d_ch.data_ptr(), _stream_ptr(d_adj.device)))
     return d_adj, d_cn, d_ch
+
+
+def sample_philox_cn16(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0", out=None, want_cn=True):
+    """scldpc_sample_philox_device_cn16: (vn_adj16 int16 [T,n,4], cn_adj16 int16 [T,nk,8] | None, chan int32 [T,nw]);
+    the first and the last are bit for bit sample_philox(..., adj16=True)'s; cn_adj16 holds the VNs of every CN as
+    uint16 bit patterns (0xFFFF: none), in unspecified order."""
+    return _sample_philox_tables(lib().scldpc_sample_philox_device_cn16, p, seed, trial0, ntrials, eps, doped, device, out, want_cn)
 
 
 def sw_ring_supported(p, W):
@@ -204,18 +208,7 @@ def sock16_supported(p):
 def sample_philox_sock16(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0", out=None):
     """scldpc_sample_philox_device_sock16: (vn_adj16 int16 [T,n,4], cn_sock16 int16 [T,nk,8], chan int32 [T,nw]); the first
     and the last are bit for bit sample_philox(..., adj16=True)'s, cn_sock16 is cn_sockets(p, vn_adj16) as a set per CN."""
-    _require_gpu()
-    if out is None:
-        d_adj = torch.empty((ntrials, p.n, p.dv), dtype=torch.int16, device=device)
-        d_cs = torch.empty((ntrials, p.nk, p.dc), dtype=torch.int16, device=device)
-        d_ch = torch.empty((ntrials, p.nw), dtype=torch.int32, device=device)
-    else:
-        d_adj, d_cs, d_ch = out
-    darr, dptr = _lib.doped_array(doped)
-    check(lib().scldpc_sample_philox_device_sock16(C.byref(p), int(seed), int(trial0), int(ntrials), float(eps), darr.size,
-                                                   dptr, d_adj.data_ptr(), d_cs.data_ptr(), d_ch.data_ptr(),
-                                                   _stream_ptr(d_adj.device)))
-    return d_adj, d_cs, d_ch
+    return _sample_philox_tables(lib().scldpc_sample_philox_device_sock16, p, seed, trial0, ntrials, eps, doped, device, out)
 
 
 def cn_adj_from_vn_adj(p, adj16):
@@ -261,44 +254,51 @@ def global_to_adj16(p, adj):
 # ------------------------------------------------------------------------------------------------
 # decoding
 # ------------------------------------------------------------------------------------------------
+def _full_bp(p, d_adj, d_cn, d_chan, call, counters=None, want_erased=False, rows_cap=0, new_rows=torch.empty, ncaps=0):
+    """The one body of the full_bp* wrappers.  Checks the tensors against p — d_cn None: the first-generation decoders, which
+    take the 4-byte VN -> CN table too; else the 2-byte tables of the 4-bit decoders — allocates counters [T,8] ([ncaps,T,8]),
+    rows [T,rows_cap,3] (by new_rows) and erased [T,nw] where asked, and calls
+    call(head, counters, rows, erased, stream) with head = (p, T, the tables, the channel) and every tensor as its pointer."""
+    _require_gpu()
+    T = d_adj.shape[0]
+    assert d_adj.is_cuda and d_adj.dtype in ((torch.int32, torch.int16) if d_cn is None else (torch.int16,)) and d_adj.is_contiguous()
+    assert d_cn is None or (d_cn.is_cuda and d_cn.dtype == torch.int16 and d_cn.is_contiguous())
+    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
+    assert tuple(d_adj.shape[1:]) == (p.n, p.dv) and tuple(d_chan.shape) == (T, p.nw)
+    assert d_cn is None or tuple(d_cn.shape) == (T, p.nk, p.dc)
+    dev = d_adj.device
+    shape = (ncaps, T, NCOUNTERS) if ncaps else (T, NCOUNTERS)
+    if counters is None:
+        counters = torch.empty(shape, dtype=torch.int32, device=dev)
+    assert not ncaps or (counters.is_contiguous() and counters.dtype == torch.int32 and tuple(counters.shape) == shape)
+    rows = new_rows((T, rows_cap, 3), dtype=torch.int32, device=dev) if rows_cap > 0 else None
+    erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
+    head = (C.byref(p), T, d_adj.data_ptr()) + ((d_cn.data_ptr(),) if d_cn is not None else ()) + (d_chan.data_ptr(),)
+    check(call(head, counters.data_ptr(), rows.data_ptr() if rows is not None else None,
+               erased.data_ptr() if erased is not None else None, _stream_ptr(dev)))
+    return {"counters": counters, "rows": rows, "erased": erased}
+
+
 def full_bp(p, d_adj, d_chan, max_it=0, is_term=True, rows_cap=0, want_erased=False, counters=None):
     """decodeBP for a batch resident on the device.  Returns dict of device tensors:
     counters int32 [T,8] (+ rows int32 [T,rows_cap,3], erased int32 [T,nw] when asked)."""
-    _require_gpu()
-    T = d_adj.shape[0]
-    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
-    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
-    assert tuple(d_adj.shape[1:]) == (p.n, p.dv) and tuple(d_chan.shape) == (T, p.nw)
-    dev = d_adj.device
-    if counters is None:
-        counters = torch.empty((T, NCOUNTERS), dtype=torch.int32, device=dev)
-    rows = torch.zeros((T, rows_cap, 3), dtype=torch.int32, device=dev) if rows_cap > 0 else None
-    erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
     fn = lib().scldpc_full_bp_device_adj16 if _is_adj16(d_adj) else lib().scldpc_full_bp_device
-    ws, wsb, _keep = _workspace(WS_FULL_BP, p, T, dev, 1 if rows is not None else 0)
-    check(fn(C.byref(p), T, d_adj.data_ptr(), d_chan.data_ptr(), int(max_it), 1 if is_term else 0,
-             counters.data_ptr(), rows.data_ptr() if rows is not None else None, int(rows_cap),
-             erased.data_ptr() if erased is not None else None, ws, wsb, _stream_ptr(dev)))
-    return {"counters": counters, "rows": rows, "erased": erased}
+
+    def call(head, cnt, rows, erased, stream):
+        ws, wsb, _keep = _workspace(WS_FULL_BP, p, head[1], d_adj.device, 1 if rows is not None else 0)
+        return fn(*head, int(max_it), 1 if is_term else 0, cnt, rows, int(rows_cap), erased, ws, wsb, stream)
+    return _full_bp(p, d_adj, None, d_chan, call, counters, want_erased, rows_cap, torch.zeros)
 
 
 def full_bp_fixpoint(p, d_adj, d_chan, is_term=True, want_erased=False, counters=None):
     """What unlimited decodeBP converges to, without its iteration count (scldpc_full_bp_fixpoint_device): counters as
     full_bp's except column 5 (barrier rounds of the kernel) — for runs with no iteration cap and no trajectory rows."""
-    _require_gpu()
-    T = d_adj.shape[0]
-    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
-    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
-    assert tuple(d_adj.shape[1:]) == (p.n, p.dv) and tuple(d_chan.shape) == (T, p.nw)
-    dev = d_adj.device
-    if counters is None:
-        counters = torch.empty((T, NCOUNTERS), dtype=torch.int32, device=dev)
-    erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
     fn = lib().scldpc_full_bp_fixpoint_device_adj16 if _is_adj16(d_adj) else lib().scldpc_full_bp_fixpoint_device
-    ws, wsb, _keep = _workspace(WS_FULL_BP, p, T, dev, 0)
-    check(fn(C.byref(p), T, d_adj.data_ptr(), d_chan.data_ptr(), 1 if is_term else 0, counters.data_ptr(),
-             erased.data_ptr() if erased is not None else None, ws, wsb, _stream_ptr(dev)))
-    return {"counters": counters, "rows": None, "erased": erased}
+
+    def call(head, cnt, rows, erased, stream):
+        ws, wsb, _keep = _workspace(WS_FULL_BP, p, head[1], d_adj.device, 0)
+        return fn(*head, 1 if is_term else 0, cnt, erased, ws, wsb, stream)
+    return _full_bp(p, d_adj, None, d_chan, call, counters, want_erased)
 
 
 def full_bp_sock16_supported(p):
@@ -309,47 +309,29 @@ def full_bp_sock16_supported(p):
 def full_bp_fixpoint_cn16(p, d_adj16, d_cn16, d_chan, is_term=True, want_erased=False, counters=None, sockets=False):
     """scldpc_full_bp_fixpoint_device_cn16: full_bp_fixpoint's counters from the VN -> CN and CN -> VN tables
     (sockets=True: the CN -> socket table, scldpc_full_bp_fixpoint_device_sock16)."""
-    _require_gpu()
-    T = d_adj16.shape[0]
-    assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous()
-    assert d_cn16.is_cuda and d_cn16.dtype == torch.int16 and d_cn16.is_contiguous()
-    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
-    assert tuple(d_adj16.shape[1:]) == (p.n, p.dv) and tuple(d_cn16.shape) == (T, p.nk, p.dc) and tuple(d_chan.shape) == (T, p.nw)
-    dev = d_adj16.device
-    if counters is None:
-        counters = torch.empty((T, NCOUNTERS), dtype=torch.int32, device=dev)
-    erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
     fn = lib().scldpc_full_bp_fixpoint_device_sock16 if sockets else lib().scldpc_full_bp_fixpoint_device_cn16
-    check(fn(C.byref(p), T, d_adj16.data_ptr(), d_cn16.data_ptr(), d_chan.data_ptr(),
-             1 if is_term else 0, counters.data_ptr(), erased.data_ptr() if erased is not None else None, _stream_ptr(dev)))
-    return {"counters": counters, "rows": None, "erased": erased}
+    return _full_bp(p, d_adj16, d_cn16, d_chan, lambda head, cnt, rows, erased, stream:
+                    fn(*head, 1 if is_term else 0, cnt, erased, stream), counters, want_erased)
+
+
+def _level_call(fn, max_it, is_term, rows_cap):
+    """The call of a level-synchronous 4-bit decoder for _full_bp: the trajectory symbols take the rows too."""
+    if rows_cap > 0:
+        return lambda head, cnt, rows, erased, stream: fn(*head, int(max_it), 1 if is_term else 0, cnt, rows, int(rows_cap), erased, stream)
+    return lambda head, cnt, rows, erased, stream: fn(*head, int(max_it), 1 if is_term else 0, cnt, erased, stream)
 
 
 def full_bp_cn16(p, d_adj16, d_cn16, d_chan, max_it=0, is_term=True, want_erased=False, counters=None, sockets=False,
                  rows_cap=0):
     """scldpc_full_bp_device_cn16: decodeBP with its iterations (count, cap, stop tests) from the VN -> CN and CN -> VN
-    tables — every counter of full_bp (no trajectory rows)."""
-    _require_gpu()
-    T = d_adj16.shape[0]
-    assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous()
-    assert d_cn16.is_cuda and d_cn16.dtype == torch.int16 and d_cn16.is_contiguous()
-    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
-    assert tuple(d_adj16.shape[1:]) == (p.n, p.dv) and tuple(d_cn16.shape) == (T, p.nk, p.dc) and tuple(d_chan.shape) == (T, p.nw)
-    dev = d_adj16.device
-    if counters is None:
-        counters = torch.empty((T, NCOUNTERS), dtype=torch.int32, device=dev)
-    erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
-    if rows_cap > 0:                                    # the trajectory build's rows (scldpc_full_bp_traj_device_*)
-        rows = torch.empty((T, rows_cap, 3), dtype=torch.int32, device=dev)
-        fn = lib().scldpc_full_bp_traj_device_sock16 if sockets else lib().scldpc_full_bp_traj_device_cn16
-        check(fn(C.byref(p), T, d_adj16.data_ptr(), d_cn16.data_ptr(), d_chan.data_ptr(), int(max_it), 1 if is_term else 0,
-                 counters.data_ptr(), rows.data_ptr(), int(rows_cap), erased.data_ptr() if erased is not None else None,
-                 _stream_ptr(dev)))
-        return {"counters": counters, "rows": rows, "erased": erased}
-    fn = lib().scldpc_full_bp_device_sock16 if sockets else lib().scldpc_full_bp_device_cn16
-    check(fn(C.byref(p), T, d_adj16.data_ptr(), d_cn16.data_ptr(), d_chan.data_ptr(), int(max_it), 1 if is_term else 0,
-             counters.data_ptr(), erased.data_ptr() if erased is not None else None, _stream_ptr(dev)))
-    return {"counters": counters, "rows": None, "erased": erased}
+    tables — every counter of full_bp; rows_cap > 0: the trajectory build's rows too (scldpc_full_bp_traj_device_cn16);
+    sockets=True: the _sock16 symbols."""
+    L = lib()
+    if rows_cap > 0:
+        fn = L.scldpc_full_bp_traj_device_sock16 if sockets else L.scldpc_full_bp_traj_device_cn16
+    else:
+        fn = L.scldpc_full_bp_device_sock16 if sockets else L.scldpc_full_bp_device_cn16
+    return _full_bp(p, d_adj16, d_cn16, d_chan, _level_call(fn, max_it, is_term, rows_cap), counters, want_erased, rows_cap)
 
 
 def full_bp_wide_supported(p):
@@ -362,27 +344,9 @@ def full_bp_wide(p, d_adj16, d_cn_sock, d_chan, max_it=0, is_term=True, rows_cap
     """scldpc_full_bp_device_wide / scldpc_full_bp_traj_device_wide (rows_cap > 0): full_bp_cn16(sockets=True) for trials of
     more than 65536 CNs — the same dict: counters int32 [T,8], rows int32 [T,rows_cap,3] | None, erased int32 [T,nw] | None.
     d_cn_sock: cn_sockets(p, d_adj16) or sample_philox_sock16's table."""
-    _require_gpu()
-    T = d_adj16.shape[0]
-    assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous()
-    assert d_cn_sock.is_cuda and d_cn_sock.dtype == torch.int16 and d_cn_sock.is_contiguous()
-    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
-    assert tuple(d_adj16.shape[1:]) == (p.n, p.dv) and tuple(d_cn_sock.shape) == (T, p.nk, p.dc) and tuple(d_chan.shape) == (T, p.nw)
-    dev = d_adj16.device
-    if counters is None:
-        counters = torch.empty((T, NCOUNTERS), dtype=torch.int32, device=dev)
-    erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
-    if rows_cap > 0:
-        rows = torch.zeros((T, rows_cap, 3), dtype=torch.int32, device=dev)         # zeros, as full_bp's
-        check(lib().scldpc_full_bp_traj_device_wide(C.byref(p), T, d_adj16.data_ptr(), d_cn_sock.data_ptr(), d_chan.data_ptr(),
-                                                    int(max_it), 1 if is_term else 0, counters.data_ptr(), rows.data_ptr(),
-                                                    int(rows_cap), erased.data_ptr() if erased is not None else None,
-                                                    _stream_ptr(dev)))
-        return {"counters": counters, "rows": rows, "erased": erased}
-    check(lib().scldpc_full_bp_device_wide(C.byref(p), T, d_adj16.data_ptr(), d_cn_sock.data_ptr(), d_chan.data_ptr(), int(max_it),
-                                           1 if is_term else 0, counters.data_ptr(),
-                                           erased.data_ptr() if erased is not None else None, _stream_ptr(dev)))
-    return {"counters": counters, "rows": None, "erased": erased}
+    fn = lib().scldpc_full_bp_traj_device_wide if rows_cap > 0 else lib().scldpc_full_bp_device_wide
+    return _full_bp(p, d_adj16, d_cn_sock, d_chan, _level_call(fn, max_it, is_term, rows_cap), counters, want_erased, rows_cap,
+                    torch.zeros)                        # zeros, as full_bp's
 
 
 def check_caps(caps):
@@ -399,21 +363,10 @@ def full_bp_caps_cn16(p, d_adj16, d_cn16, d_chan, caps, is_term=True, counters=N
     """scldpc_full_bp_caps_device_cn16 (sockets=True: _sock16): one decode, the counters of several iteration caps —
     counters [K, T, 8], where counters[k] == full_bp_cn16(..., max_it=caps[k])["counters"] on all eight columns."""
     caps = check_caps(caps)
-    _require_gpu()
-    T = d_adj16.shape[0]
-    assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous()
-    assert d_cn16.is_cuda and d_cn16.dtype == torch.int16 and d_cn16.is_contiguous()
-    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
-    assert tuple(d_adj16.shape[1:]) == (p.n, p.dv) and tuple(d_cn16.shape) == (T, p.nk, p.dc) and tuple(d_chan.shape) == (T, p.nw)
-    dev = d_adj16.device
-    if counters is None:
-        counters = torch.empty((len(caps), T, NCOUNTERS), dtype=torch.int32, device=dev)
-    assert counters.is_contiguous() and counters.dtype == torch.int32 and tuple(counters.shape) == (len(caps), T, NCOUNTERS)
     arr = (C.c_int32 * len(caps))(*caps)
     fn = lib().scldpc_full_bp_caps_device_sock16 if sockets else lib().scldpc_full_bp_caps_device_cn16
-    check(fn(C.byref(p), T, d_adj16.data_ptr(), d_cn16.data_ptr(), d_chan.data_ptr(), len(caps), arr, 1 if is_term else 0,
-             counters.data_ptr(), _stream_ptr(dev)))
-    return counters
+    return _full_bp(p, d_adj16, d_cn16, d_chan, lambda head, cnt, rows, erased, stream:
+                    fn(*head, len(caps), arr, 1 if is_term else 0, cnt, stream), counters, ncaps=len(caps))["counters"]
 
 
 def cn_sockets(p, d_adj16, out=None):
@@ -440,33 +393,27 @@ def sw_bp(p, d_adj, d_chan, W, max_it, init_it=0, want_erased=False, counters=No
         if ring and not ok:
             raise ScldpcError("the ring window kernel takes the square window on 2-byte tables of the (4,8) chain only")
         use_ring = ok
-    if use_ring:
-        assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
-        dev = d_adj.device
-        if counters is None:
-            counters = torch.empty((T, NCOUNTERS), dtype=torch.int32, device=dev)
-        erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
-        if d_cn_sock is None:
-            d_cn_sock = cn_sockets(p, d_adj)
-        check(lib().scldpc_sw_bp_ring_device(C.byref(p), T, d_adj.data_ptr(), d_cn_sock.data_ptr(), d_chan.data_ptr(), int(W),
-                                             int(max_it), int(init_it), counters.data_ptr(),
-                                             erased.data_ptr() if erased is not None else None, _stream_ptr(dev)))
-        return {"counters": counters, "erased": erased}
     assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
     assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
     dev = d_adj.device
     if counters is None:
         counters = torch.empty((T, NCOUNTERS), dtype=torch.int32, device=dev)
     erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
+    head = (C.byref(p), T, d_adj.data_ptr())
+    tail = (counters.data_ptr(), erased.data_ptr() if erased is not None else None)
+    if use_ring:
+        if d_cn_sock is None:
+            d_cn_sock = cn_sockets(p, d_adj)
+        check(lib().scldpc_sw_bp_ring_device(*head, d_cn_sock.data_ptr(), d_chan.data_ptr(), int(W), int(max_it), int(init_it),
+                                             *tail, _stream_ptr(dev)))
+        return {"counters": counters, "erased": erased}
     ws, wsb, _keep = _workspace(WS_SW_BP, p, T, dev, int(W))
     if classical:
         fn = lib().scldpc_swc_bp_device_adj16 if _is_adj16(d_adj) else lib().scldpc_swc_bp_device
-        check(fn(C.byref(p), T, d_adj.data_ptr(), d_chan.data_ptr(), int(W), int(max_it),
-                 counters.data_ptr(), erased.data_ptr() if erased is not None else None, ws, wsb, _stream_ptr(dev)))
-        return {"counters": counters, "erased": erased}
-    fn = lib().scldpc_sw_bp_device_adj16 if _is_adj16(d_adj) else lib().scldpc_sw_bp_device
-    check(fn(C.byref(p), T, d_adj.data_ptr(), d_chan.data_ptr(), int(W), int(max_it), int(init_it),
-             counters.data_ptr(), erased.data_ptr() if erased is not None else None, ws, wsb, _stream_ptr(dev)))
+        check(fn(*head, d_chan.data_ptr(), int(W), int(max_it), *tail, ws, wsb, _stream_ptr(dev)))
+    else:
+        fn = lib().scldpc_sw_bp_device_adj16 if _is_adj16(d_adj) else lib().scldpc_sw_bp_device
+        check(fn(*head, d_chan.data_ptr(), int(W), int(max_it), int(init_it), *tail, ws, wsb, _stream_ptr(dev)))
     return {"counters": counters, "erased": erased}
 
 
