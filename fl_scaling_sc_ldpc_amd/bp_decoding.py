@@ -136,6 +136,11 @@ def write_risultati(path, sim, point):
 # (profiles/traj_wide_speedup.json)
 WIDE_BY_DEFAULT = True
 
+# Whether Simulator(deg=None) takes the 4-bit level decoder for the pairs (3,6) and (5,10) where it applies: True only if every
+# repetition of the new path beats every repetition of the first-generation path end to end on every shape of
+# tools/deg_speedup.py (profiles/deg_speedup.json)
+DEG_BY_DEFAULT = False
+
 
 # The path of a Simulator, decided once in Simulator._select:
 #   adj_dtype    VN -> CN table: torch.int16 (position-local ids) or torch.int32 (the reference's VNdegree)
@@ -143,8 +148,10 @@ WIDE_BY_DEFAULT = True
 #                generation, with the CN -> VN / CN -> socket table)
 #   cn_table     the CN table kept next to the VN -> CN one: None, "vn" or "sock"
 #   cn_pass      that table comes from the cn_sockets pass (the sampler does not emit it)
-#   decoder      "sw_ring" / "sw_chain" (E.sw_bp), or the full-BP call that walks the iterations: "level16", "wide", "full_bp"
-#   fix_decoder  the fixpoint kernel an unlimited fixpoint run takes for calls without rows: "fixpoint16", "fixpoint" or None
+#   decoder      "sw_ring" / "sw_chain" (E.sw_bp), or the full-BP call that walks the iterations: "level16", "wide", "full_bp",
+#                "deg16" / "degwide" (the 4-bit level decoder of the pairs (3,6) and (5,10), 16- / 32-bit queue entries)
+#   fix_decoder  the fixpoint kernel an unlimited fixpoint run takes for calls without rows: "fixpoint16", "fixpoint_deg",
+#                "fixpoint" or None
 Path = collections.namedtuple("Path", "adj_dtype sampler cn_table cn_pass decoder fix_decoder")
 
 
@@ -159,10 +166,13 @@ class Simulator:
 
     def __init__(self, p, decoder="full", W=0, max_it=0, init_it=0, is_term=True, doped=(), batch=2048,
                  rng="philox", seed=1, device=None, rows_cap=0, schedule="flooding", shard_frames=True, index=0,
-                 verbose=False, caps=None, wide=None):
+                 verbose=False, caps=None, wide=None, deg=None):
         # wide: the 1024-thread 4-bit level decoder for trials of more than 65536 CNs (full_bp_small wide).  None = where
         # WIDE_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path, for A/B and tests)
         self.want_wide = wide
+        # deg: the 4-bit level decoder for dv, dc other than (4,8) (full_bp_small's (3,6) and (5,10) instances).  None = where
+        # DEG_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path)
+        self.want_deg = deg
         self.p, self.decoder, self.W, self.max_it, self.init_it = p, decoder, W, max_it, init_it
         # caps: several MaxNumIt from one decode (run_point_caps; the level-synchronous 4-bit decoder only)
         self.caps = E.check_caps(caps) if caps is not None else None
@@ -216,6 +226,13 @@ class Simulator:
                 self.path = Path(adj_dtype, sampler, table, False, "full_bp", "fixpoint16")
             else:
                 self.path = Path(adj_dtype, sampler, table, False, "level16", None)
+        elif self._deg_form(adj_dtype, unlimited_fix) is not None:
+            # another degree pair the 4-bit decoder has instances for: the first-generation sampler writes the 2-byte VN -> CN
+            # table for every dv, the cn_sockets pass the CN -> socket table; doped positions come with the channel.  Unlimited,
+            # no rows: the narrow fixpoint form (a wide shape keeps full_bp_fixpoint: _deg_form)
+            form = self._deg_form(adj_dtype, unlimited_fix)
+            fix = ("fixpoint_deg" if form == "deg16" else "fixpoint") if unlimited_fix else None
+            self.path = Path(adj_dtype, first, "sock", True, form, fix)
         else:
             # more than 65536 CNs per trial (bp_traj's default N = 5000; L = 100, N = 2000): the wide form of the level decoder,
             # on the CN -> socket table — from the second-generation sampler where it takes the ensemble, else from the
@@ -234,10 +251,25 @@ class Simulator:
         self.sock = (self.gen2 or self.lvl2) and path.cn_table == "sock"
         self.ring2 = path.decoder == "sw_ring" and path.cn_table == "sock"
         self.wide_sock = self.wide and not path.cn_pass
+        self.deg = path.decoder in ("deg16", "degwide")
         if self.caps is not None and not (self.lvl2 and self.rows_cap == 0 and not self.doped):
             raise ValueError("caps: the fused decode takes Philox sampling, no doping and an ensemble of the "
                              "level-synchronous 4-bit decoder (caps_sequential_reason)")
         return adj_dtype
+
+    def _deg_form(self, adj_dtype, unlimited_fix):
+        """"deg16" / "degwide" where the _deg forms of the 4-bit decoder apply to this configuration, else None."""
+        p = self.p
+        use = DEG_BY_DEFAULT if self.want_deg is None else bool(self.want_deg)
+        if not (use and (p.dv, p.dc) != (4, 8) and self.rng == "philox" and self.decoder == "full" and adj_dtype == torch.int16
+                and self.caps is None):
+            return None
+        if E.full_bp_deg_supported(p):
+            return "deg16"
+        # no wide fixpoint kernel: an unlimited fixpoint run without rows keeps the first-generation path, as on the wide path
+        if not (unlimited_fix and self.rows_cap == 0) and E.full_bp_deg_supported(p, wide=True):
+            return "degwide"
+        return None
 
     def _alloc(self):
         p, batch = self.p, self.batch
@@ -271,6 +303,13 @@ class Simulator:
             return samp + " + full_bp_small level-synchronous (4-bit CN counts" + rows
         if path.decoder == "wide":
             return samp + " + full_bp_small wide level-synchronous (4-bit CN counts, 32-bit queue entries" + rows
+        if self.deg:
+            pair = "4-bit CN counts, dv = %d, dc = %d" % (self.p.dv, self.p.dc)
+            if path.fix_decoder == "fixpoint_deg" and not self.rows_cap:
+                return samp + " + full_bp_small fixpoint (" + pair + ")"
+            if path.decoder == "degwide":
+                return samp + " + full_bp_small wide level-synchronous (" + pair + ", 32-bit queue entries" + rows
+            return samp + " + full_bp_small level-synchronous (" + pair + rows
         return samp + " + full_bp (16-bit CN words" + rows + \
             ": the 4-bit decoders take dv = 4, dc = 8 with device sampling and at most 65536 CNs per trial, or (the wide " \
             "form, unless switched off) a state that leaves 1024 queue entries in one CU's LDS"
@@ -297,6 +336,11 @@ class Simulator:
                                   sockets=sockets, rows_cap=rows_cap)
         if decoder == "fixpoint":
             return E.full_bp_fixpoint(self.p, adj, ch, is_term=self.is_term, counters=cnt)    # no iteration counts
+        if decoder == "fixpoint_deg":
+            return E.full_bp_fixpoint_deg(self.p, adj, self.d_cn[:nb], ch, is_term=self.is_term, counters=cnt)
+        if decoder in ("deg16", "degwide"):
+            return E.full_bp_deg(self.p, adj, self.d_cn[:nb], ch, max_it=self.max_it, is_term=self.is_term, rows_cap=rows_cap,
+                                 counters=cnt, wide=decoder == "degwide")
         if decoder == "wide":
             return E.full_bp_wide(self.p, adj, self.d_cn[:nb], ch, max_it=self.max_it, is_term=self.is_term,
                                   rows_cap=rows_cap, counters=cnt)
@@ -644,7 +688,8 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                         rows_cap=opts.rows_cap if prog == "bp_traj" else 0, schedule=getattr(opts, "schedule", "flooding"),
                         shard_frames=shard == "frames", device=getattr(opts, "device", None), index=replica,
                         verbose=rank == 0 and not opts.quiet,
-                        wide={"auto": None, "on": True, "off": False}[getattr(opts, "wide", "auto")])
+                        wide={"auto": None, "on": True, "off": False}[getattr(opts, "wide", "auto")],
+                        deg={"auto": None, "on": True, "off": False}[getattr(opts, "deg", "auto")])
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     t0 = time.time()
@@ -749,6 +794,10 @@ def _parser(prog):
     ap.add_argument("--wide", choices=("auto", "on", "off"), default="auto",
                     help="full BP of trials with more than 65536 CNs (e.g. the default N = 5000): the wide 4-bit level "
                          "decoder (on), the first-generation decoder (off), or the measured default (auto); same files")
+    if prog != "sw_lim_iter":
+        ap.add_argument("--deg", choices=("auto", "on", "off"), default="auto",
+                        help="full BP with --dv/--dc 3/6 or 5/10: the 4-bit level decoder (on), the first-generation decoder "
+                             "(off), or the measured default (auto); same files")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")

@@ -53,14 +53,56 @@ struct SmArgs {
     int rows_cap;                                   // TRAJ: rows kept per trial
     int32_t *rows;                                  // TRAJ: [T][rows_cap][3] = deg_1_iter, recovered, first erased position
     int off_U, off_q0, off_q1, off_pos, off_scal, off_fb, total, qcap;      // LDS offsets in 32-bit words; qcap in entries (u16; WIDE: u32)
-    const uint16_t *vn_adj16;                       // [T][n][4]   CN index local to its position
-    const uint16_t *cn_adj16;                       // [T][nk][8]  VNs of every CN (0xFFFF: none); SOCK: their sockets dv*t + i instead
+    const uint16_t *vn_adj16;                       // [T][n][dv]  CN index local to its position
+    const uint16_t *cn_adj16;                       // [T][nk][dc] VNs of every CN (0xFFFF: none); SOCK: their sockets dv*t + i instead
     const uint32_t *chan;
     int32_t *counters;
     uint32_t *erased_out;
     int ncaps;                                      // CAPS: caps[0] < caps[1] < … (>= 1); counters [ncaps][ntrials][8]
     int caps[SCLDPC_MAX_CAPS];
 };
+
+// A table row as it is kept in registers: its 16-bit entries two to a word.
+template <int D>
+struct Row {
+    uint32_t w[(D + 1) / 2];
+    __device__ __forceinline__ uint32_t operator[](int i) const { return (w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu; }
+};
+// Loads no wider than the alignment the layout guarantees: the unit in which a trial's table is addressed (one load each) and
+// how many of them make a row — a whole row where its size is a power of two, else uint16 (VN rows) or uint32 (CN rows).
+template <int D> struct VnUnit { using type = uint16_t; static constexpr int per_row = D; };
+template <> struct VnUnit<4> { using type = uint2; static constexpr int per_row = 1; };
+template <int D> struct CnUnit { using type = uint32_t; static constexpr int per_row = D / 2; };
+template <> struct CnUnit<8> { using type = uint4; static constexpr int per_row = 1; };
+
+__device__ __forceinline__ Row<4> load_row(const uint2 *rows, int j)
+{
+    const uint2 v = rows[j];
+    return {{v.x, v.y}};
+}
+__device__ __forceinline__ Row<8> load_row(const uint4 *rows, int c)
+{
+    const uint4 v = rows[c];
+    return {{v.x, v.y, v.z, v.w}};
+}
+template <int DV>
+__device__ __forceinline__ Row<DV> load_row(const uint16_t *rows, int j)
+{
+    Row<DV> r;
+    const uint16_t *h = rows + (size_t)j * DV;
+#pragma unroll
+    for (int i = 0; i < DV; i += 2) r.w[i >> 1] = (uint32_t)h[i] | (i + 1 < DV ? (uint32_t)h[i + 1] << 16 : 0u);
+    return r;
+}
+template <int DC>
+__device__ __forceinline__ Row<DC> load_row(const uint32_t *rows, int c)
+{
+    Row<DC> r;
+    const uint32_t *h = rows + (size_t)c * (DC / 2);
+#pragma unroll
+    for (int i = 0; i < DC / 2; i++) r.w[i] = h[i];
+    return r;
+}
 
 // Seven 4-wave workgroups per CU are 7 waves per SIMD: at most 96 SGPRs and 72 VGPRs per wave (MI355X_MICROARCH.md).
 // SOCK: the CN -> VN table holds sockets (s = dv*t + i = edge i of VN t of position CNpos - i: scldpc_sample_philox_device_sock16's
@@ -75,10 +117,17 @@ struct SmArgs {
 // the CU and all of its LDS (four waves per SIMD, at most 128 VGPRs) — trials of more than 65536 CNs, e.g. bp_traj's default
 // N = 5000, L = 50 (nk = 132 500).  There is no wide fixpoint form (the private-queue carve below assumes four waves), no wide
 // PERSIST and no wide CAPS form.
-template <int BLOCK, bool LEVEL, bool PERSIST, bool SOCK, bool TRAJ = false, bool CAPS = false, bool WIDE = false>
-__global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((amdgpu_num_sgpr(96))) void full_bp_small_kernel(const SmArgs a)
+// DV, DC: the degree pair, fixed at compile time (the rows of both tables are unrolled).  A VN row is DV uint16 and only 2-byte
+// aligned unless DV = 4 (one 8-byte load); a CN row is DC uint16, DC even, so 4-byte aligned (DC = 8: one 16-byte load).  Pairs
+// other than (4,8) have the socket-table forms without PERSIST and CAPS only (kernel_of).
+// OCC: waves per SIMD the registers are bounded for where an instance cannot hold its form's (0: the form's).
+template <int BLOCK, bool LEVEL, bool PERSIST, bool SOCK, bool TRAJ = false, bool CAPS = false, bool WIDE = false, int DV = 4, int DC = 8,
+          int OCC = 0>
+__global__ __launch_bounds__(BLOCK, OCC ? OCC : WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((amdgpu_num_sgpr(96))) void full_bp_small_kernel(const SmArgs a)
 {
     static_assert(!WIDE || (BLOCK == 1024 && LEVEL && SOCK && !PERSIST && !CAPS), "the wide form: LEVEL [+ TRAJ], socket table");
+    static_assert((DV == 4 && DC == 8) || (SOCK && !PERSIST && !CAPS), "other degree pairs: the socket table, no PERSIST, no CAPS");
+    static_assert(DC <= 15 && DC % 2 == 0 && DV < DC, "a CN's count of erased neighbours is a nibble; CN rows are read as 32-bit words");
     using QT = std::conditional_t<WIDE, uint32_t, uint16_t>;             // a queue entry: a CN id
     constexpr int kWaves = BLOCK / 64;
     extern __shared__ uint32_t lds[];
@@ -93,8 +142,10 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
     auto decode_trial = [&](const int trial) {
     STAMP_DECL
     const int n = a.n, nk = a.nk, cn_lim = a.cn_lim, nw = a.nw, V = a.V, C = a.C, L = a.L, qcap = a.qcap;
-    const uint2 *vrow = reinterpret_cast<const uint2 *>(a.vn_adj16) + (size_t)trial * n;
-    const uint4 *crow = reinterpret_cast<const uint4 *>(a.cn_adj16) + (size_t)trial * nk;
+    const auto *vrow = reinterpret_cast<const typename VnUnit<DV>::type *>(a.vn_adj16) + (size_t)trial * n * VnUnit<DV>::per_row;
+    const auto *crow = reinterpret_cast<const typename CnUnit<DC>::type *>(a.cn_adj16) + (size_t)trial * nk * CnUnit<DC>::per_row;
+    auto vn_row = [&](int j) { if constexpr (DV == 4) return load_row(vrow, j); else return load_row<DV>(vrow, j); };
+    auto cn_row = [&](int c) { if constexpr (DC == 8) return load_row(crow, c); else return load_row<DC>(crow, c); };
     const uint32_t *ch = a.chan + (size_t)trial * nw;
 
     // ---- channel bits, clear the counts -------------------------------------------------------------------------
@@ -112,28 +163,27 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
     ne_local = wave_sum(ne_local);
     if (lane == 0 && ne_local) atomicAdd(&scal[SC_NE], ne_local);
 
-    // ---- build: every erased VN counts itself into its 4 CNs; rows are loaded unconditionally (coalesced 8-B loads) --
+    // ---- build: every erased VN counts itself into its DV CNs; rows are loaded unconditionally (coalesced loads) -------
     constexpr int NB = 8;                                                // rows in flight per thread
     for (int j0 = tid; j0 < n; j0 += NB * BLOCK) {
-        uint2 r[NB];
+        Row<DV> r[NB];
         bool er[NB];
 #pragma unroll
         for (int u = 0; u < NB; u++) {
             const int j = j0 + u * BLOCK;
             er[u] = false;
-            if (j < n) { r[u] = vrow[j]; er[u] = (U[j >> 5] >> (j & 31)) & 1u; }
+            if (j < n) { r[u] = vn_row(j); er[u] = (U[j >> 5] >> (j & 31)) & 1u; }
         }
 #pragma unroll
         for (int u = 0; u < NB; u++) {
             const int j = j0 + u * BLOCK;
             if (er[u]) {
                 const int base = (int)__umulhi((uint32_t)j, a.magic_v) * C;
-                const int c0 = base + (int)(r[u].x & 0xFFFFu), c1 = base + C + (int)(r[u].x >> 16);
-                const int c2 = base + 2 * C + (int)(r[u].y & 0xFFFFu), c3 = base + 3 * C + (int)(r[u].y >> 16);
-                atomicAdd(&cnt[c0 >> 3], 1u << ((c0 & 7) * 4));
-                atomicAdd(&cnt[c1 >> 3], 1u << ((c1 & 7) * 4));
-                atomicAdd(&cnt[c2 >> 3], 1u << ((c2 & 7) * 4));
-                atomicAdd(&cnt[c3 >> 3], 1u << ((c3 & 7) * 4));
+                int cc[DV];
+#pragma unroll
+                for (int i = 0; i < DV; i++) cc[i] = base + i * C + (int)r[u][i];
+#pragma unroll
+                for (int i = 0; i < DV; i++) atomicAdd(&cnt[cc[i] >> 3], 1u << ((cc[i] & 7) * 4));
             }
         }
     }
@@ -144,39 +194,40 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
     // ---- one release step: CN c is believed to have exactly one erased neighbour -----------------------------------
     // out[i] = 1 + the CN on edge i of the released VN if this release left it with one erased neighbour, else 0
     int removed = 0, drops = 0;                                          // drops (LEVEL): counts taken from one to zero
-    auto step = [&](int c, uint32_t (&out)[4]) {
-        out[0] = out[1] = out[2] = out[3] = 0;
-        const uint4 s4 = crow[c];
-        uint32_t jk[8] = {s4.x & 0xFFFFu, s4.x >> 16, s4.y & 0xFFFFu, s4.y >> 16,
-                          s4.z & 0xFFFFu, s4.z >> 16, s4.w & 0xFFFFu, s4.w >> 16};
-        bool none[8];
+    auto step = [&](int c, uint32_t (&out)[DV]) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) none[k] = jk[k] == 0xFFFFu;
-        if constexpr (SOCK) {                                            // socket -> global VN index
+        for (int i = 0; i < DV; i++) out[i] = 0;
+        const Row<DC> s = cn_row(c);
+        uint32_t jk[DC];
+        bool none[DC];
+#pragma unroll
+        for (int k = 0; k < DC; k++) { jk[k] = s[k]; none[k] = jk[k] == 0xFFFFu; }
+        if constexpr (SOCK) {                                            // socket s = DV * t + i -> global VN index
             const int vbase = (int)__umulhi((uint32_t)c, a.magic_c) * V;                   // CN position * V
 #pragma unroll
-            for (int k = 0; k < 8; k++) jk[k] = (uint32_t)(vbase - (int)(jk[k] & 3u) * V) + (jk[k] >> 2);
+            for (int k = 0; k < DC; k++) jk[k] = (uint32_t)(vbase - (int)(jk[k] % DV) * V) + (jk[k] / DV);
         }
-        uint32_t wd[8];
+        uint32_t wd[DC];
 #pragma unroll
-        for (int k = 0; k < 8; k++) wd[k] = U[none[k] ? 0u : jk[k] >> 5];               // no VN: any word, masked below
+        for (int k = 0; k < DC; k++) wd[k] = U[none[k] ? 0u : jk[k] >> 5];              // no VN: any word, masked below
         int j = -1;
 #pragma unroll
-        for (int k = 0; k < 8; k++)
+        for (int k = 0; k < DC; k++)
             if (!none[k] && ((wd[k] >> (jk[k] & 31u)) & 1u)) j = (int)jk[k];
         if (j < 0) return;                                               // its last neighbour is being released elsewhere
-        const uint2 r = vrow[j];                                         // issued before the claim: overlaps its round trip
+        const Row<DV> r = vn_row(j);                      // issued before the claim: overlaps its round trip
         const uint32_t bit = 1u << (j & 31);
         if (!(atomicAnd(&U[j >> 5], ~bit) & bit)) return;
         removed++;
         const int base = (int)__umulhi((uint32_t)j, a.magic_v) * C;
-        const int cc[4] = {base + (int)(r.x & 0xFFFFu), base + C + (int)(r.x >> 16),
-                           base + 2 * C + (int)(r.y & 0xFFFFu), base + 3 * C + (int)(r.y >> 16)};
-        uint32_t o[4];
+        int cc[DV];
 #pragma unroll
-        for (int i = 0; i < 4; i++) o[i] = atomicSub(&cnt[cc[i] >> 3], 1u << ((cc[i] & 7) * 4));
+        for (int i = 0; i < DV; i++) cc[i] = base + i * C + (int)r[i];
+        uint32_t o[DV];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
+        for (int i = 0; i < DV; i++) o[i] = atomicSub(&cnt[cc[i] >> 3], 1u << ((cc[i] & 7) * 4));
+#pragma unroll
+        for (int i = 0; i < DV; i++) {
             const uint32_t old = (o[i] >> ((cc[i] & 7) * 4)) & 15u;
             if (old == 2u && cc[i] < cn_lim) out[i] = (uint32_t)cc[i] + 1u;
             if constexpr (LEVEL) drops += (old == 1u && cc[i] < cn_lim);
@@ -193,8 +244,10 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
         return z;
     };
     // a wave appends its lanes' out[] entries to queue qn behind *push (one prefix scan + one LDS atomic per wave)
-    auto append = [&](const uint32_t (&out)[4], int *push, QT *qn, bool &overflow) {
-        const int mine = (out[0] != 0u) + (out[1] != 0u) + (out[2] != 0u) + (out[3] != 0u);
+    auto append = [&](const uint32_t (&out)[DV], int *push, QT *qn, bool &overflow) {
+        int mine = 0;
+#pragma unroll
+        for (int i = 0; i < DV; i++) mine += out[i] != 0u;
         const int incl = (int)wave_inclusive_scan((uint32_t)mine);
         const int tot = __builtin_amdgcn_readlane(incl, 63);
         if (tot) {
@@ -202,7 +255,7 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
             if (lane == 0) base = atomicAdd(push, tot);
             int idx = __builtin_amdgcn_readfirstlane(base) + incl - mine;
 #pragma unroll
-            for (int i = 0; i < 4; i++)
+            for (int i = 0; i < DV; i++)
                 if (out[i]) { if (idx < qcap) qn[idx] = (QT)(out[i] - 1u); else overflow = true; idx++; }
         }
     };
@@ -235,24 +288,24 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
             for (int t = tid; t < V; t += BLOCK) {
                 const int j = q0 * V + t;
                 if (!((U[j >> 5] >> (j & 31)) & 1u)) continue;
-                const uint2 r = vrow[j];
+                const Row<DV> r = vn_row(j);
                 const int base = q0 * C;
-                const int cc[4] = {base + (int)(r.x & 0xFFFFu), base + C + (int)(r.x >> 16),
-                                   base + 2 * C + (int)(r.y & 0xFFFFu), base + 3 * C + (int)(r.y >> 16)};
-                bool pair = true;
+                int cc[DV];
 #pragma unroll
-                for (int i = 0; i < 4; i++) pair = pair && ((cnt[cc[i] >> 3] >> ((cc[i] & 7) * 4)) & 15u) == 2u;
+                for (int i = 0; i < DV; i++) cc[i] = base + i * C + (int)r[i];
+                bool pair = true;                                        // all DV CNs of the VN have two erased neighbours …
+#pragma unroll
+                for (int i = 0; i < DV; i++) pair = pair && ((cnt[cc[i] >> 3] >> ((cc[i] & 7) * 4)) & 15u) == 2u;
                 if (!pair) continue;
-                int partner = -1;
-                for (int i = 0; i < 4 && pair; i++) {                    // the other erased neighbour of each CN
-                    const uint4 s4 = crow[cc[i]];
-                    const uint32_t jk[8] = {s4.x & 0xFFFFu, s4.x >> 16, s4.y & 0xFFFFu, s4.y >> 16,
-                                            s4.z & 0xFFFFu, s4.z >> 16, s4.w & 0xFFFFu, s4.w >> 16};
+                int partner = -1;                                        // … and the other one is the same VN for all of them
+                for (int i = 0; i < DV && pair; i++) {                   // the other erased neighbour of each CN
+                    const Row<DC> s = cn_row(cc[i]);
                     int other = -1;
-                    for (int k = 0; k < 8; k++) {
-                        if (jk[k] == 0xFFFFu) continue;
+                    for (int k = 0; k < DC; k++) {
+                        const uint32_t jk = s[k];
+                        if (jk == 0xFFFFu) continue;
                         // (cc[i] lies in CN position q0 + i)
-                        const int j2 = SOCK ? (q0 + i - (int)(jk[k] & 3u)) * V + (int)(jk[k] >> 2) : (int)jk[k];
+                        const int j2 = SOCK ? (q0 + i - (int)(jk % DV)) * V + (int)(jk / DV) : (int)jk;
                         if (j2 != j && ((U[j2 >> 5] >> (j2 & 31)) & 1u)) other = j2;
                     }
                     if (other < 0 || (i > 0 && other != partner)) pair = false;
@@ -289,14 +342,14 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
             // degree-1 CNs whose single VN is known count into iteration 0's deg_1_iter (BPF:969-978).  Only the first and the
             // last dv-1 CN positions of the chain hold CNs of degree below dc: their rows say how many neighbours they have.
             int extra = 0;
-            const int head = 3 * C, tail0 = L * C;
+            const int head = (DV - 1) * C, tail0 = L * C;
             for (int i = tid; i < 2 * head; i += BLOCK) {
                 const int c = i < head ? i : tail0 + (i - head);
                 if (c >= cn_lim || c >= nk) continue;
-                const uint4 s4 = crow[c];
-                const int deg = ((s4.x & 0xFFFFu) != 0xFFFFu) + ((s4.x >> 16) != 0xFFFFu) + ((s4.y & 0xFFFFu) != 0xFFFFu) +
-                                ((s4.y >> 16) != 0xFFFFu) + ((s4.z & 0xFFFFu) != 0xFFFFu) + ((s4.z >> 16) != 0xFFFFu) +
-                                ((s4.w & 0xFFFFu) != 0xFFFFu) + ((s4.w >> 16) != 0xFFFFu);
+                const Row<DC> s = cn_row(c);
+                int deg = 0;
+#pragma unroll
+                for (int k = 0; k < DC; k++) deg += s[k] != 0xFFFFu;
                 extra += deg == 1 && ((cnt[c >> 3] >> ((c & 7) * 4)) & 15u) == 0u;
             }
             extra = wave_sum(extra);
@@ -313,7 +366,7 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
             removed = 0; drops = 0;
             auto run_queue = [&](int nq) {
                 for (int k0 = wave * 64; k0 < nq; k0 += BLOCK) {
-                    uint32_t out[4] = {0, 0, 0, 0};
+                    uint32_t out[DV] = {};
                     if (k0 + lane < nq) step((int)qc[k0 + lane], out);
                     append(out, push, qn, overflow);
                 }
@@ -377,6 +430,11 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
                 // last are full (at most nk / qcap + 1 of them), so a wave releases at most nk / 16 + 64 (nk / qcap + 1) VNs
                 // per iteration.  wide_shape() refuses shapes where that exceeds 32 767 (with qcap >= 1024 and the LDS's
                 // nk < 190 000 it is below 23 900), and four times as many zeroed CNs still fit the upper 17 bits.
+                // Other DV: a release decrements DV counts, so drops <= DV * removed.  With r = nk / waves + 64 (nk / qcap + 1)
+                // bounding a wave's releases per iteration (the narrow form's scan rounds run several queue-fulls as well),
+                // the _deg forms are refused unless r <= 32 767 and DV * r < 2^17 (shape_limit).  Where the queues have
+                // their full length the narrow r is at most 16 384 + 64 * 17 = 17 472, DV * r <= 87 360 for DV = 5; a
+                // carve squeezed to its shortest queue (256 entries) on 65 536 CNs would reach r = 32 832 and is refused.
                 const uint32_t both = (uint32_t)wave_sum((int)((uint32_t)removed | ((uint32_t)drops << 15)));
                 removed = (int)(both & 0x7FFFu); drops = (int)(both >> 15);
             }
@@ -479,7 +537,7 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
             bool overflow = false;
             if (ncur > kSwitch || half_cap < 64) {
                 for (int k0 = wave * 64; k0 < ncur; k0 += BLOCK) {
-                    uint32_t out[4] = {0, 0, 0, 0};
+                    uint32_t out[DV] = {};
                     if (k0 + lane < ncur) step((int)qc[k0 + lane], out);
                     append(out, push, qn, overflow);
                 }
@@ -493,14 +551,16 @@ __global__ __launch_bounds__(BLOCK, WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((a
                     QT *src = mine + cur * half_cap, *dst = mine + (cur ^ 1) * half_cap;
                     int ncnt = 0;
                     for (int b0 = 0; b0 < cntw; b0 += 64) {
-                        uint32_t out[4] = {0, 0, 0, 0};
+                        uint32_t out[DV] = {};
                         if (b0 + lane < cntw) step((int)src[b0 + lane], out);
                         {   // append: wave-synchronous, no atomics
-                            const int mine_n = (out[0] != 0u) + (out[1] != 0u) + (out[2] != 0u) + (out[3] != 0u);
+                            int mine_n = 0;
+    #pragma unroll
+                            for (int i = 0; i < DV; i++) mine_n += out[i] != 0u;
                             const int incl = (int)wave_inclusive_scan((uint32_t)mine_n);
                             int idx = ncnt + incl - mine_n;
     #pragma unroll
-                            for (int i = 0; i < 4; i++)
+                            for (int i = 0; i < DV; i++)
                                 if (out[i]) { if (idx < half_cap) dst[idx] = (QT)(out[i] - 1u); else overflow = true; idx++; }
                             ncnt += __builtin_amdgcn_readlane(incl, 63);
                         }
@@ -586,14 +646,37 @@ constexpr int kBlockWide = 1024;        // the wide form: one workgroup per CU, 
 constexpr int kWideMinQueue = 1024;     // entries per queue below which the wide form is not worth selecting
 static_assert(kSwitchWidth <= 64 * (kBlockSmall / 64), "a wave takes at most one frontier entry per lane into its private queue");
 
+// The degree pairs with instances (kernel_of): their index, or -1
+constexpr int pair_of(int dv, int dc) { return dv == 4 && dc == 8 ? 0 : dv == 3 && dc == 6 ? 1 : dv == 5 && dc == 10 ? 2 : -1; }
+
+// The carve a launch uses: as many workgroups per CU as the form aims at (wide: one), fewer while the queues do not fit.
+// Returns the workgroups per CU, or -1.
+int carve(const scldpc_code_params *p, int32_t is_term, bool level, bool wide, SmArgs *a, int per_cu = kPerCu)
+{
+    if (wide) per_cu = 1;
+    while (per_cu > 1 && make_args(p, is_term, a, per_cu, level, wide) != 0) per_cu--;
+    return make_args(p, is_term, a, per_cu, level, wide) == 0 ? per_cu : -1;
+}
+
 // Which limit keeps this ensemble from the forms with 16-bit (wide = false) or 32-bit queue entries, reading the CN -> VN
 // (sock = false) or the CN -> socket table; nullptr: none.  The wide forms' LEVEL carve at one workgroup per CU must leave
 // kWideMinQueue entries per queue (a shorter queue would still decode correctly — overflow falls back to scan rounds — but is
 // no fast path), and the packed reduction of the kernel needs nk / 16 + 64 (nk / qcap + 1) <= 32 767 (see there).
-const char *shape_limit(const scldpc_code_params *p, bool wide, bool sock)
+// deg: the entry points that take the degree pairs of pair_of() (socket table only), and with them the bounds of the
+// kernel's packed reduction for the carve the launch will use, narrow or wide.
+const char *shape_limit(const scldpc_code_params *p, bool wide, bool sock, bool deg = false)
 {
     if (scldpc::check_params(p)) return "invalid code parameters";
-    if (p->dv != 4 || p->dc != 8) return "takes dv = 4, dc = 8 only";
+    if (!deg) {
+        if (p->dv != 4 || p->dc != 8) return "takes dv = 4, dc = 8 only";
+    } else {
+        if (p->dc > 15) return "dc must be at most 15 (a CN's count of erased neighbours is kept in 4 bits)";
+        if (pair_of(p->dv, p->dc) < 0) {
+            static thread_local char text[96];
+            snprintf(text, sizeof text, "no instance for dv = %d, dc = %d (takes (3,6), (4,8) and (5,10))", p->dv, p->dc);
+            return text;
+        }
+    }
     if (sock && (int64_t)p->vns_pos * p->dv > 65535) return "sockets: vns_pos * dv must fit 16 bits (at most 65535)";
     if (p->cns_pos > 65536) return "at most 65536 CNs per position (16-bit position-local CN ids)";
     const int64_t n64 = (int64_t)p->L * p->vns_pos, nk64 = (int64_t)(p->L + p->dv - 1) * p->cns_pos;
@@ -607,6 +690,12 @@ const char *shape_limit(const scldpc_code_params *p, bool wide, bool sock)
     if (make_args(p, 1, &a, 1, wide, wide) != 0) return "LDS: the CN counts and VN bits of a trial leave no room for the queues";
     if (wide && a.qcap < kWideMinQueue) return "queue: the LDS left by the state holds fewer than 1024 entries per queue";
     if (wide && a.nk / 16 + 64 * (a.nk / a.qcap + 1) > 32767) return "queue: a wave's releases per iteration could exceed 15 bits";
+    if (deg) {
+        if (!wide && carve(p, 1, true, false, &a) < 0) return "LDS: the CN counts and VN bits of a trial leave no room for the queues";
+        const int r = a.nk / (wide ? kBlockWide / 64 : kBlockSmall / 64) + 64 * (a.nk / a.qcap + 1);
+        if (r > 32767) return "queue: a wave's releases per iteration could exceed 15 bits";
+        if (p->dv * r >= (1 << 17)) return "queue: the CNs a wave zeroes per iteration could exceed 17 bits";
+    }
     return nullptr;
 }
 
@@ -626,13 +715,14 @@ namespace {
 // What an entry point asks of the kernel.  M_FIX: the fixpoint; M_LEVEL: one flooding iteration per barrier round; M_TRAJ: the
 // same with the trajectory rows; M_CAPS: the same with a checkpoint at every cap.
 enum Mode { M_FIX, M_LEVEL, M_TRAJ, M_CAPS };
-constexpr bool kCnTable = false, kSockTable = true, kNarrow = false, kWide = true;
+constexpr bool kCnTable = false, kSockTable = true, kNarrow = false, kWide = true, kDeg = true;
 struct Form {
     Mode mode;
     bool sock;          // the CN table holds sockets instead of global VN ids
     bool wide;          // 32-bit queue entries, one 1024-thread workgroup per CU (LEVEL or TRAJ with sockets only)
+    bool deg = false;   // the _deg entry points: the degree pair of the parameters picks the instance (sockets only)
     // the A/B knobs SCLDPC_DEBUG_DECODER_KSWITCH, SCLDPC_DEBUG_GRID_DECODER and SCLDPC_DEBUG_LDS_PAD_DECODER act on these forms only
-    bool knobs() const { return mode != M_CAPS && !wide; }
+    bool knobs() const { return mode != M_CAPS && !wide && !deg; }
 };
 
 // the arguments of a call; an entry point leaves what it does not have at zero
@@ -650,15 +740,19 @@ struct Call {
 };
 
 using Kernel = void (*)(const SmArgs);
-constexpr int form_key(Mode mode, bool sock, bool wide, bool persist) { return mode * 8 + sock * 4 + wide * 2 + persist; }
+constexpr int form_key(Mode mode, bool sock, bool wide, bool persist, int pair = 0)
+{
+    return pair * 32 + mode * 8 + sock * 4 + wide * 2 + persist;
+}
 
-// The twelve instances <BLOCK, LEVEL, PERSIST, SOCK, TRAJ, CAPS, WIDE> with their VGPRs / SGPRs at -O3 for gfx950; no scratch
+// The instances <BLOCK, LEVEL, PERSIST, SOCK, TRAJ, CAPS, WIDE, DV, DC> with their VGPRs / SGPRs at -O3 for gfx950; no scratch
 // except where noted (as found; not looked into here).  persist: workgroup b decodes trials b, b + gridDim.x, … — reached through
-// SCLDPC_DEBUG_GRID_DECODER only, CN -> VN table only.  nullptr: no such instance.
-Kernel kernel_of(const Form &f, bool persist)
+// SCLDPC_DEBUG_GRID_DECODER only, CN -> VN table only.  pair: pair_of(dv, dc); the twelve (4,8) instances first, then five per
+// further pair (socket table: fixpoint, LEVEL, TRAJ, wide LEVEL, wide TRAJ).  nullptr: no such instance.
+Kernel kernel_of(const Form &f, bool persist, int pair = 0)
 {
     constexpr int S = kBlockSmall, W = kBlockWide;
-    switch (form_key(f.mode, f.sock, f.wide, persist)) {
+    switch (form_key(f.mode, f.sock, f.wide, persist, pair)) {
     case form_key(M_FIX, kCnTable, kNarrow, false):      return full_bp_small_kernel<S, false, false, false>;                   // 64 / 93
     case form_key(M_FIX, kSockTable, kNarrow, false):    return full_bp_small_kernel<S, false, false, true>;                    // 64 / 94
     case form_key(M_FIX, kCnTable, kNarrow, true):       return full_bp_small_kernel<S, false, true, false>;                    // 64 / 78, 136 B of scratch
@@ -671,9 +765,23 @@ Kernel kernel_of(const Form &f, bool persist)
     case form_key(M_CAPS, kSockTable, kNarrow, false):   return full_bp_small_kernel<S, true, false, true, false, true>;        // 63 / 94
     case form_key(M_LEVEL, kSockTable, kWide, false):    return full_bp_small_kernel<W, true, false, true, false, false, true>; // 63 / 94
     case form_key(M_TRAJ, kSockTable, kWide, false):     return full_bp_small_kernel<W, true, false, true, true, false, true>;  // 67 / 94
+    case form_key(M_FIX, kSockTable, kNarrow, false, 1):   return full_bp_small_kernel<S, false, false, true, false, false, false, 3, 6>;   // 65 / 94
+    case form_key(M_LEVEL, kSockTable, kNarrow, false, 1): return full_bp_small_kernel<S, true, false, true, false, false, false, 3, 6>;    // 63 / 94
+    case form_key(M_TRAJ, kSockTable, kNarrow, false, 1):  return full_bp_small_kernel<S, true, false, true, true, false, false, 3, 6>;     // 67 / 94
+    case form_key(M_LEVEL, kSockTable, kWide, false, 1):   return full_bp_small_kernel<W, true, false, true, false, false, true, 3, 6>;     // 63 / 94
+    case form_key(M_TRAJ, kSockTable, kWide, false, 1):    return full_bp_small_kernel<W, true, false, true, true, false, true, 3, 6>;      // 67 / 94
+    case form_key(M_FIX, kSockTable, kNarrow, false, 2):   return full_bp_small_kernel<S, false, false, true, false, false, false, 5, 10>;  // 71 / 94
+    case form_key(M_LEVEL, kSockTable, kNarrow, false, 2): return full_bp_small_kernel<S, true, false, true, false, false, false, 5, 10>;   // 67 / 94
+    case form_key(M_TRAJ, kSockTable, kNarrow, false, 2):  return full_bp_small_kernel<S, true, false, true, true, false, false, 5, 10, 6>; // 77 / 94, six waves per SIMD (28 B of scratch at seven): per_cu_of
+    case form_key(M_LEVEL, kSockTable, kWide, false, 2):   return full_bp_small_kernel<W, true, false, true, false, false, true, 5, 10>;    // 67 / 94
+    case form_key(M_TRAJ, kSockTable, kWide, false, 2):    return full_bp_small_kernel<W, true, false, true, true, false, true, 5, 10>;     // 81 / 94
     }
     return nullptr;
 }
+
+// Workgroups per CU the carve of an instance aims at: the narrow forms' seven, except where kernel_of() bounds the registers
+// for fewer waves per SIMD
+int per_cu_of(const Form &f, int pair) { return f.wide ? 1 : (pair == pair_of(5, 10) && f.mode == M_TRAJ) ? 6 : kPerCu; }
 
 // Every decoder entry point below is one call of this.  The checks come in one fixed order — the parameters, the form's own
 // arguments (rows, caps), the shape, the buffers — so a call with several defects reports the first of these.  The shape is
@@ -691,15 +799,14 @@ int launch(const char *who, const Form &f, const Call &c)
                 return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: caps must be strictly increasing and >= 1 (caps[%d] = %d)", who,
                                          k, c.caps[k]);
     }
-    if (const char *why = shape_limit(c.p, f.wide, f.sock)) return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
+    if (const char *why = shape_limit(c.p, f.wide, f.sock, f.deg)) return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
     if (c.ntrials < 0 || (c.ntrials > 0 && (!c.counters || !c.vn_adj16 || !c.cn_adj16 || !c.chan)))
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
     if (c.ntrials == 0) return SCLDPC_OK;
 
     SmArgs a{};
-    int per_cu = f.wide ? 1 : kPerCu;                                   // workgroups per CU the LDS carve aims at
-    while (per_cu > 1 && make_args(c.p, c.is_term, &a, per_cu, f.mode != M_FIX, f.wide) != 0) per_cu--;
-    if (make_args(c.p, c.is_term, &a, per_cu, f.mode != M_FIX, f.wide) != 0)
+    const int pair = f.deg ? pair_of(c.p->dv, c.p->dc) : 0;
+    if (carve(c.p, c.is_term, f.mode != M_FIX, f.wide, &a, per_cu_of(f, pair)) < 0)
         return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: LDS: the CN counts and VN bits do not fit", who);
     scldpc::magic_of(c.p->vns_pos, a.n + 32, &a.magic_v);
     scldpc::magic_of(c.p->cns_pos, a.nk, &a.magic_c);
@@ -723,7 +830,7 @@ int launch(const char *who, const Form &f, const Call &c)
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: no persistent form with the socket table", who);
     // (as found: the rows form has no persistent instance either and takes a debug grid as it is — it then decodes the first
     // `grid` trials only)
-    const Kernel kern = kernel_of(f, grid < c.ntrials && f.mode != M_TRAJ);
+    const Kernel kern = kernel_of(f, grid < c.ntrials && f.mode != M_TRAJ, pair);
     if (int rc = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(f.wide ? kBlockWide : kBlockSmall), lds_bytes, static_cast<hipStream_t>(c.stream), a);
     SCLDPC_HIP_CHECK(hipGetLastError());
@@ -826,5 +933,57 @@ extern "C" int scldpc_full_bp_traj_device_wide(const scldpc_code_params *p, int3
 {
     if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_wide: null d_rows");
     return launch("scldpc_full_bp_traj_device_wide", {M_TRAJ, kSockTable, kWide},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap});
+}
+
+// The same five decoders for the regular pairs (3,6), (4,8) and (5,10): 4 bits of LDS per CN where scldpc_full_bp_device_adj16 and
+// scldpc_full_bp_fixpoint_device_adj16 (decodeBP, BPF:900-1140; rows: the BPT build, BPT:988, 1037-1038, 1051) keep a 16-bit word.
+// They read the 2-byte VN -> CN table [T][n][dv] of scldpc_sample_philox_device_adj16 and the CN -> socket table [T][nk][dc] of
+// scldpc_cn_sockets_device; (4,8) runs the _sock16 / _wide instances.
+extern "C" int scldpc_full_bp_deg_supported(const scldpc_code_params *p) { return shape_limit(p, false, true, true) == nullptr; }
+
+extern "C" int scldpc_full_bp_deg_wide_supported(const scldpc_code_params *p) { return shape_limit(p, true, true, true) == nullptr; }
+
+extern "C" int scldpc_full_bp_fixpoint_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                                  const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t is_term,
+                                                  int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
+{
+    return launch("scldpc_full_bp_fixpoint_device_deg", {M_FIX, kSockTable, kNarrow, kDeg},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, 0, is_term, d_counters, d_erased_bits, stream});
+}
+
+extern "C" int scldpc_full_bp_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                         const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
+                                         int32_t is_term, int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
+{
+    return launch("scldpc_full_bp_device_deg", {M_LEVEL, kSockTable, kNarrow, kDeg},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream});
+}
+
+extern "C" int scldpc_full_bp_traj_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                              const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
+                                              int32_t is_term, int32_t *d_counters, int32_t *d_rows, int32_t rows_cap,
+                                              uint32_t *d_erased_bits, void *stream)
+{
+    if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_deg: null d_rows");
+    return launch("scldpc_full_bp_traj_device_deg", {M_TRAJ, kSockTable, kNarrow, kDeg},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap});
+}
+
+extern "C" int scldpc_full_bp_device_deg_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                              const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
+                                              int32_t is_term, int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
+{
+    return launch("scldpc_full_bp_device_deg_wide", {M_LEVEL, kSockTable, kWide, kDeg},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream});
+}
+
+extern "C" int scldpc_full_bp_traj_device_deg_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                                   const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
+                                                   int32_t is_term, int32_t *d_counters, int32_t *d_rows, int32_t rows_cap,
+                                                   uint32_t *d_erased_bits, void *stream)
+{
+    if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_deg_wide: null d_rows");
+    return launch("scldpc_full_bp_traj_device_deg_wide", {M_TRAJ, kSockTable, kWide, kDeg},
                   {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap});
 }

@@ -349,6 +349,29 @@ def full_bp_wide(p, d_adj16, d_cn_sock, d_chan, max_it=0, is_term=True, rows_cap
                     torch.zeros)                        # zeros, as full_bp's
 
 
+def full_bp_deg_supported(p, wide=False):
+    """The (3,6), (4,8) and (5,10) chains the _deg forms of the 4-bit decoder take: at most 65536 CNs per trial, or (wide=True)
+    a state that leaves 1024 32-bit queue entries per queue in one CU's LDS."""
+    fn = lib().scldpc_full_bp_deg_wide_supported if wide else lib().scldpc_full_bp_deg_supported
+    return bool(fn(C.byref(p)))
+
+
+def full_bp_deg(p, d_adj16, d_cn_sock, d_chan, max_it=0, is_term=True, rows_cap=0, want_erased=False, counters=None, wide=False):
+    """scldpc_full_bp_device_deg / scldpc_full_bp_traj_device_deg (rows_cap > 0), wide=True: their _wide forms — full_bp's
+    counters, rows and erased bitmap for the pairs (3,6), (4,8), (5,10) from the 2-byte VN -> CN table and
+    cn_sockets(p, d_adj16); the same dict as full_bp_cn16 / full_bp_wide."""
+    name = "scldpc_full_bp_%sdevice_deg%s" % ("traj_" if rows_cap > 0 else "", "_wide" if wide else "")
+    return _full_bp(p, d_adj16, d_cn_sock, d_chan, _level_call(getattr(lib(), name), max_it, is_term, rows_cap), counters,
+                    want_erased, rows_cap, torch.zeros)                 # zeros, as full_bp's
+
+
+def full_bp_fixpoint_deg(p, d_adj16, d_cn_sock, d_chan, is_term=True, want_erased=False, counters=None):
+    """scldpc_full_bp_fixpoint_device_deg: full_bp_fixpoint's counters for the same pairs and tables (narrow shapes only)."""
+    fn = lib().scldpc_full_bp_fixpoint_device_deg
+    return _full_bp(p, d_adj16, d_cn_sock, d_chan, lambda head, cnt, rows, erased, stream:
+                    fn(*head, 1 if is_term else 0, cnt, erased, stream), counters, want_erased)
+
+
 def check_caps(caps):
     """The cap list of full_bp_caps_cn16 as a tuple, with the C side's rules: 1 .. MAX_CAPS strictly increasing caps >= 1."""
     caps = tuple(int(k) for k in caps)

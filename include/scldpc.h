@@ -251,6 +251,38 @@ int scldpc_full_bp_device_wide(const scldpc_code_params *p, int32_t ntrials, con
 int scldpc_full_bp_traj_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                     const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
                                     int32_t *d_counters, int32_t *d_rows, int32_t rows_cap, uint32_t *d_erased_bits, void *stream);
+/* The 4-bit decoders above for the regular pairs (3,6), (4,8) and (5,10), on the socket table: what
+ * scldpc_full_bp_device_adj16 / scldpc_full_bp_fixpoint_device_adj16 compute for these pairs (decodeBP, BPF:900-1140; the rows of
+ * the BPT build, BPT:988, 1037-1038, 1051) with 4 bits of LDS per CN instead of a 16-bit word.  They read d_vn_adj16 uint16
+ * [ntrials][n][dv] (scldpc_sample_philox_device_adj16) and d_cn_sock16 uint16 [ntrials][nk][dc] (scldpc_cn_sockets_device).
+ * Arguments, counters, rows and error codes of
+ *   scldpc_full_bp_fixpoint_device_deg     as scldpc_full_bp_fixpoint_device_sock16   (BPF:900-1140 without the iteration count)
+ *   scldpc_full_bp_device_deg              as scldpc_full_bp_device_sock16            (BPF:900-1140)
+ *   scldpc_full_bp_traj_device_deg         as scldpc_full_bp_traj_device_sock16       (BPT:900-1140 with its rows)
+ *   scldpc_full_bp_device_deg_wide         as scldpc_full_bp_device_wide              (more than 65536 CNs per trial)
+ *   scldpc_full_bp_traj_device_deg_wide    as scldpc_full_bp_traj_device_wide
+ * For (4,8) they run the _sock16 / _wide kernels: bit for bit the same result.  SCLDPC_ERR_TOO_LARGE names the limit: a pair
+ * without a kernel, dc > 15 (a CN's count is a nibble), sockets beyond 16 bits, more than 65536 CNs per trial (narrow), a
+ * state that leaves no room for the queues (wide: fewer than 1024 entries per queue), or queues so short that a wave's
+ * per-iteration tallies could leave their 15 + 17 bits.  *_supported: 1 when every narrow (wide) form takes the ensemble.
+ * No caps form. */
+int scldpc_full_bp_deg_supported(const scldpc_code_params *p);        /* narrow: <= 65536 CNs per trial */
+int scldpc_full_bp_deg_wide_supported(const scldpc_code_params *p);
+int scldpc_full_bp_fixpoint_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                       const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t is_term,
+                                       int32_t *d_counters, uint32_t *d_erased_bits, void *stream);
+int scldpc_full_bp_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                              const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
+                              int32_t *d_counters, uint32_t *d_erased_bits, void *stream);
+int scldpc_full_bp_traj_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                   const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
+                                   int32_t *d_counters, int32_t *d_rows, int32_t rows_cap, uint32_t *d_erased_bits, void *stream);
+int scldpc_full_bp_device_deg_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                   const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
+                                   int32_t *d_counters, uint32_t *d_erased_bits, void *stream);
+int scldpc_full_bp_traj_device_deg_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                        const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
+                                        int32_t *d_counters, int32_t *d_rows, int32_t rows_cap, uint32_t *d_erased_bits, void *stream);
 
 /* decodeBP_SW, square window (BPW:628-912): window of W positions, init_it iterations for the
  * first window and max_it for the others (init_it == 0 ⇒ max_it, BPW:2101-2102). */
