@@ -49,6 +49,7 @@ EXPORTS = (
     "scldpc_full_bp_deg_supported", "scldpc_full_bp_deg_wide_supported", "scldpc_full_bp_fixpoint_device_deg",
     "scldpc_full_bp_device_deg", "scldpc_full_bp_traj_device_deg", "scldpc_full_bp_device_deg_wide",
     "scldpc_full_bp_traj_device_deg_wide",
+    "scldpc_sw_bp_ring_deg_supported", "scldpc_sw_bp_ring_device_deg",
 )
 
 
@@ -159,6 +160,8 @@ def lib():
     L.scldpc_sw_bp_ring_supported.argtypes = [pp, i32]
     L.scldpc_cn_sockets_device.argtypes = [pp, i32, vp, vp, vp]
     L.scldpc_sw_bp_ring_device.argtypes = [pp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.scldpc_sw_bp_ring_deg_supported.argtypes = L.scldpc_sw_bp_ring_supported.argtypes
+    L.scldpc_sw_bp_ring_device_deg.argtypes = L.scldpc_sw_bp_ring_device.argtypes
     L.scldpc_accumulate_run_device.argtypes = [i32, vp, i64, vp, vp]
     L.scldpc_accumulate_peel_device.argtypes = [i32, vp, i64, vp, vp]
     L.scldpc_clear_channel_range_device.argtypes = [pp, i32, i32, i32, vp, vp]

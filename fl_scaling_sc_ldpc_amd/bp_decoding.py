@@ -141,6 +141,11 @@ WIDE_BY_DEFAULT = True
 # tools/deg_speedup.py (profiles/deg_speedup.json)
 DEG_BY_DEFAULT = False
 
+# Whether Simulator(ring=None) takes the ring window decoder for the pairs (3,6) and (5,10) where it applies: True only if every
+# repetition of the new path beats every repetition of the whole-chain kernel end to end on every shape of
+# tools/ring_deg_speedup.py, with identical counters (profiles/ring_deg_speedup.json)
+RING_DEG_BY_DEFAULT = False
+
 
 # The path of a Simulator, decided once in Simulator._select:
 #   adj_dtype    VN -> CN table: torch.int16 (position-local ids) or torch.int32 (the reference's VNdegree)
@@ -148,7 +153,7 @@ DEG_BY_DEFAULT = False
 #                generation, with the CN -> VN / CN -> socket table)
 #   cn_table     the CN table kept next to the VN -> CN one: None, "vn" or "sock"
 #   cn_pass      that table comes from the cn_sockets pass (the sampler does not emit it)
-#   decoder      "sw_ring" / "sw_chain" (E.sw_bp), or the full-BP call that walks the iterations: "level16", "wide", "full_bp",
+#   decoder      "sw_ring" / "sw_chain" (E.sw_bp; "sw_ring" with cn_pass: the _deg entry points, pairs (3,6) and (5,10)), or the full-BP call that walks the iterations: "level16", "wide", "full_bp",
 #                "deg16" / "degwide" (the 4-bit level decoder of the pairs (3,6) and (5,10), 16- / 32-bit queue entries)
 #   fix_decoder  the fixpoint kernel an unlimited fixpoint run takes for calls without rows: "fixpoint16", "fixpoint_deg",
 #                "fixpoint" or None
@@ -166,13 +171,16 @@ class Simulator:
 
     def __init__(self, p, decoder="full", W=0, max_it=0, init_it=0, is_term=True, doped=(), batch=2048,
                  rng="philox", seed=1, device=None, rows_cap=0, schedule="flooding", shard_frames=True, index=0,
-                 verbose=False, caps=None, wide=None, deg=None):
+                 verbose=False, caps=None, wide=None, deg=None, ring=None):
         # wide: the 1024-thread 4-bit level decoder for trials of more than 65536 CNs (full_bp_small wide).  None = where
         # WIDE_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path, for A/B and tests)
         self.want_wide = wide
         # deg: the 4-bit level decoder for dv, dc other than (4,8) (full_bp_small's (3,6) and (5,10) instances).  None = where
         # DEG_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path)
         self.want_deg = deg
+        # ring: the ring window decoder (sw_ring) for dv, dc other than (4,8), decoder="sw" only.  None = where RING_DEG_BY_DEFAULT
+        # says, True = wherever it applies, False = never (the whole-chain kernel)
+        self.want_ring = ring
         self.p, self.decoder, self.W, self.max_it, self.init_it = p, decoder, W, max_it, init_it
         # caps: several MaxNumIt from one decode (run_point_caps; the level-synchronous 4-bit decoder only)
         self.caps = E.check_caps(caps) if caps is not None else None
@@ -214,6 +222,10 @@ class Simulator:
             ring = adj_dtype == torch.int16 and E.sw_ring_supported(p, self.W)
             if ring and E.sock16_supported(p):
                 self.path = Path(adj_dtype, "sock16", "sock", False, "sw_ring", None)
+            elif ring_deg_reason(p, self.W, self.rng, self.want_ring) is None:
+                # another degree pair the ring kernel has an instance for: the first-generation sampler writes the 2-byte VN -> CN
+                # table for every dv, the cn_sockets pass the CN -> socket table into the preallocated d_cn
+                self.path = Path(adj_dtype, first, "sock", True, "sw_ring", None)
             else:
                 self.path = Path(adj_dtype, first, None, False, "sw_ring" if ring else "sw_chain", None)
         elif table is not None:
@@ -250,6 +262,7 @@ class Simulator:
         self.gen2, self.lvl2, self.wide = path.fix_decoder == "fixpoint16", path.decoder == "level16", path.decoder == "wide"
         self.sock = (self.gen2 or self.lvl2) and path.cn_table == "sock"
         self.ring2 = path.decoder == "sw_ring" and path.cn_table == "sock"
+        self.ring_deg = path.decoder == "sw_ring" and path.cn_pass
         self.wide_sock = self.wide and not path.cn_pass
         self.deg = path.decoder in ("deg16", "degwide")
         if self.caps is not None and not (self.lvl2 and self.rows_cap == 0 and not self.doped):
@@ -287,6 +300,9 @@ class Simulator:
     def kernel_choice(self):
         """Which device kernels this configuration runs."""
         path = self.path
+        if path.decoder == "sw_ring" and path.cn_pass:
+            return ("sampler (first generation) + cn_sockets pass + sw_ring (window state in LDS, dv = %d, dc = %d)"
+                    % (self.p.dv, self.p.dc))
         if path.decoder == "sw_ring":
             return ("sampler_v2 (CN->socket table) + sw_ring (window state in LDS)" if path.cn_table is not None else
                     "sampler (first generation) + sw_ring + cn_sockets pass")
@@ -325,7 +341,8 @@ class Simulator:
         path, adj, ch, cnt = self.path, self.d_adj[:nb], self.d_ch[:nb], self.d_cnt[:nb]
         if path.decoder in ("sw_ring", "sw_chain"):
             return E.sw_bp(self.p, adj, ch, self.W, self.max_it, self.init_it, counters=cnt,
-                           d_cn_sock=self.d_cn[:nb] if path.cn_table is not None else None)
+                           d_cn_sock=self.d_cn[:nb] if path.cn_table is not None else None,
+                           ring=True if self.ring_deg else None, deg=self.ring_deg)
         # the fixpoint kernels report neither iteration counts nor rows: a call that wants rows walks the iterations
         decoder = path.fix_decoder if (path.fix_decoder is not None and not want_rows) else path.decoder
         sockets, rows_cap = path.cn_table == "sock", self.rows_cap if want_rows else 0
@@ -487,6 +504,24 @@ class Simulator:
             frame0 += R
         bad = bad.cpu().tolist()
         return [PointResult(eps, p.n, p.L, runs[k].cpu().numpy(), bad=bad[k]) for k in range(K)]
+
+
+def ring_deg_reason(p, W, rng, want=True):
+    """Why decoder="sw" does not take the ring window decoder of the pairs (3,6) and (5,10) — sampler (first generation) +
+    cn_sockets pass + sw_ring through the _deg entry points — on this configuration, or None where it does.  want: the
+    Simulator's ring argument (None: RING_DEG_BY_DEFAULT)."""
+    if (p.dv, p.dc) == (4, 8):
+        return "dv = 4, dc = 8 has a ring path of its own, chosen without this switch"
+    if not (RING_DEG_BY_DEFAULT if want is None else bool(want)):
+        return "switched off"
+    if rng != "philox":
+        return "--rng %s samples the 4-byte VN -> CN table on the host: the ring kernel reads the 2-byte tables" % rng
+    if p.cns_pos > 65536:
+        return "more than 65536 CNs per position: no 2-byte VN -> CN table"
+    if not E.sw_ring_deg_supported(p, W):
+        return ("the ring kernel takes the pairs (3,6), (4,8) and (5,10) with W >= 1, vns_pos * dv <= 65535, L + dv - 1 <= 65535 "
+                "and a window state that fits the LDS (dv = %d, dc = %d, L = %d, N = %d, W = %d)" % (p.dv, p.dc, p.L, p.vns_pos, W))
+    return None
 
 
 def caps_sequential_reason(p, rng, num_doped, schedule):
@@ -683,13 +718,19 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
         return _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, shard, by_points)
     # the decoders' loop is do { … } while (iter < MaxNumIt) (BPF:1065, BPT:1076): at least one iteration runs
     cap = max(1, max_it)
+    ring = {"auto": None, "on": True, "off": False}[getattr(opts, "ring", "auto")]
+    if ring and prog == "sw_lim_iter":
+        why = ring_deg_reason(p, W, opts.rng)
+        if why is not None:
+            raise SystemExit("--ring on: " + why)
     sim_obj = Simulator(p, decoder=decoder, W=W, max_it=cap, init_it=init_it,
                         is_term=is_term, doped=doped, batch=opts.batch, rng=opts.rng, seed=opts.seed,
                         rows_cap=opts.rows_cap if prog == "bp_traj" else 0, schedule=getattr(opts, "schedule", "flooding"),
                         shard_frames=shard == "frames", device=getattr(opts, "device", None), index=replica,
                         verbose=rank == 0 and not opts.quiet,
                         wide={"auto": None, "on": True, "off": False}[getattr(opts, "wide", "auto")],
-                        deg={"auto": None, "on": True, "off": False}[getattr(opts, "deg", "auto")])
+                        deg={"auto": None, "on": True, "off": False}[getattr(opts, "deg", "auto")],
+                        ring=ring if prog == "sw_lim_iter" else None)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     t0 = time.time()
@@ -798,6 +839,10 @@ def _parser(prog):
         ap.add_argument("--deg", choices=("auto", "on", "off"), default="auto",
                         help="full BP with --dv/--dc 3/6 or 5/10: the 4-bit level decoder (on), the first-generation decoder "
                              "(off), or the measured default (auto); same files")
+    if prog == "sw_lim_iter":
+        ap.add_argument("--ring", choices=("auto", "on", "off"), default="auto",
+                        help="--dv/--dc 3/6 or 5/10: the ring window decoder (on), the whole-chain kernel (off), or the measured "
+                             "default (auto); same files")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")

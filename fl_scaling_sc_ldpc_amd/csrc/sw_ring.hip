@@ -2,11 +2,11 @@
 //
 // sw_bp.hip keeps one word per CN of the WHOLE chain (in LDS up to N = 1024, in a device workspace beyond: L2 atomics,
 // two trials per CU).  But window posW only ever fires CNs of positions [posW, posW+W) and only releases VNs of positions
-// [posW, posW+W), whose edges reach CN positions up to posW+W+2: everything to the left is frozen for good (BPW:672-693,
+// [posW, posW+W), whose edges reach CN positions up to posW+W+dv-2: everything to the left is frozen for good (BPW:672-693,
 // SURVEY.md §7.4 B), everything further right has not been looked at yet.  So the kernel keeps a RING over positions:
-//   * CN counts, 4 bits per CN, for positions [posW-4, posW+W+2]  (W+7 slots; the four slots behind the window serve the
-//     size-2 stopping-set expurgation, see below),
-//   * S bits (what the CNs still see as erased), for VN positions [posW-3, posW+W]  (W+4 slots),
+//   * CN counts, 4 bits per CN, for positions [posW-dv, posW+W+dv-2]  (W+2dv-1 slots, W+7 at dv = 4; the dv slots behind the
+//     window serve the size-2 stopping-set expurgation, see below),
+//   * S bits (what the CNs still see as erased), for VN positions [posW-(dv-1), posW+W]  (W+dv slots),
 // 21 KB per trial at (L=100, N=2000, W=10) instead of 412 KB of CN words in a workspace: seven 256-thread workgroups per
 // CU with all atomics in LDS.  A VN position ENTERS the ring when the window first reaches it (its channel bits are read,
 // its erased VNs count themselves into their dv CN positions — the right-most of which is a fresh slot), and leaves it
@@ -25,8 +25,12 @@
 // Size-2 stopping sets (BPW:850-908: every failing position contributes): VN position q is examined when the window has
 // moved dv positions past it — then its dv CN positions are final and still in the ring; a qualifying partner lies in the
 // same position, so only S bits of position q are consulted.
+//
+// Instances: (dv, dc) = (4,8), and (3,6) and (5,10) behind scldpc_sw_bp_ring_device_deg.  A queue entry is
+// [CN position : 16 | CN : 16], a count a nibble (dc <= 15).
 #include "common.h"
 #include "kernel_util.h"
+#include "table_rows.h"
 
 namespace {
 
@@ -54,9 +58,12 @@ __device__ __forceinline__ uint32_t bits_at(const uint32_t *w, int nw, long long
     return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
 }
 
+// DV, DC: the degree pair, fixed at compile time (the rows of both tables are unrolled; loads no wider than a row's alignment
+// allows: table_rows.h).  Every instance holds the bound of eight workgroups per CU (64 VGPRs) without scratch.
 template <int DV, int DC>
 __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) void sw_ring_kernel(const RArgs a)
 {
+    static_assert(DC <= 15 && DC % 2 == 0 && DV < DC, "a CN's count of erased neighbours is a nibble; CN rows are read as 32-bit words");
     extern __shared__ uint32_t lds[];
     uint32_t *cnt = lds;                                                  // [R][Cw] words of 8 count nibbles
     uint32_t *S = lds + a.off_S;                                          // [RV][wpp]
@@ -70,8 +77,11 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
     const int trial = blockIdx.x;
     const int L = a.L, V = a.V, C = a.C, W = a.W, R = a.R, RV = a.RV, Cw = a.Cw, wpp = a.wpp, qcap = a.qcap;
     const int D = L + DV - 1;
-    const uint2 *vrow = reinterpret_cast<const uint2 *>(a.vn_adj16) + (size_t)trial * a.n;
+    const auto *vrow = reinterpret_cast<const typename VnUnit<DV>::type *>(a.vn_adj16) + (size_t)trial * a.n * VnUnit<DV>::per_row;
     const uint16_t *crow = a.cn_sock16 + (size_t)trial * a.nk * DC;
+    const auto *crow_u = reinterpret_cast<const typename CnUnit<DC>::type *>(crow);
+    auto vn_row = [&](int j) { if constexpr (DV == 4) return load_row(vrow, j); else return load_row<DV>(vrow, j); };
+    auto cn_row = [&](int c) { if constexpr (DC == 8) return load_row(crow_u, c); else return load_row<DC>(crow_u, c); };
     const uint32_t *ch = a.chan + (size_t)trial * a.nw;
     uint32_t *eout = a.erased_out ? a.erased_out + (size_t)trial * a.nw : nullptr;
 
@@ -112,22 +122,21 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
         mine = wave_sum(mine);
         if (lane == 0 && mine) { atomicAdd(&pos_cnt[qq], mine); atomicAdd(&scal[R_NCH], mine); }
         __syncthreads();
-        // rows are loaded unconditionally, four per thread in flight (coalesced 8-byte loads), then the erased ones count
+        // rows are loaded unconditionally, four per thread in flight (dv = 4: coalesced 8-byte loads), then the erased ones count
         for (int t0 = tid; t0 < V; t0 += 4 * kBlock) {
-            uint2 r[4];
+            Row<DV> r[4];
             bool er[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int t = t0 + u * kBlock;
                 er[u] = false;
-                if (t < V) { r[u] = vrow[(size_t)qq * V + t]; er[u] = (S[sslot(qq) + (t >> 5)] >> (t & 31)) & 1u; }
+                if (t < V) { r[u] = vn_row(qq * V + t); er[u] = (S[sslot(qq) + (t >> 5)] >> (t & 31)) & 1u; }
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 if (!er[u]) continue;
-                const uint32_t l[4] = {r[u].x & 0xFFFFu, r[u].x >> 16, r[u].y & 0xFFFFu, r[u].y >> 16};
 #pragma unroll
-                for (int i = 0; i < DV; i++) atomicAdd(&cnt[cslot(qq + i) + (l[i] >> 3)], 1u << ((l[i] & 7) * 4));
+                for (int i = 0; i < DV; i++) atomicAdd(&cnt[cslot(qq + i) + (r[u][i] >> 3)], 1u << ((r[u][i] & 7) * 4));
             }
         }
         __syncthreads();
@@ -138,8 +147,10 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
         if (pos_cnt[qe] == 0) return;                                     // uniform: pos_cnt is read after a barrier
         for (int t = tid; t < V; t += kBlock) {
             if (!((S[sslot(qe) + (t >> 5)] >> (t & 31)) & 1u)) continue;
-            const uint2 r = vrow[(size_t)qe * V + t];
-            const uint32_t l[4] = {r.x & 0xFFFFu, r.x >> 16, r.y & 0xFFFFu, r.y >> 16};
+            const Row<DV> r = vn_row(qe * V + t);
+            uint32_t l[DV];
+#pragma unroll
+            for (int i = 0; i < DV; i++) l[i] = r[i];
             bool pair = true;
 #pragma unroll
             for (int i = 0; i < DV; i++) pair = pair && nib(qe + i, (int)l[i]) == 2u;
@@ -231,26 +242,23 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
             int removed = 0;
             // CN (p, l) of the snapshot: release its lone erased neighbour unless that one is frozen
             // out[i] = 1 + [CN position | CN] of edge i if this release left that CN with one erased neighbour inside the window
-            auto release = [&](int p, int l, uint32_t (&out)[4]) {
+            auto release = [&](int p, int l, uint32_t (&out)[DV]) {
                 if (p < posW) return;                                     // queued by the previous window for the position it left
-                const uint4 s4 = *reinterpret_cast<const uint4 *>(crow + ((size_t)p * C + l) * DC);
-                const uint32_t sk[8] = {s4.x & 0xFFFFu, s4.x >> 16, s4.y & 0xFFFFu, s4.y >> 16,
-                                        s4.z & 0xFFFFu, s4.z >> 16, s4.w & 0xFFFFu, s4.w >> 16};
+                const Row<DC> sk = cn_row(p * C + l);
                 int jq = -1, jt = 0;
 #pragma unroll
-                for (int k = 0; k < 8; k++) {
+                for (int k = 0; k < DC; k++) {
                     if (sk[k] == 0xFFFFu) continue;
                     const int qq = p - (int)(sk[k] % DV), t = (int)(sk[k] / DV);
                     if ((unsigned)qq < (unsigned)L && ((S[sslot(qq) + (t >> 5)] >> (t & 31)) & 1u)) { jq = qq; jt = t; }
                 }
                 if (jq < posW) return;                                    // none left (released this round) or frozen (BPW:745)
-                const uint2 r = vrow[(size_t)jq * V + jt];                // issued before the claim: overlaps its round trip
+                const Row<DV> ll = vn_row(jq * V + jt);                   // issued before the claim: overlaps its round trip
                 const uint32_t bit = 1u << (jt & 31);
                 if (!(atomicAnd(&S[sslot(jq) + (jt >> 5)], ~bit) & bit)) return;
                 atomicSub(&pos_cnt[jq], 1);
                 removed++;
-                const uint32_t ll[4] = {r.x & 0xFFFFu, r.x >> 16, r.y & 0xFFFFu, r.y >> 16};
-                uint32_t o[4];
+                uint32_t o[DV];
 #pragma unroll
                 for (int i = 0; i < DV; i++)                              // the dv returning atomics go out back to back
                     o[i] = atomicSub(&cnt[cslot(jq + i) + (ll[i] >> 3)], 1u << ((ll[i] & 7) * 4));
@@ -260,8 +268,10 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
                         out[i] = 1u + (((uint32_t)(jq + i) << 16) | ll[i]);
             };
             // a wave appends its lanes' entries behind *push: one prefix scan + one LDS atomic per wave
-            auto append = [&](const uint32_t (&out)[4]) {
-                const int mine = (out[0] != 0u) + (out[1] != 0u) + (out[2] != 0u) + (out[3] != 0u);
+            auto append = [&](const uint32_t (&out)[DV]) {
+                int mine = 0;
+#pragma unroll
+                for (int i = 0; i < DV; i++) mine += out[i] != 0u;
                 const int incl = (int)wave_inclusive_scan((uint32_t)mine);
                 const int tot = __builtin_amdgcn_readlane(incl, 63);
                 if (tot == 0) return;
@@ -269,7 +279,7 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
                 if (lane == 0) base = atomicAdd(push, tot);
                 int idx = __builtin_amdgcn_readfirstlane(base) + incl - mine;
 #pragma unroll
-                for (int i = 0; i < 4; i++)
+                for (int i = 0; i < DV; i++)
                     if (out[i]) { if (idx < qcap) qn[idx] = out[i] - 1u; else *ovf = 1; idx++; }
             };
             if (scan) {
@@ -288,7 +298,7 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
                         const int w = w0 + lane;
                         uint32_t z = w < Cw ? (uint32_t)fbits[(p - posW) * Cw + w] : 0u;
                         while (__any(z != 0u)) {
-                            uint32_t out[4] = {0, 0, 0, 0};
+                            uint32_t out[DV] = {};
                             if (z) {
                                 const int k = __ffs((int)z) - 1;
                                 z &= z - 1;
@@ -299,7 +309,7 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
                     }
             } else {
                 for (int k0 = (tid >> 6) * 64; k0 < ncur; k0 += kBlock) {
-                    uint32_t out[4] = {0, 0, 0, 0};
+                    uint32_t out[DV] = {};
                     if (k0 + lane < ncur) release((int)(qc[k0 + lane] >> 16), (int)(qc[k0 + lane] & 0xFFFFu), out);
                     append(out);
                 }
@@ -387,6 +397,17 @@ __global__ __launch_bounds__(256) void cn_sockets_kernel(const IArgs a)
     for (int i = tid; i < a.C * a.dc; i += 256) dst[i] = stage[i];
 }
 
+using RingKernel = void (*)(const RArgs);
+
+// the instance of a degree pair, nullptr: none
+RingKernel ring_kernel_of(int dv, int dc)
+{
+    if (dv == 4 && dc == 8) return sw_ring_kernel<4, 8>;
+    if (dv == 3 && dc == 6) return sw_ring_kernel<3, 6>;
+    if (dv == 5 && dc == 10) return sw_ring_kernel<5, 10>;
+    return nullptr;
+}
+
 int ring_args(const scldpc_code_params *p, int W, RArgs *a)
 {
     a->dv = p->dv; a->dc = p->dc; a->L = p->L; a->V = p->vns_pos; a->C = p->cns_pos;
@@ -411,6 +432,47 @@ int ring_args(const scldpc_code_params *p, int W, RArgs *a)
     a->off_q1 = take(qcap);
     a->total = off;
     return 4 * off <= scldpc::kMaxLdsBytes ? 0 : -1;
+}
+
+// Which limit keeps (p, W) from scldpc_sw_bp_ring_device_deg; nullptr: none
+const char *ring_deg_limit(const scldpc_code_params *p, int W)
+{
+    if (scldpc::check_params(p)) return "invalid code parameters";
+    if (p->dc > 15) return "dc must be at most 15 (a CN's count of erased neighbours is kept in 4 bits)";
+    if (!ring_kernel_of(p->dv, p->dc)) {
+        static thread_local char text[96];
+        snprintf(text, sizeof text, "no instance for dv = %d, dc = %d (takes (3,6), (4,8) and (5,10))", p->dv, p->dc);
+        return text;
+    }
+    if (W < 1) return "need W >= 1";
+    if ((int64_t)p->vns_pos * p->dv > 65535) return "sockets: vns_pos * dv must fit 16 bits (at most 65535)";
+    if (p->cns_pos > 65536) return "at most 65536 CNs per position (16-bit position-local CN ids)";
+    if ((int64_t)p->L + p->dv - 1 > 65535) return "queue: L + dv - 1 CN positions must fit 16 bits (at most 65535)";
+    // the state in 64 bits first: ring_args computes in int
+    const int64_t state = ((int64_t)W + 2 * p->dv - 1) * ((p->cns_pos + 7) / 8) + ((int64_t)W + p->dv) * ((p->vns_pos + 31) / 32) +
+                          ((int64_t)W * ((p->cns_pos + 7) / 8) + 3) / 4 + 2 * (int64_t)p->L;
+    RArgs a{};
+    if (4 * state > scldpc::kMaxLdsBytes || ring_args(p, W, &a) != 0)
+        return "LDS: the window's CN counts, S bits and queues exceed 160 KiB";
+    return nullptr;
+}
+
+int ring_launch(const char *who, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16, const uint16_t *d_cn_sock16,
+                const uint32_t *d_chan_bits, int32_t W, int32_t max_it, int32_t init_it, int32_t *d_counters,
+                uint32_t *d_erased_bits, void *stream)
+{
+    RArgs a{};
+    ring_args(p, W, &a);
+    a.max_it = max_it; a.init_it = init_it ? init_it : max_it;           // BPW:2101-2102
+    a.vn_adj16 = d_vn_adj16; a.cn_sock16 = d_cn_sock16; a.chan = d_chan_bits;
+    a.counters = d_counters; a.erased_out = d_erased_bits;
+    RingKernel kern = ring_kernel_of(p->dv, p->dc);
+    if (!kern) return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: no instance for dv = %d, dc = %d", who, p->dv, p->dc);
+    const size_t lds_bytes = 4u * (size_t)a.total;
+    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
+    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(kBlock), lds_bytes, static_cast<hipStream_t>(stream), a);
+    SCLDPC_HIP_CHECK(hipGetLastError());
+    return SCLDPC_OK;
 }
 
 }  // namespace
@@ -458,15 +520,24 @@ extern "C" int scldpc_sw_bp_ring_device(const scldpc_code_params *p, int32_t ntr
     if (!scldpc_sw_bp_ring_supported(p, W))
         return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: takes dv = 4, dc = 8, 16-bit sockets and a window that fits the LDS", who);
     if (ntrials == 0) return SCLDPC_OK;
-    RArgs a{};
-    ring_args(p, W, &a);
-    a.max_it = max_it; a.init_it = init_it ? init_it : max_it;           // BPW:2101-2102
-    a.vn_adj16 = d_vn_adj16; a.cn_sock16 = d_cn_sock16; a.chan = d_chan_bits;
-    a.counters = d_counters; a.erased_out = d_erased_bits;
-    void (*kern)(const RArgs) = sw_ring_kernel<4, 8>;
-    const size_t lds_bytes = 4u * (size_t)a.total;
-    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
-    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(kBlock), lds_bytes, static_cast<hipStream_t>(stream), a);
-    SCLDPC_HIP_CHECK(hipGetLastError());
-    return SCLDPC_OK;
+    return ring_launch(who, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, W, max_it, init_it, d_counters, d_erased_bits, stream);
+}
+
+// The same decoder for the regular pairs (3,6), (4,8) and (5,10): sw_ring_kernel's instance of the pair ((4,8): the one above).
+// 1 when scldpc_sw_bp_ring_device_deg takes (p, W)
+extern "C" int scldpc_sw_bp_ring_deg_supported(const scldpc_code_params *p, int32_t W) { return ring_deg_limit(p, W) == nullptr; }
+
+extern "C" int scldpc_sw_bp_ring_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                            const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t W, int32_t max_it,
+                                            int32_t init_it, int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
+{
+    const char *who = "scldpc_sw_bp_ring_device_deg";
+    if (int rc = scldpc::check_params(p)) return rc;
+    if (W < 1 || max_it < 0 || init_it < 0)
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: need W >= 1, max_it >= 0, init_it >= 0", who);
+    if (const char *why = ring_deg_limit(p, W)) return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
+    if (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj16 || !d_cn_sock16 || !d_chan_bits)))
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
+    if (ntrials == 0) return SCLDPC_OK;
+    return ring_launch(who, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, W, max_it, init_it, d_counters, d_erased_bits, stream);
 }

@@ -200,6 +200,11 @@ def sw_ring_supported(p, W):
     return bool(lib().scldpc_sw_bp_ring_supported(C.byref(p), int(W)))
 
 
+def sw_ring_deg_supported(p, W):
+    """Whether scldpc_sw_bp_ring_device_deg takes the square window W on this ensemble: the pairs (3,6), (4,8) and (5,10)."""
+    return bool(lib().scldpc_sw_bp_ring_deg_supported(C.byref(p), int(W)))
+
+
 def sock16_supported(p):
     """The (4,8) chain with N <= 2048: the second-generation sampler emits the ring window decoder's CN -> socket table."""
     return bool(lib().scldpc_sample_philox_sock16_supported(C.byref(p)))
@@ -403,18 +408,23 @@ def cn_sockets(p, d_adj16, out=None):
     return out
 
 
-def sw_bp(p, d_adj, d_chan, W, max_it, init_it=0, want_erased=False, counters=None, classical=False, ring=None, d_cn_sock=None):
+def sw_bp(p, d_adj, d_chan, W, max_it, init_it=0, want_erased=False, counters=None, classical=False, ring=None, d_cn_sock=None,
+          deg=False):
     """decodeBP_SW for a batch resident on the device: square window (BPW:628-912) or, with classical=True, the
     classical window kept in BPF:627-897 (init_it unused).  ring: None = use the window-state-in-LDS kernel (sw_ring.hip)
     whenever it takes the ensemble (square window, 2-byte tables; the CN -> socket table is built on the fly unless
-    d_cn_sock is given), False = the whole-chain kernel, True = insist on the ring kernel."""
+    d_cn_sock is given), False = the whole-chain kernel, True = insist on the ring kernel.  deg=True: the ring decision and the
+    launch go through scldpc_sw_bp_ring_deg_supported / scldpc_sw_bp_ring_device_deg, which take the pairs (3,6) and (5,10) too."""
     _require_gpu()
     T = d_adj.shape[0]
     use_ring = ring
     if ring is None or ring:
-        ok = (not classical) and _is_adj16(d_adj) and bool(lib().scldpc_sw_bp_ring_supported(C.byref(p), int(W)))
+        supported = lib().scldpc_sw_bp_ring_deg_supported if deg else lib().scldpc_sw_bp_ring_supported
+        ok = (not classical) and _is_adj16(d_adj) and bool(supported(C.byref(p), int(W)))
         if ring and not ok:
-            raise ScldpcError("the ring window kernel takes the square window on 2-byte tables of the (4,8) chain only")
+            raise ScldpcError("the ring window kernel takes the square window on 2-byte tables of the (3,6), (4,8) and (5,10) "
+                              "chains only" if deg else
+                              "the ring window kernel takes the square window on 2-byte tables of the (4,8) chain only")
         use_ring = ok
     assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
     assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
@@ -427,8 +437,8 @@ def sw_bp(p, d_adj, d_chan, W, max_it, init_it=0, want_erased=False, counters=No
     if use_ring:
         if d_cn_sock is None:
             d_cn_sock = cn_sockets(p, d_adj)
-        check(lib().scldpc_sw_bp_ring_device(*head, d_cn_sock.data_ptr(), d_chan.data_ptr(), int(W), int(max_it), int(init_it),
-                                             *tail, _stream_ptr(dev)))
+        fn = lib().scldpc_sw_bp_ring_device_deg if deg else lib().scldpc_sw_bp_ring_device
+        check(fn(*head, d_cn_sock.data_ptr(), d_chan.data_ptr(), int(W), int(max_it), int(init_it), *tail, _stream_ptr(dev)))
         return {"counters": counters, "erased": erased}
     ws, wsb, _keep = _workspace(WS_SW_BP, p, T, dev, int(W))
     if classical:

@@ -303,6 +303,17 @@ int scldpc_cn_sockets_device(const scldpc_code_params *p, int32_t ntrials, const
 int scldpc_sw_bp_ring_device(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                              const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t W, int32_t max_it,
                              int32_t init_it, int32_t *d_counters, uint32_t *d_erased_bits, void *stream);
+/* The same decoder for the regular pairs (3,6), (4,8) and (5,10): sw_ring.hip's instance of the pair ((4,8): the one
+ * scldpc_sw_bp_ring_device runs, bit for bit its counters).  Arguments, counters and error codes of
+ * scldpc_sw_bp_ring_device_deg as scldpc_sw_bp_ring_device; d_vn_adj16 uint16 [ntrials][n][dv] (scldpc_sample_philox_device_adj16),
+ * d_cn_sock16 uint16 [ntrials][nk][dc] (scldpc_cn_sockets_device).  scldpc_sw_bp_ring_deg_supported: 1 if (p, W) is taken —
+ * one of the three pairs, W >= 1, cns_pos <= 65536, vns_pos * dv <= 65535, L + dv - 1 <= 65535 (a queue entry is
+ * CN position << 16 | CN) and a window state that fits the CU's 160 KiB; otherwise SCLDPC_ERR_TOO_LARGE names the limit.
+ * scldpc_sw_bp_ring_supported / scldpc_sw_bp_ring_device answer as before ((4,8) only). */
+int scldpc_sw_bp_ring_deg_supported(const scldpc_code_params *p, int32_t W);
+int scldpc_sw_bp_ring_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                 const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t W, int32_t max_it,
+                                 int32_t init_it, int32_t *d_counters, uint32_t *d_erased_bits, void *stream);
 
 /* decodeBP_SW, classical window — the variant kept in BPF:627-897 (its call is commented out at BPF:2137-2138):
  * L+dv-1 windows, VNs [posW-ms, posW+W), position posW-ms decided when window posW closes, max_it per window. */
