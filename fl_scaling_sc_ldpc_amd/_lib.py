@@ -50,6 +50,7 @@ EXPORTS = (
     "scldpc_full_bp_device_deg", "scldpc_full_bp_traj_device_deg", "scldpc_full_bp_device_deg_wide",
     "scldpc_full_bp_traj_device_deg_wide",
     "scldpc_sw_bp_ring_deg_supported", "scldpc_sw_bp_ring_device_deg",
+    "scldpc_stream_supported",
 )
 
 
@@ -150,6 +151,7 @@ def lib():
     L.scldpc_r1_moments_device.argtypes = [i32, i32, vp, vp, vp]
     L.scldpc_swc_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_swc_bp_device_adj16.argtypes = L.scldpc_swc_bp_device.argtypes
+    L.scldpc_stream_supported.argtypes = [pp, i32]
     L.scldpc_stream_state_bytes.argtypes = [pp, i32]
     L.scldpc_stream_state_bytes.restype = i64
     L.scldpc_stream_run_device.argtypes = [pp, i32, u64, u64, dbl, i32, i32, vp, i32, vp, vp, vp, vp]

@@ -36,6 +36,7 @@
 #include "common.h"
 #include "kernel_util.h"
 #include "philox.h"
+#include "table_rows.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -46,7 +47,7 @@ using namespace scldpc_dev;
 constexpr int kGenThreads = 1024, kDecThreads = 256, kMaxDoped = 32, kMaxL = 256;
 constexpr int kQCap = 512;                          // frontier-queue entries (an overflow falls back to a scan of the window's CNs)
 constexpr int kScratch = 2048;                       // GENERATE: keys of straddling buckets ordered at a time (beyond: the fallback ranking)
-constexpr int kFrozen = 8;                          // slots of the frozen-position rings in the blob (> 2dv - 1 - (dv - 1) positions)
+constexpr int kFrozen = 8;                          // slots of the frozen-position rings in the blob (a power of two >= dv, see stream_dec_body)
 enum { C_NE = 0, C_BE, C_EE, C_BEE, C_GB, C_GBL, C_GBE, C_GBLE, C_POS, C_GEN, C_NCOUNT = 16 };
 enum { S_PUSH = 0, S_OVF = 3, S_REM = 6, S_ACC = 9, S_WL = 10, S_BAD = 11, S_NSCAL = 16 };
 
@@ -79,6 +80,8 @@ struct Args {
     long long *counters_out;    // [nstreams][10]
     int32_t *trace;             // optional [nstreams][trace_stride][10]; this launch writes rows trace_off .. trace_off + npos - 1
     int trace_stride, trace_off;
+    int fz_rows_gone;           // DECODE: 1 = a buffer so short that the reference itself has re-used the CN rows of a position by the
+                                // time it expurgates it (see stream_run): no size-2 stopping set is ever found there
 };
 
 using scldpc_dev::philox4x32_10;
@@ -105,8 +108,15 @@ __device__ __forceinline__ bool position_is_doped(const Args &a, long long pos) 
 // LDS, FUSED (at most 8 Philox calls per thread, everything within a CU's LDS): [scan scratch | scalars | stage: S sockets of
 // 2 bytes | hist: a.nb / 2 words | the straddlers' worklist]; once the ranks are final, what follows the stage holds the
 // socket -> CN row (S entries of 2 bytes).  Otherwise [scan scratch | scalars | hist | fill counters of cn_rows] and the stage
-// lies over hist.  78 KB at N = 5000: two workgroups per CU (64 VGPRs, 72 SGPRs).
-template <bool FUSED>
+// lies over hist.  dv = 4: 78 KB at N = 5000, two workgroups per CU (64 VGPRs, 72 SGPRs); the dv = 3 and 5 instances run one
+// workgroup per CU (kGenWavesPerSimd below; 65 KB and 98 KB at N = 5000).
+// DV = the VN degree (a.dv), instances 3, 4 and 5.  At DV = 3 and 5 it is a compile-time constant everywhere: the socket -> CN
+// row's layout (a division by dv per socket) and the ring of dv rows cost multiplications and shifts.  The DV = 4 instance is
+// the body this kernel had when 4 was its only degree, expression for expression — dv read from the arguments, the wiring
+// loop with its generic branch — because that is the code C5 is measured with: its instructions are unchanged, and so are its
+// 64 VGPRs and 52 (fused) / 20 bytes of scratch, which any reshaping of these expressions moves (folding dv to 4 costs the fused
+// instance three more spilled registers).
+template <bool FUSED, int DV>
 __device__ __forceinline__ void stream_gen_body(const Args &a)
 {
     constexpr int kThreads = kGenThreads, kWaves = kThreads / 64;
@@ -119,7 +129,8 @@ __device__ __forceinline__ void stream_gen_body(const Args &a)
     uint32_t *aux = FUSED ? base : hist + a.nb / 2;                     // FUSED: the stage; else the fill counters
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int L = a.L, C = a.C, V = a.V, S = a.S, dv = a.dv, wpp = a.lay.wpp;
+    const int L = a.L, C = a.C, V = a.V, S = a.S, wpp = a.lay.wpp;
+    const int dv = DV == 4 ? a.dv : DV;
     char *st = a.state + (size_t)blockIdx.x * a.lay.total;
     // the blob's arrays, addressed from `st` where they are used: kept as seven pointers they would sit in scalar registers the
     // kernel does not have (72 per wave for two workgroups per CU) and end up in scratch memory
@@ -131,10 +142,14 @@ __device__ __forceinline__ void stream_gen_body(const Args &a)
     auto gkey_p = [&] { return reinterpret_cast<uint2 *>(blob(a.lay.gkey)); };           // [S] (key, socket) of straddling buckets' keys, by rank slot (rank_wide)
     auto wlist_p = [&] { return reinterpret_cast<uint2 *>(blob(a.lay.wlist)); };         // [S] the same keys as a dense list: (key, socket | first rank << 16)
     auto cnt64_p = [&] { return reinterpret_cast<long long *>(blob(a.lay.counters)); };
-    // a socket -> CN row is kept by edge: entry of socket s = dv*t + i at i * V + t, so that the wiring of a VN position reads
-    // V consecutive entries of each of its dv rows (a quarter of a row each) instead of every dv-th entry of whole rows
-    const uint32_t S4 = (uint32_t)(a.S >> 2);
-    auto tp = [&](uint32_t sck) { return (sck & 3u) * S4 + (sck >> 2); };
+    // a socket -> CN row is kept by edge: entry of socket s = dv*t + i at i * V + t (S = dv * V), so that the wiring of a VN
+    // position reads V consecutive entries of each of its dv rows (a dv-th of a row each) instead of every dv-th entry of whole
+    // rows; a bijection on [0, S) for every S, a multiple of four or not
+    const uint32_t Vu = DV == 4 ? (uint32_t)(a.S >> 2) : (uint32_t)a.V;     // V either way
+    auto tp = [&](uint32_t sck) {
+        if constexpr (DV == 4) return (sck & 3u) * Vu + (sck >> 2);
+        else return (sck % (uint32_t)DV) * Vu + sck / (uint32_t)DV;
+    };
     const unsigned long long sid = a.sid0 + blockIdx.x;
     const uint32_t s_lo = (uint32_t)sid, s_hi = (uint32_t)(sid >> 32);
 
@@ -517,14 +532,25 @@ __device__ __forceinline__ void stream_gen_body(const Args &a)
         STAMP(5);
         const uint16_t *inter = inter_p();
         uint16_t *vrows = adj_p() + (size_t)slot * V * dv;
-        for (int t = tid; t < V; t += kThreads) {                                // wiring (BPF:1841-1854)
-            if (dv == 4) {                                  // four independent loads, one 8-byte row store
-                uint32_t loc[4];
+        if constexpr (DV == 4) {
+            for (int t = tid; t < V; t += kThreads) {                            // wiring (BPF:1841-1854)
+                if (dv == 4) {                              // four independent loads, one 8-byte row store
+                    uint32_t loc[4];
 #pragma unroll
-                for (int i = 0; i < 4; i++) loc[i] = inter[(size_t)((g + i) & 3) * S + (size_t)i * S4 + t];
-                *reinterpret_cast<uint2 *>(vrows + (size_t)t * 4) = make_uint2(loc[0] | (loc[1] << 16), loc[2] | (loc[3] << 16));
-            } else {
-                for (int i = 0; i < dv; i++) vrows[(size_t)t * dv + i] = inter[(size_t)((g + i) % dv) * S + tp((uint32_t)(dv * t + i))];
+                    for (int i = 0; i < 4; i++) loc[i] = inter[(size_t)((g + i) & 3) * S + (size_t)i * Vu + t];
+                    *reinterpret_cast<uint2 *>(vrows + (size_t)t * 4) = make_uint2(loc[0] | (loc[1] << 16), loc[2] | (loc[3] << 16));
+                } else {                                    // (never taken: kept with the instance's code, see above)
+                    for (int i = 0; i < dv; i++) vrows[(size_t)t * dv + i] = inter[(size_t)((g + i) % dv) * S + tp((uint32_t)(dv * t + i))];
+                }
+            }
+        } else {
+            const int g0 = (int)(g % DV);
+            for (int t = tid; t < V; t += kThreads) {                            // dv independent loads; rows of 6 or 10 bytes are
+                uint32_t loc[DV];                                                // 2-byte aligned, no more, when V * dv is odd
+#pragma unroll
+                for (int i = 0; i < DV; i++) loc[i] = inter[(size_t)((g0 + i) % DV) * S + (size_t)i * Vu + t];
+#pragma unroll
+                for (int i = 0; i < DV; i++) vrows[(size_t)t * DV + i] = (uint16_t)loc[i];
             }
         }
         __syncthreads();
@@ -545,10 +571,15 @@ __device__ __forceinline__ void stream_gen_body(const Args &a)
     }
 }
 
-template <bool FUSED>
-__global__ __launch_bounds__(kGenThreads, 8) __attribute__((amdgpu_num_sgpr(80))) void stream_gen_kernel(const Args a)
+// Waves per SIMD the instance is compiled for: 8 (64 VGPRs, two workgroups per CU) at dv = 4.  At dv = 3 and 5 the body does not
+// fit 64 VGPRs (it spills 12 - 56 bytes per lane; the dv = 4 instances keep the 52 and 20 bytes they are measured with), and a
+// 1024-thread workgroup has no occupancy between 4 and 8 waves per SIMD: those instances get 4 — one workgroup per CU, no scratch.
+template <int DV> constexpr int kGenWavesPerSimd = DV == 4 ? 8 : 4;
+
+template <bool FUSED, int DV>
+__global__ __launch_bounds__(kGenThreads, kGenWavesPerSimd<DV>) __attribute__((amdgpu_num_sgpr(80))) void stream_gen_kernel(const Args a)
 {
-    stream_gen_body<FUSED>(a);
+    stream_gen_body<FUSED, DV>(a);
 }
 
 // ==================================================== DECODE =============================================================
@@ -559,9 +590,22 @@ __global__ __launch_bounds__(kGenThreads, 8) __attribute__((amdgpu_num_sgpr(80))
 // reach of the next window's VNs, so both leave the LDS at the end of the step for a small ring in the blob, where the
 // size-2 stopping-set test of position pos - 2dv + 1 reads them (only when that position still holds erasures).  That keeps
 // the LDS at W + 2dv - 2 CN positions and W + dv - 1 VN positions: 50 KB at N = 5000, W = 20 — three streams per CU.
+// The frozen rings: at step pos the expurgation reads the CN positions pe .. pe + DV - 1 (pe = pos - 2 DV + 1), the last of
+// them written at the end of step pos - 1, and the end of step pos writes position pos - DV + 1: DV + 1 positions at most
+// 2 DV - 2 < kFrozen apart, so no slot is written while it is still to be read.
+// A VN row (DV entries of 2 bytes, table_rows.h) is loaded no wider than its alignment allows: the rows of a position start at
+// slot * V * DV * 2 bytes, a multiple of 8 for DV = 4 only.
+template <int DV>
+__device__ __forceinline__ Row<DV> vn_row(const uint16_t *rows, int t)
+{
+    if constexpr (DV == 4) return load_row(reinterpret_cast<const uint2 *>(rows), t);
+    else return load_row<DV>(rows, t);
+}
+
 template <int DV>
 __device__ __forceinline__ void stream_dec_body(const Args &a)
 {
+    static_assert(DV <= kFrozen && (kFrozen & (kFrozen - 1)) == 0, "the frozen rings hold the dv positions the expurgation reads");
     constexpr int kThreads = kDecThreads;
     extern __shared__ uint32_t lds[];
     const int L = a.L, C = a.C, V = a.V, W = a.W, wpp = a.lay.wpp, Cw = a.lay.Cw, R = a.lay.R, RV = a.lay.RV, dc = a.dc;
@@ -638,23 +682,25 @@ __device__ __forceinline__ void stream_dec_body(const Args &a)
         if (tid == 0) pos_cnt[ls] = 0;
         __syncthreads();
         if (lane == 0 && mine) atomicAdd(&pos_cnt[ls], mine);
-        // rows are loaded unconditionally, four per thread in flight (coalesced 8-byte loads), then the erased ones count
-        const uint2 *vrow = reinterpret_cast<const uint2 *>(adj) + (size_t)ls * V;
+        // rows are loaded unconditionally, four per thread in flight (coalesced 8-byte loads at dv = 4), then the erased ones count
+        const uint16_t *vrow = adj + (size_t)ls * V * DV;
         for (int t0 = tid; t0 < V; t0 += 4 * kThreads) {
-            uint2 r[4];
+            Row<DV> r[4];
             bool er[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int t = t0 + u * kThreads;
                 er[u] = false;
-                if (t < V) { r[u] = vrow[t]; er[u] = (Sr[sb + (t >> 5)] >> (t & 31)) & 1u; }
+                if (t < V) { r[u] = vn_row<DV>(vrow, t); er[u] = (Sr[sb + (t >> 5)] >> (t & 31)) & 1u; }
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 if (!er[u]) continue;
-                const uint32_t l[4] = {r[u].x & 0xFFFFu, r[u].x >> 16, r[u].y & 0xFFFFu, r[u].y >> 16};
 #pragma unroll
-                for (int i = 0; i < DV; i++) atomicAdd(&cnt[cslot(d + i) + (l[i] >> 3)], 1u << ((l[i] & 7) * 4));
+                for (int i = 0; i < DV; i++) {
+                    const uint32_t l = r[u][i];
+                    atomicAdd(&cnt[cslot(d + i) + (l >> 3)], 1u << ((l & 7) * 4));
+                }
             }
         }
         __syncthreads();
@@ -714,7 +760,7 @@ __device__ __forceinline__ void stream_dec_body(const Args &a)
             // to memory: the CN's sockets, then the VN's row (issued before the claim of its S bit); every atomic is in LDS.
             // out[i] = 1 + [CN position offset + 2dv | CN] of edge i if this release left that CN with one erased neighbour
             // inside the CN window.
-            auto release = [&](int d, int l, uint32_t (&out)[4]) {
+            auto release = [&](int d, int l, uint32_t (&out)[DV]) {
                 const uint16_t *row = cnsock + ((size_t)lslot(d) * C + l) * dc;
                 uint32_t sk[8];
                 if (dc == 8) {
@@ -734,12 +780,13 @@ __device__ __forceinline__ void stream_dec_body(const Args &a)
                     }
                 }
                 if (jd == (1 << 20) || jd < -ms) return;                 // none left (released this round) or frozen (BPF:1285-1310)
-                const uint2 r = reinterpret_cast<const uint2 *>(adj)[(size_t)lslot(jd) * V + jt];
+                const Row<DV> r = vn_row<DV>(adj + (size_t)lslot(jd) * V * DV, jt);
                 const uint32_t bit = 1u << (jt & 31);
                 if (!(atomicAnd(&Sr[sslot(jd) + (jt >> 5)], ~bit) & bit)) return;
                 atomicSub(&pos_cnt[lslot(jd)], 1);
-                const uint32_t ll[4] = {r.x & 0xFFFFu, r.x >> 16, r.y & 0xFFFFu, r.y >> 16};
-                uint32_t o[4];
+                uint32_t ll[DV], o[DV];
+#pragma unroll
+                for (int i = 0; i < DV; i++) ll[i] = r[i];
 #pragma unroll
                 for (int i = 0; i < DV; i++)                             // the dv returning atomics go out back to back
                     o[i] = atomicSub(&cnt[cslot(jd + i) + (ll[i] >> 3)], 1u << ((ll[i] & 7) * 4));
@@ -749,8 +796,10 @@ __device__ __forceinline__ void stream_dec_body(const Args &a)
                         out[i] = 1u + (((uint32_t)(jd + i + 2 * DV) << 16) | ll[i]);
             };
             // a wave appends its lanes' entries behind *push_cnt: one prefix scan + one LDS atomic per wave
-            auto append = [&](const uint32_t (&out)[4]) {
-                const int mine = (out[0] != 0u) + (out[1] != 0u) + (out[2] != 0u) + (out[3] != 0u);
+            auto append = [&](const uint32_t (&out)[DV]) {
+                int mine = 0;
+#pragma unroll
+                for (int i = 0; i < DV; i++) mine += out[i] != 0u;
                 const int incl = (int)wave_inclusive_scan((uint32_t)mine);
                 const int tot = __builtin_amdgcn_readlane(incl, 63);
                 if (tot == 0) return;
@@ -758,7 +807,7 @@ __device__ __forceinline__ void stream_dec_body(const Args &a)
                 if (lane == 0) base = atomicAdd(push_cnt, tot);
                 int idx = __builtin_amdgcn_readfirstlane(base) + incl - mine;
 #pragma unroll
-                for (int i = 0; i < 4; i++)
+                for (int i = 0; i < DV; i++)
                     if (out[i]) { if (idx < kQCap) qn[idx] = out[i] - 1u; else *push_ovf = 1; idx++; }
             };
             if (rescan) {
@@ -775,7 +824,7 @@ __device__ __forceinline__ void stream_dec_body(const Args &a)
                             if (w * 8 + 8 > C) z &= (1u << (4 * (C - w * 8))) - 1u;
                         }
                         while (__any(z != 0u)) {
-                            uint32_t out[4] = {0, 0, 0, 0};
+                            uint32_t out[DV] = {};
                             if (z) {
                                 const int k = (__ffs((int)z) - 1) >> 2;
                                 z &= z - 1;
@@ -787,7 +836,7 @@ __device__ __forceinline__ void stream_dec_body(const Args &a)
                 }
             } else {
                 for (int k0 = (tid >> 6) * 64; k0 < ncur; k0 += kThreads) {
-                    uint32_t out[4] = {0, 0, 0, 0};
+                    uint32_t out[DV] = {};
                     if (k0 + lane < ncur) release((int)(qc[k0 + lane] >> 16) - 2 * DV, (int)(qc[k0 + lane] & 0xFFFFu), out);
                     append(out);
                 }
@@ -811,12 +860,15 @@ __device__ __forceinline__ void stream_dec_body(const Args &a)
             if (pos_cnt[ls] > 0) {
                 for (int w = tid; w < wpp; w += kThreads) {
                     uint32_t x = fs[w];
+                    if (a.fz_rows_gone) { mine += __popc(x); x = 0; }
                     while (x) {
                         const int b = __ffs((int)x) - 1;
                         x &= x - 1;
                         const int t = w * 32 + b;
-                        const uint2 r = reinterpret_cast<const uint2 *>(adj)[(size_t)ls * V + t];
-                        const uint32_t l[4] = {r.x & 0xFFFFu, r.x >> 16, r.y & 0xFFFFu, r.y >> 16};
+                        const Row<DV> r = vn_row<DV>(adj + (size_t)ls * V * DV, t);
+                        uint32_t l[DV];
+#pragma unroll
+                        for (int i = 0; i < DV; i++) l[i] = r[i];
                         bool pair = true;
 #pragma unroll
                         for (int i = 0; i < DV; i++)
@@ -919,17 +971,22 @@ size_t dec_lds_bytes(const StateLayout &lay)
     return 4u * ((size_t)16 + (size_t)lay.R * lay.Cw + (size_t)lay.RV * lay.wpp + 2 * kQCap + lay.Lp + S_NSCAL);
 }
 
+// The one rule of what the streaming kernels take: scldpc_stream_supported and every entry point answer through it.
 int check_stream(const scldpc_code_params *p, int W, const char *who)
 {
     if (int rc = scldpc::check_params(p)) return rc;
+    if (p->dv < 3 || p->dv > 5)
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: the streaming kernels take dv = 3, 4 or 5 (dv=%d)", who, p->dv);
+    if (p->dc > 15)
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: dc must be at most 15, a CN's count is a nibble (dc=%d)", who, p->dc);
+    if ((int64_t)p->cns_pos * p->dc > 65536)
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: at most 65536 sockets per position (cns_pos * dc = %lld)", who,
+                                 (long long)p->cns_pos * p->dc);
     if (p->L > kMaxL || p->L < 2 * p->dv)
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: buffer length L=%d outside [%d, %d]", who, p->L, 2 * p->dv, kMaxL);
     // the stream is generated L/2 positions ahead (BPF:2001): the window and the CNs of its VNs must exist already
     if (W < 1 || W + p->dv - 1 > p->L / 2)
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: need 1 <= W and W + dv - 1 <= L/2 (W=%d, L=%d)", who, W, p->L);
-    if (p->dv != 4 || (int64_t)p->cns_pos * p->dc > 65536 || p->dc > 15)
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: the streaming kernels take dv = 4, dc <= 15 and at most 65536 "
-                                 "sockets per position", who);
     StateLayout lay;
     make_state_layout(p, W, &lay);
     if (dec_lds_bytes(lay) > (size_t)scldpc::kMaxLdsBytes)
@@ -938,6 +995,11 @@ int check_stream(const scldpc_code_params *p, int W, const char *who)
 }
 
 }  // namespace
+
+extern "C" int scldpc_stream_supported(const scldpc_code_params *p, int32_t W)
+{
+    return check_stream(p, W, "scldpc_stream_supported") == SCLDPC_OK ? 1 : 0;
+}
 
 extern "C" int64_t scldpc_stream_state_bytes(const scldpc_code_params *p, int32_t W)
 {
@@ -998,16 +1060,27 @@ static int stream_run(const scldpc_code_params *p, int32_t nstreams, uint64_t se
     if (const char *v = getenv("SCLDPC_DEBUG_STREAM_WIDE")) a.force_wide = atoi(v);         // diagnostics / tests only
     if (lds_gen > (size_t)scldpc::kMaxLdsBytes)
         return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_stream_run_device: %zu bytes of LDS per stream", lds_gen);
-    void (*gen_kern)(const Args) = fused ? stream_gen_kernel<true> : stream_gen_kernel<false>;
-    void (*dec_kern)(const Args) = stream_dec_kernel<4>;
+    void (*gen_kern)(const Args) = nullptr, (*dec_kern)(const Args) = nullptr;
+    switch (p->dv) {                                    // (check_stream: 3, 4 or 5)
+    case 3: gen_kern = fused ? stream_gen_kernel<true, 3> : stream_gen_kernel<false, 3>; dec_kern = stream_dec_kernel<3>; break;
+    case 4: gen_kern = fused ? stream_gen_kernel<true, 4> : stream_gen_kernel<false, 4>; dec_kern = stream_dec_kernel<4>; break;
+    default: gen_kern = fused ? stream_gen_kernel<true, 5> : stream_gen_kernel<false, 5>; dec_kern = stream_dec_kernel<5>; break;
+    }
     if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(gen_kern))) return rc_;
     if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(dec_kern))) return rc_;
     // Cycles of GENERATE (run `ahead` positions beyond the reference's lag of L/2) and DECODE (as many positions as are
     // then generated far enough: decodeBP_SW_circular(pos) needs positions up to pos + W + dv - 2).  `ahead` is bounded by the
     // buffer: generating position g re-uses the slots of VN position g - L and CN position g + dv - 1 - L, and the decoder
     // still reads CN position pos - 2dv + 1 (expurgation): ahead <= ceil(L/2) - 3dv + 2.  The call ends as main_streaming
-    // leaves a stream: generated = decoded + L/2.
+    // leaves a stream: generated = decoded + L/2.  With ahead = 0 a launch generates no further than main_streaming has by its
+    // first position and decodes c >= 1 positions (W + dv - 1 <= L/2): what the window itself reads — VN positions from
+    // pos - dv + 1, CN positions from pos — is never re-used that early (L/2 + dv - 2 < L).
+    // A buffer shorter than that bound (ceil(L/2) < 3dv - 2; L = 20 at dv = 5) is one in which the reference has re-used the
+    // slot of CN position pos - 2dv + 1 when it expurgates VN position pos - 2dv + 1 (it has generated CN positions up to
+    // pos + L/2 + dv - 2): get_deg_two_ss then finds no VN pair behind edge 0 and counts every erased VN (BPF:1227-1283).
+    // The decoder does the same (fz_rows_gone) without reading the rows, whose re-use a launch of c > 1 positions lags behind.
     const int half = p->L / 2, ahead_max = std::max(0, (p->L - half) - 3 * p->dv + 2);
+    a.fz_rows_gone = (p->L - half) - 3 * p->dv + 2 < 0;
     const hipStream_t hs = static_cast<hipStream_t>(stream);
     a.trace_stride = npos;
     for (int done = 0; done < npos;) {

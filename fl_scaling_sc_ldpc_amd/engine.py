@@ -550,6 +550,13 @@ STREAM_COUNTERS = ("num_erasures", "num_blocks_err", "num_erasures_exp", "num_bl
                    "num_blocks_generated", "num_bits_generated_exp", "num_blocks_generated_exp", "positions", "generated")
 
 
+def stream_supported(p, W):
+    """True if the streaming kernels take ensemble p with window W (scldpc_stream_supported: dv = 3, 4 or 5, dc <= 15, at most
+    65 536 sockets per position, 2 dv <= L <= 256, W + dv - 1 <= L/2, the window's state within the LDS); on False
+    lib().scldpc_last_error() names the limit.  Streams, InputStreams and GlibcStreamRun raise on such an ensemble."""
+    return bool(lib().scldpc_stream_supported(C.byref(p), int(W)))
+
+
 class Streams:
     """nstreams independent doped SC-LDPC streams on the device, each a circular buffer of p.L positions."""
 

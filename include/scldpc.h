@@ -407,7 +407,19 @@ int scldpc_r1_moments_device(int32_t ntrials, int32_t ncols, const int32_t *d_r1
  * draw does), and rather than rank wrongly both kernels leave such a stream untouched from then on — callers check the
  * column when they read the counters (bp_decoding.run_streaming does).  d_trace (optional) int32
  * [nstreams][npos][10]: position, value returned by decodeBP_SW_circular, then the eight counters after it.
- * Requires W + dv - 1 <= L/2 (the stream is generated L/2 positions ahead of the decoder, BPF:2001). */
+ * Requires W + dv - 1 <= L/2 (the stream is generated L/2 positions ahead of the decoder, BPF:2001).
+ * What the kernels take: dv = 3, 4 or 5 (one instance of each kernel per degree), any dc <= 15 (dc = 2 dv or not), at most
+ * 65 536 sockets (cns_pos * dc) per position, 2 dv <= L <= 256, 1 <= W with W + dv - 1 <= L/2, and a window whose state
+ * (4-bit counts of W + 2dv - 2 CN positions, S bits of W + dv - 1 VN positions, two queues) fits one CU's LDS.
+ * scldpc_stream_supported(p, W) is that rule: 1 if the streaming entry points take (p, W), else 0 with scldpc_last_error
+ * naming the limit that refused.  scldpc_stream_state_bytes and every scldpc_stream_run_device* entry point decide
+ * through the same function (they return the error code and the same message under their own name).  The blob of a
+ * dv = 4 stream is laid out as it always was: a saved state continues.
+ * Short buffers: with ceil(L/2) < 3dv - 2 the reference expurgates a position after it has re-used the slot of its first CN
+ * position and finds no size-2 stopping set; the kernels count the same (num_erasures_exp = every erased VN).  With
+ * L <= 4dv - 4 (windows narrower than dv) the reference reads re-used VN rows as well, the kernels do not: the counters are
+ * NOT the reference's there, although scldpc_stream_supported answers 1. */
+int scldpc_stream_supported(const scldpc_code_params *p, int32_t W);
 int64_t scldpc_stream_state_bytes(const scldpc_code_params *p, int32_t W);
 int scldpc_stream_run_device(const scldpc_code_params *p, int32_t nstreams, uint64_t seed, uint64_t stream0,
                              double eps, int32_t W, int32_t ndoped, const int32_t *doped_positions,
