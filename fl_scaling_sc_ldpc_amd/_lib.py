@@ -49,6 +49,7 @@ EXPORTS = (
     "scldpc_full_bp_deg_supported", "scldpc_full_bp_deg_wide_supported", "scldpc_full_bp_fixpoint_device_deg",
     "scldpc_full_bp_device_deg", "scldpc_full_bp_traj_device_deg", "scldpc_full_bp_device_deg_wide",
     "scldpc_full_bp_traj_device_deg_wide",
+    "scldpc_full_bp_caps_device_wide", "scldpc_full_bp_caps_device_deg", "scldpc_full_bp_caps_device_deg_wide",
     "scldpc_sw_bp_ring_deg_supported", "scldpc_sw_bp_ring_device_deg",
     "scldpc_stream_supported",
 )
@@ -139,6 +140,9 @@ def lib():
     L.scldpc_full_bp_device_deg_wide.argtypes = L.scldpc_full_bp_device_cn16.argtypes
     L.scldpc_full_bp_traj_device_deg.argtypes = L.scldpc_full_bp_traj_device_cn16.argtypes
     L.scldpc_full_bp_traj_device_deg_wide.argtypes = L.scldpc_full_bp_traj_device_cn16.argtypes
+    L.scldpc_full_bp_caps_device_wide.argtypes = L.scldpc_full_bp_caps_device_cn16.argtypes
+    L.scldpc_full_bp_caps_device_deg.argtypes = L.scldpc_full_bp_caps_device_cn16.argtypes
+    L.scldpc_full_bp_caps_device_deg_wide.argtypes = L.scldpc_full_bp_caps_device_cn16.argtypes
     L.scldpc_full_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, u64, vp]
     L.scldpc_sw_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_sample_philox_device_adj16.argtypes = L.scldpc_sample_philox_device.argtypes

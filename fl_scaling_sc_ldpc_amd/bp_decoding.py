@@ -31,7 +31,8 @@ Two sampling modes:
 `bp_lim_iter … --caps 175,200,250` writes the files of several MAX_IT from one run: one file per cap, each the file that
 `bp_lim_iter` with that MAX_IT writes.  Where that is exact and the level-synchronous decoder takes the ensemble (Philox
 sampling, NUM_DOPED = 0) the frames are sampled and decoded once, with a checkpoint at every cap
-(engine.full_bp_caps_cn16); otherwise the caps run one after another.
+(engine.full_bp_caps_cn16); otherwise the caps run one after another.  `--caps-fused on` extends the one decode to trials of
+more than 65536 CNs (engine.full_bp_caps_wide) and to the pairs (3,6) and (5,10) (engine.full_bp_caps_deg).
 
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
@@ -146,6 +147,11 @@ DEG_BY_DEFAULT = False
 # tools/ring_deg_speedup.py, with identical counters (profiles/ring_deg_speedup.json)
 RING_DEG_BY_DEFAULT = False
 
+# Whether Simulator(fused_caps=None) and `bp_lim_iter --caps` take the cap checkpoints of the wide form and of the pairs (3,6) and
+# (5,10) where they apply, instead of one single-cap pass per cap (tools/caps_forms_speedup.py, profiles/caps_forms_speedup.json).
+# The (4,8) forms of at most 65536 CNs fuse without this switch.
+CAPS_FORMS_BY_DEFAULT = False
+
 
 # The path of a Simulator, decided once in Simulator._select:
 #   adj_dtype    VN -> CN table: torch.int16 (position-local ids) or torch.int32 (the reference's VNdegree)
@@ -171,7 +177,7 @@ class Simulator:
 
     def __init__(self, p, decoder="full", W=0, max_it=0, init_it=0, is_term=True, doped=(), batch=2048,
                  rng="philox", seed=1, device=None, rows_cap=0, schedule="flooding", shard_frames=True, index=0,
-                 verbose=False, caps=None, wide=None, deg=None, ring=None):
+                 verbose=False, caps=None, wide=None, deg=None, ring=None, fused_caps=None):
         # wide: the 1024-thread 4-bit level decoder for trials of more than 65536 CNs (full_bp_small wide).  None = where
         # WIDE_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path, for A/B and tests)
         self.want_wide = wide
@@ -181,6 +187,9 @@ class Simulator:
         # ring: the ring window decoder (sw_ring) for dv, dc other than (4,8), decoder="sw" only.  None = where RING_DEG_BY_DEFAULT
         # says, True = wherever it applies, False = never (the whole-chain kernel)
         self.want_ring = ring
+        # fused_caps: with caps, the cap checkpoints of the wide form and of the pairs (3,6) and (5,10).  None = where
+        # CAPS_FORMS_BY_DEFAULT says, True = wherever an instance applies (wide=False / deg=False veto their family), False = never
+        self.want_fused_caps = fused_caps
         self.p, self.decoder, self.W, self.max_it, self.init_it = p, decoder, W, max_it, init_it
         # caps: several MaxNumIt from one decode (run_point_caps; the level-synchronous 4-bit decoder only)
         self.caps = E.check_caps(caps) if caps is not None else None
@@ -238,6 +247,16 @@ class Simulator:
                 self.path = Path(adj_dtype, sampler, table, False, "full_bp", "fixpoint16")
             else:
                 self.path = Path(adj_dtype, sampler, table, False, "level16", None)
+        elif self._caps_form(adj_dtype) is not None:
+            # cap checkpoints beyond the (4,8) forms of at most 65536 CNs (opt-in): the path a single-cap run of the family takes —
+            # the wide form on the CN -> socket table, sampled with the code where the second-generation sampler takes the
+            # ensemble; for the other pairs the first-generation sampler and the cn_sockets pass
+            form = self._caps_form(adj_dtype)
+            if form == "wide":
+                sampled = E.sock16_supported(p)
+                self.path = Path(adj_dtype, "sock16" if sampled else first, "sock", not sampled, "wide", None)
+            else:
+                self.path = Path(adj_dtype, first, "sock", True, form, None)
         elif self._deg_form(adj_dtype, unlimited_fix) is not None:
             # another degree pair the 4-bit decoder has instances for: the first-generation sampler writes the 2-byte VN -> CN
             # table for every dv, the cn_sockets pass the CN -> socket table; doped positions come with the channel.  Unlimited,
@@ -265,10 +284,20 @@ class Simulator:
         self.ring_deg = path.decoder == "sw_ring" and path.cn_pass
         self.wide_sock = self.wide and not path.cn_pass
         self.deg = path.decoder in ("deg16", "degwide")
-        if self.caps is not None and not (self.lvl2 and self.rows_cap == 0 and not self.doped):
+        fused_form = self.caps is not None and path.decoder in ("wide", "deg16", "degwide")      # reached through _caps_form only
+        if self.caps is not None and not ((self.lvl2 or fused_form) and self.rows_cap == 0 and not self.doped):
             raise ValueError("caps: the fused decode takes Philox sampling, no doping and an ensemble of the "
                              "level-synchronous 4-bit decoder (caps_sequential_reason)")
         return adj_dtype
+
+    def _caps_form(self, adj_dtype):
+        """"wide" / "deg16" / "degwide" where this configuration takes the cap checkpoints of those forms, else None."""
+        if self.caps is None or self.decoder != "full" or adj_dtype != torch.int16 or self.rows_cap != 0:
+            return None
+        if caps_sequential_reason(self.p, self.rng, len(self.doped), self.schedule, self.want_fused_caps, self.want_wide,
+                                  self.want_deg) is not None:
+            return None
+        return _caps_form(self.p, self.want_wide, self.want_deg)[0]
 
     def _deg_form(self, adj_dtype, unlimited_fix):
         """"deg16" / "degwide" where the _deg forms of the 4-bit decoder apply to this configuration, else None."""
@@ -317,10 +346,17 @@ class Simulator:
             return samp + " + full_bp_small level-synchronous with %d cap checkpoints per decode (4-bit CN counts)" % len(self.caps)
         if path.decoder == "level16":
             return samp + " + full_bp_small level-synchronous (4-bit CN counts" + rows
+        if path.decoder == "wide" and self.caps is not None:
+            return samp + (" + full_bp_small wide level-synchronous with %d cap checkpoints per decode (4-bit CN counts, "
+                           "32-bit queue entries)" % len(self.caps))
         if path.decoder == "wide":
             return samp + " + full_bp_small wide level-synchronous (4-bit CN counts, 32-bit queue entries" + rows
         if self.deg:
             pair = "4-bit CN counts, dv = %d, dc = %d" % (self.p.dv, self.p.dc)
+            if self.caps is not None:
+                return samp + (" + full_bp_small %slevel-synchronous with %d cap checkpoints per decode (%s%s)"
+                               % ("wide " if path.decoder == "degwide" else "", len(self.caps), pair,
+                                  ", 32-bit queue entries" if path.decoder == "degwide" else ""))
             if path.fix_decoder == "fixpoint_deg" and not self.rows_cap:
                 return samp + " + full_bp_small fixpoint (" + pair + ")"
             if path.decoder == "degwide":
@@ -366,6 +402,13 @@ class Simulator:
     def decode_batch_caps(self, nb):
         """The counters [K, nb, 8] of every cap of self.caps for the batch in place (one decode)."""
         cnt = self.d_cnt_caps[:len(self.caps) * nb * NCOUNTERS].view(len(self.caps), nb, NCOUNTERS)
+        decoder = self.path.decoder
+        if decoder == "wide":
+            return E.full_bp_caps_wide(self.p, self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb], self.caps, is_term=self.is_term,
+                                       counters=cnt)
+        if decoder in ("deg16", "degwide"):
+            return E.full_bp_caps_deg(self.p, self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb], self.caps, is_term=self.is_term,
+                                      counters=cnt, wide=decoder == "degwide")
         return E.full_bp_caps_cn16(self.p, self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb], self.caps, is_term=self.is_term,
                                    counters=cnt, sockets=self.path.cn_table == "sock")
 
@@ -524,9 +567,37 @@ def ring_deg_reason(p, W, rng, want=True):
     return None
 
 
-def caps_sequential_reason(p, rng, num_doped, schedule):
+def _caps_form(p, wide=None, deg=None):
+    """The cap-checkpoint form beyond the (4,8) forms of at most 65536 CNs that takes ensemble p — ("wide" | "deg16" |
+    "degwide", None) — or (None, the limit that keeps it off).  wide, deg: the Simulator's arguments; False vetoes the family.
+    A caps form takes exactly the shapes of its family's level form, so the library's *_supported rules decide."""
+    if (p.dv, p.dc) == (4, 8):
+        if wide is False:
+            return None, "--wide off: more than 65536 CNs per trial take the wide form of the level-synchronous 4-bit decoder"
+        if not E.full_bp_wide_supported(p):
+            return None, ("the wide form of the level-synchronous 4-bit decoder takes a state that leaves 1024 queue entries per "
+                          "queue in one CU's LDS, and vns_pos * dv <= 65535 (L = %d, N = %d)" % (p.L, p.vns_pos))
+        return "wide", None
+    if (p.dv, p.dc) not in ((3, 6), (5, 10)):
+        return None, "the level-synchronous 4-bit decoder takes the pairs (3,6), (4,8) and (5,10) (dv = %d, dc = %d)" % (p.dv, p.dc)
+    if deg is False:
+        return None, "--deg off: dv = %d, dc = %d takes the _deg forms of the level-synchronous 4-bit decoder" % (p.dv, p.dc)
+    if p.cns_pos > 65536:
+        return None, "more than 65536 CNs per position: no 2-byte VN -> CN table"
+    if E.full_bp_deg_supported(p):
+        return "deg16", None
+    if E.full_bp_deg_supported(p, wide=True):
+        return "degwide", None
+    return None, ("the _deg forms of the level-synchronous 4-bit decoder take at most 65536 CNs per trial, or a state that leaves "
+                  "1024 queue entries per queue in one CU's LDS, and vns_pos * dv <= 65535 (dv = %d, dc = %d, L = %d, N = %d)"
+                  % (p.dv, p.dc, p.L, p.vns_pos))
+
+
+def caps_sequential_reason(p, rng, num_doped, schedule, fused=None, wide=None, deg=None):
     """Why `bp_lim_iter --caps` runs its caps one after another instead of from one decode, or None.  The fused decode is
-    used only where each cap's file is exactly the single-cap file and the level-synchronous 4-bit decoder takes the ensemble."""
+    used only where each cap's file is exactly the single-cap file and the level-synchronous 4-bit decoder takes the ensemble.
+    fused, wide, deg: the Simulator's fused_caps, wide and deg (None: CAPS_FORMS_BY_DEFAULT; no veto) — with the fused path on,
+    the wide form and the pairs (3,6) and (5,10) fuse as well (_caps_form)."""
     if rng != "philox":
         return "--rng %s: each cap's run replays srandom(seed) from the start and stops drawing at its own frame" % rng
     if num_doped > 0:
@@ -534,6 +605,8 @@ def caps_sequential_reason(p, rng, num_doped, schedule):
     if schedule != "flooding":
         return "--schedule %s has no iteration caps" % schedule
     if _cn16_table(p) is None:
+        if CAPS_FORMS_BY_DEFAULT if fused is None else bool(fused):
+            return _caps_form(p, wide, deg)[1]
         if E.full_bp_wide_supported(p):
             return ("more than 65536 CNs per trial: the wide form of the level-synchronous 4-bit decoder has no cap "
                     "checkpoints")
@@ -560,8 +633,12 @@ def _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, sh
     writes — from one decode per batch with a checkpoint at every cap where that is exact, else one run per cap."""
     dist, rank, world = _dist()
     file_its = sorted(set(opts.caps) | {max_it})                  # the MAX_IT of each file
-    reason = caps_sequential_reason(p, opts.rng, num_doped, getattr(opts, "schedule", "flooding"))
+    switch = {"auto": None, "on": True, "off": False}
+    fused, wide, deg = (switch[getattr(opts, name, "auto")] for name in ("caps_fused", "wide", "deg"))
+    reason = caps_sequential_reason(p, opts.rng, num_doped, getattr(opts, "schedule", "flooding"), fused, wide, deg)
     verbose = rank == 0 and not opts.quiet
+    if reason is not None and fused:
+        raise SystemExit("--caps-fused on: " + reason)
     if reason is not None:
         if verbose:
             print("[scldpc] kernels: --caps runs %d single-cap passes one after another (%s)" % (len(file_its), reason),
@@ -585,7 +662,8 @@ def _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, sh
     slot = {v: caps.index(max(1, v)) for v in file_its}
     sim_obj = Simulator(p, decoder="full", W=W, max_it=caps[-1], is_term=True, doped=doped, batch=opts.batch, rng=opts.rng,
                         seed=opts.seed, schedule="flooding", shard_frames=shard == "frames",
-                        device=getattr(opts, "device", None), index=index, verbose=verbose, caps=caps)
+                        device=getattr(opts, "device", None), index=index, verbose=verbose, caps=caps, wide=wide, deg=deg,
+                        fused_caps=fused)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     paths = {v: os.path.join(outdir, result_filename(prog, p, W, v, 0, index)) for v in file_its}
@@ -832,6 +910,10 @@ def _parser(prog):
         ap.add_argument("--caps", type=_caps_list, default=None, metavar="K1,K2,…",
                         help="also write the files of these MAX_IT (one file per cap, each the file of a run with that "
                              "MAX_IT); from one decode per frame where that is exact, else one run per cap")
+        ap.add_argument("--caps-fused", choices=("auto", "on", "off"), default="auto",
+                        help="--caps with more than 65536 CNs per trial (e.g. --N 5000) or --dv/--dc 3/6 or 5/10: one decode "
+                             "with a checkpoint at every cap (on), one run per cap (off), or the measured default (auto); same "
+                             "files.  'on' where the one decode cannot apply is an error that names the limit")
     ap.add_argument("--wide", choices=("auto", "on", "off"), default="auto",
                     help="full BP of trials with more than 65536 CNs (e.g. the default N = 5000): the wide 4-bit level "
                          "decoder (on), the first-generation decoder (off), or the measured default (auto); same files")

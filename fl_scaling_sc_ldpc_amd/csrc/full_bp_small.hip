@@ -24,7 +24,8 @@
 // WIDE is the LEVEL machine (with or without the trajectory rows) for trials of more than 65536 CNs — bp_traj's shipped N = 5000,
 // L = 50 has 132 500: queue entries are 32-bit CN ids, one 1024-thread workgroup takes a CU and all of its 160 KiB, and the CN ->
 // socket table comes from scldpc_cn_sockets_device where the second-generation sampler stops (8192 sockets per position).
-// Socket table only; the fixpoint form (its private-queue carve assumes four waves), PERSIST and CAPS have no wide form.
+// Socket table only; CAPS has a wide form (the checkpoints sit inside the LEVEL loop), the fixpoint form (its private-queue carve
+// assumes four waves) and PERSIST have none.
 //
 // Outputs: the counters of scldpc_full_bp_fixpoint_device (everything decodeBP reports except the iteration count), or
 // with LEVEL all of scldpc_full_bp_device's counters.
@@ -74,20 +75,21 @@ struct SmArgs {
 // the loop (BPF:1065): where a single-cap decode tests it, the decoder takes a checkpoint instead — the counters that decode
 // would report, written to that cap's block of counters [ncaps][ntrials][8] — and goes on to the next cap.  Caps the decode
 // does not reach (a stop test or a broken invariant ended it first) get its final state.
-// WIDE (LEVEL or LEVEL + TRAJ with SOCK, nothing else): queue entries are 32-bit CN ids and ONE 1024-thread workgroup owns
+// WIDE (LEVEL, LEVEL + TRAJ or LEVEL + CAPS with SOCK, nothing else): queue entries are 32-bit CN ids and ONE 1024-thread workgroup owns
 // the CU and all of its LDS (four waves per SIMD, at most 128 VGPRs) — trials of more than 65536 CNs, e.g. bp_traj's default
-// N = 5000, L = 50 (nk = 132 500).  There is no wide fixpoint form (the private-queue carve below assumes four waves), no wide
-// PERSIST and no wide CAPS form.
+// N = 5000, L = 50 (nk = 132 500).  There is no wide fixpoint form (the private-queue carve below assumes four waves) and no wide
+// PERSIST.  A checkpoint of the wide CAPS form is the narrow one's: residual() strides by BLOCK and never touches the queues.
 // DV, DC: the degree pair, fixed at compile time (the rows of both tables are unrolled).  A VN row is DV uint16 and only 2-byte
 // aligned unless DV = 4 (one 8-byte load); a CN row is DC uint16, DC even, so 4-byte aligned (DC = 8: one 16-byte load).  Pairs
-// other than (4,8) have the socket-table forms without PERSIST and CAPS only (kernel_of).
+// other than (4,8) have the socket-table forms without PERSIST only (kernel_of).
 // OCC: waves per SIMD the registers are bounded for where an instance cannot hold its form's (0: the form's).
 template <int BLOCK, bool LEVEL, bool PERSIST, bool SOCK, bool TRAJ = false, bool CAPS = false, bool WIDE = false, int DV = 4, int DC = 8,
           int OCC = 0>
 __global__ __launch_bounds__(BLOCK, OCC ? OCC : WIDE ? 4 : PERSIST ? 8 : 7) __attribute__((amdgpu_num_sgpr(96))) void full_bp_small_kernel(const SmArgs a)
 {
-    static_assert(!WIDE || (BLOCK == 1024 && LEVEL && SOCK && !PERSIST && !CAPS), "the wide form: LEVEL [+ TRAJ], socket table");
-    static_assert((DV == 4 && DC == 8) || (SOCK && !PERSIST && !CAPS), "other degree pairs: the socket table, no PERSIST, no CAPS");
+    static_assert(!WIDE || (BLOCK == 1024 && LEVEL && SOCK && !PERSIST), "the wide form: LEVEL [+ TRAJ | CAPS], socket table");
+    static_assert(!(TRAJ && CAPS), "the checkpoints have no rows form");
+    static_assert((DV == 4 && DC == 8) || (SOCK && !PERSIST), "other degree pairs: the socket table, no PERSIST");
     static_assert(DC <= 15 && DC % 2 == 0 && DV < DC, "a CN's count of erased neighbours is a nibble; CN rows are read as 32-bit words");
     using QT = std::conditional_t<WIDE, uint32_t, uint16_t>;             // a queue entry: a CN id
     constexpr int kWaves = BLOCK / 64;
@@ -680,7 +682,7 @@ constexpr bool kCnTable = false, kSockTable = true, kNarrow = false, kWide = tru
 struct Form {
     Mode mode;
     bool sock;          // the CN table holds sockets instead of global VN ids
-    bool wide;          // 32-bit queue entries, one 1024-thread workgroup per CU (LEVEL or TRAJ with sockets only)
+    bool wide;          // 32-bit queue entries, one 1024-thread workgroup per CU (LEVEL, TRAJ or CAPS with sockets only)
     bool deg = false;   // the _deg entry points: the degree pair of the parameters picks the instance (sockets only)
     // the A/B knobs SCLDPC_DEBUG_DECODER_KSWITCH, SCLDPC_DEBUG_GRID_DECODER and SCLDPC_DEBUG_LDS_PAD_DECODER act on these forms only
     bool knobs() const { return mode != M_CAPS && !wide && !deg; }
@@ -709,7 +711,8 @@ constexpr int form_key(Mode mode, bool sock, bool wide, bool persist, int pair =
 // The instances <BLOCK, LEVEL, PERSIST, SOCK, TRAJ, CAPS, WIDE, DV, DC> with their VGPRs / SGPRs at -O3 for gfx950; no scratch
 // except where noted (as found; not looked into here).  persist: workgroup b decodes trials b, b + gridDim.x, … — reached through
 // SCLDPC_DEBUG_GRID_DECODER only, CN -> VN table only.  pair: pair_of(dv, dc); the twelve (4,8) instances first, then five per
-// further pair (socket table: fixpoint, LEVEL, TRAJ, wide LEVEL, wide TRAJ).  nullptr: no such instance.
+// further pair (socket table: fixpoint, LEVEL, TRAJ, wide LEVEL, wide TRAJ), then the five CAPS instances of the wide form and of
+// the further pairs.  nullptr: no such instance.
 Kernel kernel_of(const Form &f, bool persist, int pair = 0)
 {
     constexpr int S = kBlockSmall, W = kBlockWide;
@@ -736,6 +739,11 @@ Kernel kernel_of(const Form &f, bool persist, int pair = 0)
     case form_key(M_TRAJ, kSockTable, kNarrow, false, 2):  return full_bp_small_kernel<S, true, false, true, true, false, false, 5, 10, 6>; // 77 / 94, six waves per SIMD (28 B of scratch at seven): per_cu_of
     case form_key(M_LEVEL, kSockTable, kWide, false, 2):   return full_bp_small_kernel<W, true, false, true, false, false, true, 5, 10>;    // 67 / 94
     case form_key(M_TRAJ, kSockTable, kWide, false, 2):    return full_bp_small_kernel<W, true, false, true, true, false, true, 5, 10>;     // 81 / 94
+    case form_key(M_CAPS, kSockTable, kWide, false):       return full_bp_small_kernel<W, true, false, true, false, true, true>;            // 63 / 94
+    case form_key(M_CAPS, kSockTable, kNarrow, false, 1):  return full_bp_small_kernel<S, true, false, true, false, true, false, 3, 6>;     // 61 / 94
+    case form_key(M_CAPS, kSockTable, kNarrow, false, 2):  return full_bp_small_kernel<S, true, false, true, false, true, false, 5, 10>;    // 69 / 94
+    case form_key(M_CAPS, kSockTable, kWide, false, 1):    return full_bp_small_kernel<W, true, false, true, false, true, true, 3, 6>;      // 61 / 94
+    case form_key(M_CAPS, kSockTable, kWide, false, 2):    return full_bp_small_kernel<W, true, false, true, false, true, true, 5, 10>;     // 69 / 94
     }
     return nullptr;
 }
@@ -878,7 +886,8 @@ extern "C" int scldpc_full_bp_caps_device_sock16(const scldpc_code_params *p, in
 }
 
 // The level-synchronous decoder for trials of more than 65536 CNs (32-bit queue entries, a 1024-thread workgroup per CU):
-// arguments, counters and rows exactly as scldpc_full_bp_device_sock16 / scldpc_full_bp_traj_device_sock16
+// arguments, counters, rows and cap blocks exactly as scldpc_full_bp_device_sock16 / scldpc_full_bp_traj_device_sock16 /
+// scldpc_full_bp_caps_device_sock16
 extern "C" int scldpc_full_bp_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                           const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it,
                                           int32_t is_term, int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
@@ -895,6 +904,14 @@ extern "C" int scldpc_full_bp_traj_device_wide(const scldpc_code_params *p, int3
     if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_wide: null d_rows");
     return launch("scldpc_full_bp_traj_device_wide", {M_TRAJ, kSockTable, kWide},
                   {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap});
+}
+
+extern "C" int scldpc_full_bp_caps_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                               const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                               const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream)
+{
+    return launch("scldpc_full_bp_caps_device_wide", {M_CAPS, kSockTable, kWide},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, 0, is_term, d_counters, nullptr, stream, nullptr, 0, ncaps, caps});
 }
 
 // The same five decoders for the regular pairs (3,6), (4,8) and (5,10): 4 bits of LDS per CN where scldpc_full_bp_device_adj16 and
@@ -947,4 +964,22 @@ extern "C" int scldpc_full_bp_traj_device_deg_wide(const scldpc_code_params *p, 
     if (!d_rows) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_traj_device_deg_wide: null d_rows");
     return launch("scldpc_full_bp_traj_device_deg_wide", {M_TRAJ, kSockTable, kWide, kDeg},
                   {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, max_it, is_term, d_counters, d_erased_bits, stream, d_rows, rows_cap});
+}
+
+// Several caps from one decode for the same pairs: block k of d_counters [ncaps][ntrials][8] is what scldpc_full_bp_device_deg /
+// _deg_wide (max_it = caps[k]) writes; the shapes of the level forms.  (4,8) runs the _sock16 / _wide caps instances.
+extern "C" int scldpc_full_bp_caps_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                              const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                              const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream)
+{
+    return launch("scldpc_full_bp_caps_device_deg", {M_CAPS, kSockTable, kNarrow, kDeg},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, 0, is_term, d_counters, nullptr, stream, nullptr, 0, ncaps, caps});
+}
+
+extern "C" int scldpc_full_bp_caps_device_deg_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                                   const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                                   const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream)
+{
+    return launch("scldpc_full_bp_caps_device_deg_wide", {M_CAPS, kSockTable, kWide, kDeg},
+                  {p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, 0, is_term, d_counters, nullptr, stream, nullptr, 0, ncaps, caps});
 }

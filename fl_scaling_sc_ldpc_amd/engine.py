@@ -390,11 +390,30 @@ def check_caps(caps):
 def full_bp_caps_cn16(p, d_adj16, d_cn16, d_chan, caps, is_term=True, counters=None, sockets=False):
     """scldpc_full_bp_caps_device_cn16 (sockets=True: _sock16): one decode, the counters of several iteration caps —
     counters [K, T, 8], where counters[k] == full_bp_cn16(..., max_it=caps[k])["counters"] on all eight columns."""
+    fn = lib().scldpc_full_bp_caps_device_sock16 if sockets else lib().scldpc_full_bp_caps_device_cn16
+    return _full_bp_caps(fn, p, d_adj16, d_cn16, d_chan, caps, is_term, counters)
+
+
+def _full_bp_caps(fn, p, d_adj16, d_cn, d_chan, caps, is_term, counters):
+    """The call of a caps entry point (they share their arguments) through _full_bp: counters [K, T, 8]."""
     caps = check_caps(caps)
     arr = (C.c_int32 * len(caps))(*caps)
-    fn = lib().scldpc_full_bp_caps_device_sock16 if sockets else lib().scldpc_full_bp_caps_device_cn16
-    return _full_bp(p, d_adj16, d_cn16, d_chan, lambda head, cnt, rows, erased, stream:
+    return _full_bp(p, d_adj16, d_cn, d_chan, lambda head, cnt, rows, erased, stream:
                     fn(*head, len(caps), arr, 1 if is_term else 0, cnt, stream), counters, ncaps=len(caps))["counters"]
+
+
+def full_bp_caps_wide(p, d_adj16, d_cn_sock, d_chan, caps, is_term=True, counters=None):
+    """scldpc_full_bp_caps_device_wide: full_bp_caps_cn16(sockets=True) for trials of more than 65536 CNs — counters [K, T, 8],
+    where counters[k] == full_bp_wide(..., max_it=caps[k])["counters"] on all eight columns.  The shapes of full_bp_wide."""
+    return _full_bp_caps(lib().scldpc_full_bp_caps_device_wide, p, d_adj16, d_cn_sock, d_chan, caps, is_term, counters)
+
+
+def full_bp_caps_deg(p, d_adj16, d_cn_sock, d_chan, caps, is_term=True, counters=None, wide=False):
+    """scldpc_full_bp_caps_device_deg (wide=True: _deg_wide): one decode, the counters of several iteration caps for the pairs
+    (3,6), (4,8), (5,10) — counters [K, T, 8], where counters[k] == full_bp_deg(..., max_it=caps[k], wide=wide)["counters"] on
+    all eight columns.  The shapes of full_bp_deg_supported(p, wide)."""
+    fn = lib().scldpc_full_bp_caps_device_deg_wide if wide else lib().scldpc_full_bp_caps_device_deg
+    return _full_bp_caps(fn, p, d_adj16, d_cn_sock, d_chan, caps, is_term, counters)
 
 
 def cn_sockets(p, d_adj16, out=None):

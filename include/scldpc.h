@@ -243,7 +243,10 @@ int scldpc_full_bp_traj_device_sock16(const scldpc_code_params *p, int32_t ntria
  * the CN -> socket table comes from scldpc_cn_sockets_device (or scldpc_sample_philox_device_sock16 where that sampler takes
  * the ensemble).  Takes dv = 4, dc = 8, vns_pos * dv <= 65535, cns_pos <= 65536 and a per-trial state (4 bits per CN, a bit
  * per VN) that leaves at least 1024 entries per queue in the CU's 160 KiB: SCLDPC_ERR_TOO_LARGE names the limit otherwise.
- * It also takes every smaller (4,8) shape (bit for bit the _sock16 result).  No wide fixpoint or caps form. */
+ * It also takes every smaller (4,8) shape (bit for bit the _sock16 result).  No wide fixpoint form.
+ * scldpc_full_bp_caps_device_wide is scldpc_full_bp_caps_device_sock16 for these trials: same arguments and checks, block k of
+ * d_counters what scldpc_full_bp_device_wide writes with max_it = caps[k].  A caps form has no shape rule of its own: it takes
+ * exactly the shapes of its family's level form (here scldpc_full_bp_wide_supported), on the same LDS carve. */
 int scldpc_full_bp_wide_supported(const scldpc_code_params *p);
 int scldpc_full_bp_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
@@ -251,6 +254,9 @@ int scldpc_full_bp_device_wide(const scldpc_code_params *p, int32_t ntrials, con
 int scldpc_full_bp_traj_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                     const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
                                     int32_t *d_counters, int32_t *d_rows, int32_t rows_cap, uint32_t *d_erased_bits, void *stream);
+int scldpc_full_bp_caps_device_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                    const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                    const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream);
 /* The 4-bit decoders above for the regular pairs (3,6), (4,8) and (5,10), on the socket table: what
  * scldpc_full_bp_device_adj16 / scldpc_full_bp_fixpoint_device_adj16 compute for these pairs (decodeBP, BPF:900-1140; the rows of
  * the BPT build, BPT:988, 1037-1038, 1051) with 4 bits of LDS per CN instead of a 16-bit word.  They read d_vn_adj16 uint16
@@ -261,11 +267,15 @@ int scldpc_full_bp_traj_device_wide(const scldpc_code_params *p, int32_t ntrials
  *   scldpc_full_bp_traj_device_deg         as scldpc_full_bp_traj_device_sock16       (BPT:900-1140 with its rows)
  *   scldpc_full_bp_device_deg_wide         as scldpc_full_bp_device_wide              (more than 65536 CNs per trial)
  *   scldpc_full_bp_traj_device_deg_wide    as scldpc_full_bp_traj_device_wide
+ *   scldpc_full_bp_caps_device_deg         as scldpc_full_bp_caps_device_sock16       (several caps from one decode)
+ *   scldpc_full_bp_caps_device_deg_wide    as scldpc_full_bp_caps_device_wide
  * For (4,8) they run the _sock16 / _wide kernels: bit for bit the same result.  SCLDPC_ERR_TOO_LARGE names the limit: a pair
  * without a kernel, dc > 15 (a CN's count is a nibble), sockets beyond 16 bits, more than 65536 CNs per trial (narrow), a
  * state that leaves no room for the queues (wide: fewer than 1024 entries per queue), or queues so short that a wave's
  * per-iteration tallies could leave their 15 + 17 bits.  *_supported: 1 when every narrow (wide) form takes the ensemble.
- * No caps form. */
+ * The caps forms have no predicate of their own: they take exactly the shapes of the level form of their family
+ * (scldpc_full_bp_deg_supported / scldpc_full_bp_deg_wide_supported), on the same LDS carve; block k of d_counters is what
+ * scldpc_full_bp_device_deg / _deg_wide writes with max_it = caps[k]. */
 int scldpc_full_bp_deg_supported(const scldpc_code_params *p);        /* narrow: <= 65536 CNs per trial */
 int scldpc_full_bp_deg_wide_supported(const scldpc_code_params *p);
 int scldpc_full_bp_fixpoint_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
@@ -283,6 +293,12 @@ int scldpc_full_bp_device_deg_wide(const scldpc_code_params *p, int32_t ntrials,
 int scldpc_full_bp_traj_device_deg_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                         const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t max_it, int32_t is_term,
                                         int32_t *d_counters, int32_t *d_rows, int32_t rows_cap, uint32_t *d_erased_bits, void *stream);
+int scldpc_full_bp_caps_device_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                   const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                   const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream);
+int scldpc_full_bp_caps_device_deg_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                        const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t ncaps,
+                                        const int32_t *caps, int32_t is_term, int32_t *d_counters, void *stream);
 
 /* decodeBP_SW, square window (BPW:628-912): window of W positions, init_it iterations for the
  * first window and max_it for the others (init_it == 0 ⇒ max_it, BPW:2101-2102). */
