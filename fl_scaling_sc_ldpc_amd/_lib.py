@@ -52,6 +52,7 @@ EXPORTS = (
     "scldpc_full_bp_caps_device_wide", "scldpc_full_bp_caps_device_deg", "scldpc_full_bp_caps_device_deg_wide",
     "scldpc_sw_bp_ring_deg_supported", "scldpc_sw_bp_ring_device_deg",
     "scldpc_stream_supported",
+    "scldpc_swc_bp_ring_supported", "scldpc_swc_bp_ring_device",
 )
 
 
@@ -168,6 +169,8 @@ def lib():
     L.scldpc_sw_bp_ring_device.argtypes = [pp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.scldpc_sw_bp_ring_deg_supported.argtypes = L.scldpc_sw_bp_ring_supported.argtypes
     L.scldpc_sw_bp_ring_device_deg.argtypes = L.scldpc_sw_bp_ring_device.argtypes
+    L.scldpc_swc_bp_ring_supported.argtypes = L.scldpc_sw_bp_ring_supported.argtypes
+    L.scldpc_swc_bp_ring_device.argtypes = [pp, i32, vp, vp, vp, i32, i32, vp, vp, vp]
     L.scldpc_accumulate_run_device.argtypes = [i32, vp, i64, vp, vp]
     L.scldpc_accumulate_peel_device.argtypes = [i32, vp, i64, vp, vp]
     L.scldpc_clear_channel_range_device.argtypes = [pp, i32, i32, i32, vp, vp]

@@ -34,6 +34,11 @@ sampling, NUM_DOPED = 0) the frames are sampled and decoded once, with a checkpo
 (engine.full_bp_caps_cn16); otherwise the caps run one after another.  `--caps-fused on` extends the one decode to trials of
 more than 65536 CNs (engine.full_bp_caps_wide) and to the pairs (3,6) and (5,10) (engine.full_bp_caps_deg).
 
+`bp_lim_iter INDEX W NUM_DOPED MAX_IT --window classical` decodes with the classical sliding window kept in the full-BP source
+(decodeBP_SW, BPF:627-897; the reference runs it with the commented call at BPF:2137-2138 swapped in): W positions per window,
+MAX_IT iterations per window, the file name and rows of `bp_lim_iter`.  `--ring on|off|auto` picks the ring window decoder or
+the whole-chain kernel; both write the same file.
+
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
@@ -147,6 +152,11 @@ DEG_BY_DEFAULT = False
 # tools/ring_deg_speedup.py, with identical counters (profiles/ring_deg_speedup.json)
 RING_DEG_BY_DEFAULT = False
 
+# Whether Simulator(decoder="swc", ring=None) takes the classical ring window decoder where it applies, under the same rule:
+# every repetition of the ring path beats every repetition of the whole-chain kernel end to end on every shape of
+# tools/classical_ring_speedup.py, with identical counters (profiles/classical_ring_speedup.json)
+CLASSICAL_RING_BY_DEFAULT = False
+
 # Whether Simulator(fused_caps=None) and `bp_lim_iter --caps` take the cap checkpoints of the wide form and of the pairs (3,6) and
 # (5,10) where they apply, instead of one single-cap pass per cap (tools/caps_forms_speedup.py, profiles/caps_forms_speedup.json).
 # The (4,8) forms of at most 65536 CNs fuse without this switch.
@@ -159,7 +169,9 @@ CAPS_FORMS_BY_DEFAULT = False
 #                generation, with the CN -> VN / CN -> socket table)
 #   cn_table     the CN table kept next to the VN -> CN one: None, "vn" or "sock"
 #   cn_pass      that table comes from the cn_sockets pass (the sampler does not emit it)
-#   decoder      "sw_ring" / "sw_chain" (E.sw_bp; "sw_ring" with cn_pass: the _deg entry points, pairs (3,6) and (5,10)), or the full-BP call that walks the iterations: "level16", "wide", "full_bp",
+#   decoder      "sw_ring" / "sw_chain" (E.sw_bp; "sw_ring" with cn_pass: the _deg entry points, pairs (3,6) and (5,10)),
+#                "swc_ring" / "swc_chain" (E.sw_bp(classical=True): the classical window of decoder="swc"), or the full-BP call
+#                that walks the iterations: "level16", "wide", "full_bp",
 #                "deg16" / "degwide" (the 4-bit level decoder of the pairs (3,6) and (5,10), 16- / 32-bit queue entries)
 #   fix_decoder  the fixpoint kernel an unlimited fixpoint run takes for calls without rows: "fixpoint16", "fixpoint_deg",
 #                "fixpoint" or None
@@ -185,7 +197,8 @@ class Simulator:
         # DEG_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path)
         self.want_deg = deg
         # ring: the ring window decoder (sw_ring) for dv, dc other than (4,8), decoder="sw" only.  None = where RING_DEG_BY_DEFAULT
-        # says, True = wherever it applies, False = never (the whole-chain kernel)
+        # says, True = wherever it applies, False = never (the whole-chain kernel).  decoder="swc" (the classical window, W and
+        # max_it per window): the classical ring decoder of all three pairs, None = where CLASSICAL_RING_BY_DEFAULT says
         self.want_ring = ring
         # fused_caps: with caps, the cap checkpoints of the wide form and of the pairs (3,6) and (5,10).  None = where
         # CAPS_FORMS_BY_DEFAULT says, True = wherever an instance applies (wide=False / deg=False veto their family), False = never
@@ -237,6 +250,15 @@ class Simulator:
                 self.path = Path(adj_dtype, first, "sock", True, "sw_ring", None)
             else:
                 self.path = Path(adj_dtype, first, None, False, "sw_ring" if ring else "sw_chain", None)
+        elif self.decoder == "swc":
+            # classical window: the ring kernel reads the CN -> socket table, sampled with the code where the second-generation
+            # sampler takes the ensemble, else from the cn_sockets pass; everything else keeps the whole-chain kernel
+            if classical_ring_reason(p, self.W, self.rng, self.want_ring) is not None:
+                self.path = Path(adj_dtype, first, None, False, "swc_chain", None)
+            elif E.sock16_supported(p):
+                self.path = Path(adj_dtype, "sock16", "sock", False, "swc_ring", None)
+            else:
+                self.path = Path(adj_dtype, first, "sock", True, "swc_ring", None)
         elif table is not None:
             # full BP on the BASELINE ensemble family: the second-generation pair (sampler_v2 + the 4-bits-per-CN decoder) needs
             # the CN -> VN table (n >= 65535: the CN -> socket table) next to the VN -> CN one.  Unlimited, no iteration
@@ -339,6 +361,10 @@ class Simulator:
             return "sampler (first generation) + sw_bp (whole chain)"
         samp = {"glibc": "glibc replay on the host", "first": "sampler (first generation)", "cn16": "sampler_v3 (CN->VN table)",
                 "sock16": "sampler_v3 (CN->socket table)"}[path.sampler] + (" + cn_sockets pass" if path.cn_pass else "")
+        if path.decoder == "swc_ring":
+            return samp + " + sw_ring classical window (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc)
+        if path.decoder == "swc_chain":
+            return samp + " + sw_bp classical window (whole chain)"
         rows = ", trajectory rows)" if self.rows_cap else ")"
         if path.fix_decoder == "fixpoint16":
             return samp + " + full_bp_small fixpoint (4-bit CN counts)"
@@ -379,6 +405,9 @@ class Simulator:
             return E.sw_bp(self.p, adj, ch, self.W, self.max_it, self.init_it, counters=cnt,
                            d_cn_sock=self.d_cn[:nb] if path.cn_table is not None else None,
                            ring=True if self.ring_deg else None, deg=self.ring_deg)
+        if path.decoder in ("swc_ring", "swc_chain"):
+            return E.sw_bp(self.p, adj, ch, self.W, self.max_it, counters=cnt, classical=True, ring=path.decoder == "swc_ring",
+                           d_cn_sock=self.d_cn[:nb] if path.cn_table is not None else None)
         # the fixpoint kernels report neither iteration counts nor rows: a call that wants rows walks the iterations
         decoder = path.fix_decoder if (path.fix_decoder is not None and not want_rows) else path.decoder
         sockets, rows_cap = path.cn_table == "sock", self.rows_cap if want_rows else 0
@@ -564,6 +593,22 @@ def ring_deg_reason(p, W, rng, want=True):
     if not E.sw_ring_deg_supported(p, W):
         return ("the ring kernel takes the pairs (3,6), (4,8) and (5,10) with W >= 1, vns_pos * dv <= 65535, L + dv - 1 <= 65535 "
                 "and a window state that fits the LDS (dv = %d, dc = %d, L = %d, N = %d, W = %d)" % (p.dv, p.dc, p.L, p.vns_pos, W))
+    return None
+
+
+def classical_ring_reason(p, W, rng, want=True):
+    """Why decoder="swc" does not take the classical ring window decoder on this configuration, or None where it does.
+    want: the Simulator's ring argument (None: CLASSICAL_RING_BY_DEFAULT)."""
+    if not (CLASSICAL_RING_BY_DEFAULT if want is None else bool(want)):
+        return "switched off"
+    if rng != "philox":
+        return "--rng %s samples the 4-byte VN -> CN table on the host: the ring kernel reads the 2-byte tables" % rng
+    if p.cns_pos > 65536:
+        return "more than 65536 CNs per position: no 2-byte VN -> CN table"
+    if not E.swc_ring_supported(p, W):
+        return ("the classical ring kernel takes the pairs (3,6), (4,8) and (5,10) with W >= 1, vns_pos * dv <= 65535, "
+                "L + dv - 1 <= 65535 and a window state that fits the LDS (dv = %d, dc = %d, L = %d, N = %d, W = %d)"
+                % (p.dv, p.dc, p.L, p.vns_pos, W))
     return None
 
 
@@ -777,6 +822,15 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
         init_it = extra if extra else max_it                       # BPW:2101-2102
     elif prog == "bp_traj":
         is_term = bool(extra)
+    ring = {"auto": None, "on": True, "off": False}[getattr(opts, "ring", "auto")]
+    if prog == "bp_lim_iter":
+        _check_window(opts)
+        if getattr(opts, "window", "off") == "classical":
+            # the reference with the commented call at BPF:2137-2138 swapped in: same file, MAX_IT iterations per window
+            decoder = "swc"
+            why = classical_ring_reason(p, W, opts.rng) if ring else None
+            if why is not None:
+                raise SystemExit("--ring on: " + why)
     dist, rank, world = _dist()
     if opts.rng == "glibc" and world > 1:
         # one srandom(seed) stream carried from frame to frame and from point to point (BPF:2057-2131): there is nothing to
@@ -796,7 +850,6 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
         return _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, shard, by_points)
     # the decoders' loop is do { … } while (iter < MaxNumIt) (BPF:1065, BPT:1076): at least one iteration runs
     cap = max(1, max_it)
-    ring = {"auto": None, "on": True, "off": False}[getattr(opts, "ring", "auto")]
     if ring and prog == "sw_lim_iter":
         why = ring_deg_reason(p, W, opts.rng)
         if why is not None:
@@ -808,7 +861,7 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                         verbose=rank == 0 and not opts.quiet,
                         wide={"auto": None, "on": True, "off": False}[getattr(opts, "wide", "auto")],
                         deg={"auto": None, "on": True, "off": False}[getattr(opts, "deg", "auto")],
-                        ring=ring if prog == "sw_lim_iter" else None)
+                        ring=ring if decoder in ("sw", "swc") else None)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     t0 = time.time()
@@ -879,8 +932,32 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
     return 0
 
 
+def _check_window(opts):
+    """bp_lim_iter's --window / --ring against the rest of the command line: exits with the reason."""
+    window, ring = getattr(opts, "window", "off"), getattr(opts, "ring", "auto")
+    if window != "classical":
+        if ring == "on":
+            raise SystemExit("--ring on: needs --window classical (full BP has no window to keep in a ring)")
+        return
+    if getattr(opts, "caps", None):
+        raise SystemExit("--window classical: --caps belongs to full BP (the cap checkpoints of one decode); MAX_IT is the cap of "
+                         "every window here")
+    if getattr(opts, "schedule", "flooding") != "flooding":
+        raise SystemExit("--window classical: --schedule %s belongs to unlimited full BP; a window counts its flooding iterations"
+                         % opts.schedule)
+
+
+class _LimIterParser(argparse.ArgumentParser):
+    """bp_lim_iter: combinations that cannot run end the program where the command line is read."""
+
+    def parse_args(self, args=None, namespace=None):
+        opts = super().parse_args(args, namespace)
+        _check_window(opts)
+        return opts
+
+
 def _parser(prog):
-    ap = argparse.ArgumentParser(prog=prog, description=__doc__.split("\n\n")[0])
+    ap = (_LimIterParser if prog == "bp_lim_iter" else argparse.ArgumentParser)(prog=prog, description=__doc__.split("\n\n")[0])
     ap.add_argument("INDEX", type=int)
     ap.add_argument("W", type=int)
     ap.add_argument("NUM_DOPED", type=int)
@@ -925,6 +1002,15 @@ def _parser(prog):
         ap.add_argument("--ring", choices=("auto", "on", "off"), default="auto",
                         help="--dv/--dc 3/6 or 5/10: the ring window decoder (on), the whole-chain kernel (off), or the measured "
                              "default (auto); same files")
+    if prog == "bp_lim_iter":
+        ap.add_argument("--window", choices=("off", "classical"), default="off",
+                        help="classical: the classical sliding window of W positions (decodeBP_SW of the full-BP source, "
+                             "BPF:627-897, whose call is commented out at BPF:2137-2138) with MAX_IT iterations per window, "
+                             "instead of full BP; same file name and rows")
+        ap.add_argument("--ring", choices=("auto", "on", "off"), default="auto",
+                        help="--window classical with --dv/--dc 3/6, 4/8 or 5/10: the ring window decoder (on), the whole-chain "
+                             "kernel (off), or the measured default (auto); same files.  'on' where the ring cannot apply is an "
+                             "error that names the limit")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")

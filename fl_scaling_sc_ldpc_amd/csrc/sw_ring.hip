@@ -1,4 +1,5 @@
-// Square sliding-window BP (decodeBP_SW, BPW:628-912) with the window's state — and nothing else — in LDS: gfx950.
+// Sliding-window BP — the square window (decodeBP_SW, BPW:628-912) and the classical one (BPF:627-897) — with the window's
+// state, and nothing else, in LDS: gfx950.  The text describes the square form; the classical form is set apart below.
 //
 // sw_bp.hip keeps one word per CN of the WHOLE chain (in LDS up to N = 1024, in a device workspace beyond: L2 atomics,
 // two trials per CU).  But window posW only ever fires CNs of positions [posW, posW+W) and only releases VNs of positions
@@ -26,8 +27,18 @@
 // moved dv positions past it — then its dv CN positions are final and still in the ring; a qualifying partner lies in the
 // same position, so only S bits of position q are consulted.
 //
-// Instances: (dv, dc) = (4,8), and (3,6) and (5,10) behind scldpc_sw_bp_ring_device_deg.  A queue entry is
-// [CN position : 16 | CN : 16], a count a nibble (dc <= 15).
+// The classical window (CLASSICAL, scldpc_swc_bp_ring_device; the semantics of sw_bp.hip's `classical`): L + ms windows
+// (ms = dv - 1), CN positions [posW, posW+W) as before, VN positions [posW-ms, posW+W) — so no neighbour of a window CN is
+// frozen — one cap for every window, and position posW-ms decided when window posW closes.  CN positions <= posW-ms are final
+// then, so VN position posW-2ms is the one to examine for stopping sets: the rings reach ms positions further back,
+//   * CN counts for positions [posW-2ms, posW+W+ms]  (W+3dv-2 slots),
+//   * S bits for VN positions [posW-2ms, posW+W]     (W+2dv-1 slots),
+// and everything touched from one window still lies less than a ring apart.  The carried queue is kept: a count-one CN of an
+// earlier round has fired (none waits for a frozen VN here), so the last round's queue plus the CN position that entered
+// cover the next window; entries of the position that left are dropped.
+//
+// Instances: (dv, dc) = (4,8), and (3,6) and (5,10) behind scldpc_sw_bp_ring_device_deg; the classical form of each behind
+// scldpc_swc_bp_ring_device.  A queue entry is [CN position : 16 | CN : 16], a count a nibble (dc <= 15).
 #include "common.h"
 #include "kernel_util.h"
 #include "table_rows.h"
@@ -59,8 +70,9 @@ __device__ __forceinline__ uint32_t bits_at(const uint32_t *w, int nw, long long
 }
 
 // DV, DC: the degree pair, fixed at compile time (the rows of both tables are unrolled; loads no wider than a row's alignment
-// allows: table_rows.h).  Every instance holds the bound of eight workgroups per CU (64 VGPRs) without scratch.
-template <int DV, int DC>
+// allows: table_rows.h).  CLASSICAL: the classical window (head of this file); false compiles to the square kernel unchanged.
+// Every instance holds the bound of eight workgroups per CU (64 VGPRs) without scratch.
+template <int DV, int DC, bool CLASSICAL = false>
 __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) void sw_ring_kernel(const RArgs a)
 {
     static_assert(DC <= 15 && DC % 2 == 0 && DV < DC, "a CN's count of erased neighbours is a nibble; CN rows are read as 32-bit words");
@@ -76,7 +88,7 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
     const int tid = threadIdx.x, lane = tid & 63;
     const int trial = blockIdx.x;
     const int L = a.L, V = a.V, C = a.C, W = a.W, R = a.R, RV = a.RV, Cw = a.Cw, wpp = a.wpp, qcap = a.qcap;
-    const int D = L + DV - 1;
+    const int D = L + DV - 1, ms = DV - 1;
     const auto *vrow = reinterpret_cast<const typename VnUnit<DV>::type *>(a.vn_adj16) + (size_t)trial * a.n * VnUnit<DV>::per_row;
     const uint16_t *crow = a.cn_sock16 + (size_t)trial * a.nk * DC;
     const auto *crow_u = reinterpret_cast<const typename CnUnit<DC>::type *>(crow);
@@ -86,7 +98,8 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
     uint32_t *eout = a.erased_out ? a.erased_out + (size_t)trial * a.nw : nullptr;
 
     // Ring slots without a division (a release would pay a dozen of them): every position touched while the window
-    // stands at pw lies within [pw - (dv-1), pw + W + dv - 1], less than a ring apart, so one wrap of pw's own slot does.
+    // stands at pw lies within [pw - (dv-1), pw + W + dv - 1] (classical: from pw - 2(dv-1)), less than a ring apart, so
+    // one wrap of pw's own slot does.
     int pw = 0, cb = 0, vb = 0;                                           // window position, pw % R, pw % RV
     auto cslot = [&](int p) {                                             // word base of CN position p
         int sl = cb + (p - pw);
@@ -189,10 +202,12 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
     int iters_total = 0, gen = 0;
     int carry_n = 0, phi_prev = 0;
     bool carry_ok = false;                                                // the last round's queue is complete (no overflow)
-    for (int posW = 0; posW < L; posW++) {
+    const int last = CLASSICAL ? D : L;                                   // classical: L + ms windows (BPF:668-684)
+    for (int posW = 0; posW < last; posW++) {
         const int phi = min(posW + W, D);                                 // CN positions [posW, phi)   (BPW:674-676)
-        const int qhi = min(posW + W, L);                                 // VN positions [posW, qhi)   (BPW:691-693)
-        const int cap = posW == 0 ? a.init_it : a.max_it;                 // BPW:699-702
+        const int qlo = CLASSICAL ? max(posW - ms, 0) : posW;             // VN positions [qlo, qhi)    (BPW:691-693 / BPF:673-684)
+        const int qhi = min(posW + W, L);
+        const int cap = CLASSICAL ? a.max_it : (posW == 0 ? a.init_it : a.max_it);       // BPW:699-702 / BPF:824
         int iter = 0, prec = a.n, ncur = 0;
         bool scan = true;                                                 // the first window opens with a scan of its CNs
         if (carry_ok) {
@@ -200,6 +215,8 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
             // that held one erased neighbour earlier has fired since (count zero) or waits for a frozen VN for good — and
             // (b) those of the one CN position that has just entered the window (never queued: pushes stop at phi), whose
             // counts the VN position entered above has completed.  No snapshot needed: nothing is in flight here.
+            // Classical window: no neighbour of a window CN is frozen (positions >= p - ms >= qlo), so every count-one CN of
+            // an earlier round has fired and (a), (b) cover the window all the more; what (a) holds of position posW - 1 is dropped.
             uint32_t *qc = q[gen & 1];
             if (tid == 0) scal[R_TMP] = carry_n;
             __syncthreads();
@@ -233,7 +250,7 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
         }
         phi_prev = phi;
         int term = 0;
-        for (int qq = posW; qq < qhi; qq++) term += pos_cnt[qq];          // erasures inside the window (BPW:791-809)
+        for (int qq = qlo; qq < qhi; qq++) term += pos_cnt[qq];           // erasures inside the window (BPW:791-809)
         for (;;) {
             uint32_t *qc = q[gen & 1], *qn = q[(gen + 1) & 1];
             int *push = &scal[R_PUSH + (gen + 1) % 3], *ovf = &scal[R_OVF + (gen + 1) % 3], *rem = &scal[R_REM + gen % 3];
@@ -252,7 +269,7 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
                     const int qq = p - (int)(sk[k] % DV), t = (int)(sk[k] / DV);
                     if ((unsigned)qq < (unsigned)L && ((S[sslot(qq) + (t >> 5)] >> (t & 31)) & 1u)) { jq = qq; jt = t; }
                 }
-                if (jq < posW) return;                                    // none left (released this round) or frozen (BPW:745)
+                if (jq < qlo) return;                                     // none left (released this round) or frozen (BPW:745)
                 const Row<DV> ll = vn_row(jq * V + jt);                   // issued before the claim: overlaps its round trip
                 const uint32_t bit = 1u << (jt & 31);
                 if (!(atomicAnd(&S[sslot(jq) + (jt >> 5)], ~bit) & bit)) return;
@@ -264,7 +281,7 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
                     o[i] = atomicSub(&cnt[cslot(jq + i) + (ll[i] >> 3)], 1u << ((ll[i] & 7) * 4));
 #pragma unroll
                 for (int i = 0; i < DV; i++)
-                    if (((o[i] >> ((ll[i] & 7) * 4)) & 15u) == 2u && jq + i < phi)       // 2 -> 1 inside the window: fires next iteration
+                    if (((o[i] >> ((ll[i] & 7) * 4)) & 15u) == 2u && jq + i < phi && (!CLASSICAL || jq + i >= posW))     // 2 -> 1 inside the window: fires next iteration
                         out[i] = 1u + (((uint32_t)(jq + i) << 16) | ll[i]);
             };
             // a wave appends its lanes' entries behind *push: one prefix scan + one LDS atomic per wave
@@ -329,11 +346,12 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
         }
         carry_ok = !scan;
         carry_n = ncur;
-        // position posW is decided (BPW:759-788): its S bits are VNerased from now on
-        emit_erased(posW);
+        const int qdec = CLASSICAL ? posW - ms : posW;
+        // position posW (classical: posW - ms) is decided (BPW:759-788): its S bits are VNerased from now on
+        if (!CLASSICAL || qdec >= 0) emit_erased(qdec);
         if (posW + W < L) enter(posW + W);                                // the next window's new position
         else __syncthreads();
-        if (posW - (DV - 1) >= 0) expurgate(posW - (DV - 1));             // CN positions up to posW are final now
+        if (qdec - ms >= 0) expurgate(qdec - ms);                         // CN positions up to qdec are final now
         pw = posW + 1;
         cb = cb + 1 == R ? 0 : cb + 1;
         vb = vb + 1 == RV ? 0 : vb + 1;
@@ -344,12 +362,12 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
 
     if (tid == 0) {
         int ne = 0, be = 0, ee = 0, bee = 0, p1 = 0;
-        const int ms = DV - 1;
         for (int pos = 0; pos < L; pos++) {
             const int c = pos_cnt[pos];
             ne += c;
             if (c > 0) be++;
-            if (pos >= ms && pos <= W - 2) p1 += c;                       // NumErasuresP1 (BPW:846-847)
+            // NumErasuresP1: windows ms <= posW <= W-2 (BPW:846-847); the classical window decides position posW - ms
+            if (CLASSICAL ? pos <= W - 2 - ms : (pos >= ms && pos <= W - 2)) p1 += c;
             const int e = c - pos_ss[pos];
             if (e > 0) { ee += e; bee++; }                                // every position (BPW:903-907)
         }
@@ -400,19 +418,23 @@ __global__ __launch_bounds__(256) void cn_sockets_kernel(const IArgs a)
 using RingKernel = void (*)(const RArgs);
 
 // the instance of a degree pair, nullptr: none
-RingKernel ring_kernel_of(int dv, int dc)
+RingKernel ring_kernel_of(int dv, int dc, bool classical = false)
 {
-    if (dv == 4 && dc == 8) return sw_ring_kernel<4, 8>;
-    if (dv == 3 && dc == 6) return sw_ring_kernel<3, 6>;
-    if (dv == 5 && dc == 10) return sw_ring_kernel<5, 10>;
+    if (dv == 4 && dc == 8) return classical ? sw_ring_kernel<4, 8, true> : sw_ring_kernel<4, 8>;
+    if (dv == 3 && dc == 6) return classical ? sw_ring_kernel<3, 6, true> : sw_ring_kernel<3, 6>;
+    if (dv == 5 && dc == 10) return classical ? sw_ring_kernel<5, 10, true> : sw_ring_kernel<5, 10>;
     return nullptr;
 }
 
-int ring_args(const scldpc_code_params *p, int W, RArgs *a)
+// CN / VN ring slots: the classical window keeps dv - 1 more positions behind the window (see the head of this file)
+int64_t ring_slots_cn(int dv, int64_t W, bool classical) { return classical ? W + 3 * dv - 2 : W + 2 * dv - 1; }
+int64_t ring_slots_vn(int dv, int64_t W, bool classical) { return classical ? W + 2 * dv - 1 : W + dv; }
+
+int ring_args(const scldpc_code_params *p, int W, RArgs *a, bool classical = false)
 {
     a->dv = p->dv; a->dc = p->dc; a->L = p->L; a->V = p->vns_pos; a->C = p->cns_pos;
     a->n = scldpc::n_of(p); a->nk = scldpc::nk_of(p); a->W = W; a->nw = scldpc::nw_of(p);
-    a->R = W + 2 * p->dv - 1; a->RV = W + p->dv;
+    a->R = (int)ring_slots_cn(p->dv, W, classical); a->RV = (int)ring_slots_vn(p->dv, W, classical);
     a->Cw = (p->cns_pos + 7) / 8; a->wpp = (p->vns_pos + 31) / 32;
     int off = 0;
     auto take = [&](int words) { int o = off; off += (words + 3) & ~3; return o; };
@@ -434,8 +456,8 @@ int ring_args(const scldpc_code_params *p, int W, RArgs *a)
     return 4 * off <= scldpc::kMaxLdsBytes ? 0 : -1;
 }
 
-// Which limit keeps (p, W) from scldpc_sw_bp_ring_device_deg; nullptr: none
-const char *ring_deg_limit(const scldpc_code_params *p, int W)
+// Which limit keeps (p, W) from scldpc_sw_bp_ring_device_deg (classical: from scldpc_swc_bp_ring_device); nullptr: none
+const char *ring_deg_limit(const scldpc_code_params *p, int W, bool classical = false)
 {
     if (scldpc::check_params(p)) return "invalid code parameters";
     if (p->dc > 15) return "dc must be at most 15 (a CN's count of erased neighbours is kept in 4 bits)";
@@ -449,24 +471,24 @@ const char *ring_deg_limit(const scldpc_code_params *p, int W)
     if (p->cns_pos > 65536) return "at most 65536 CNs per position (16-bit position-local CN ids)";
     if ((int64_t)p->L + p->dv - 1 > 65535) return "queue: L + dv - 1 CN positions must fit 16 bits (at most 65535)";
     // the state in 64 bits first: ring_args computes in int
-    const int64_t state = ((int64_t)W + 2 * p->dv - 1) * ((p->cns_pos + 7) / 8) + ((int64_t)W + p->dv) * ((p->vns_pos + 31) / 32) +
+    const int64_t state = ring_slots_cn(p->dv, W, classical) * ((p->cns_pos + 7) / 8) + ring_slots_vn(p->dv, W, classical) * ((p->vns_pos + 31) / 32) +
                           ((int64_t)W * ((p->cns_pos + 7) / 8) + 3) / 4 + 2 * (int64_t)p->L;
     RArgs a{};
-    if (4 * state > scldpc::kMaxLdsBytes || ring_args(p, W, &a) != 0)
+    if (4 * state > scldpc::kMaxLdsBytes || ring_args(p, W, &a, classical) != 0)
         return "LDS: the window's CN counts, S bits and queues exceed 160 KiB";
     return nullptr;
 }
 
 int ring_launch(const char *who, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16, const uint16_t *d_cn_sock16,
                 const uint32_t *d_chan_bits, int32_t W, int32_t max_it, int32_t init_it, int32_t *d_counters,
-                uint32_t *d_erased_bits, void *stream)
+                uint32_t *d_erased_bits, void *stream, bool classical = false)
 {
     RArgs a{};
-    ring_args(p, W, &a);
+    ring_args(p, W, &a, classical);
     a.max_it = max_it; a.init_it = init_it ? init_it : max_it;           // BPW:2101-2102
     a.vn_adj16 = d_vn_adj16; a.cn_sock16 = d_cn_sock16; a.chan = d_chan_bits;
     a.counters = d_counters; a.erased_out = d_erased_bits;
-    RingKernel kern = ring_kernel_of(p->dv, p->dc);
+    RingKernel kern = ring_kernel_of(p->dv, p->dc, classical);
     if (!kern) return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: no instance for dv = %d, dc = %d", who, p->dv, p->dc);
     const size_t lds_bytes = 4u * (size_t)a.total;
     if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
@@ -540,4 +562,22 @@ extern "C" int scldpc_sw_bp_ring_device_deg(const scldpc_code_params *p, int32_t
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
     if (ntrials == 0) return SCLDPC_OK;
     return ring_launch(who, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, W, max_it, init_it, d_counters, d_erased_bits, stream);
+}
+
+// The classical window (BPF:627-897) of the same three pairs: sw_ring_kernel's classical instance of the pair.
+// 1 when scldpc_swc_bp_ring_device takes (p, W)
+extern "C" int scldpc_swc_bp_ring_supported(const scldpc_code_params *p, int32_t W) { return ring_deg_limit(p, W, true) == nullptr; }
+
+extern "C" int scldpc_swc_bp_ring_device(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                         const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t W, int32_t max_it,
+                                         int32_t *d_counters, uint32_t *d_erased_bits, void *stream)
+{
+    const char *who = "scldpc_swc_bp_ring_device";
+    if (int rc = scldpc::check_params(p)) return rc;
+    if (W < 1 || max_it < 0) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: need W >= 1, max_it >= 0", who);
+    if (const char *why = ring_deg_limit(p, W, true)) return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
+    if (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj16 || !d_cn_sock16 || !d_chan_bits)))
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
+    if (ntrials == 0) return SCLDPC_OK;
+    return ring_launch(who, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, W, max_it, max_it, d_counters, d_erased_bits, stream, true);
 }

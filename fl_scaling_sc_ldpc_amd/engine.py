@@ -205,6 +205,11 @@ def sw_ring_deg_supported(p, W):
     return bool(lib().scldpc_sw_bp_ring_deg_supported(C.byref(p), int(W)))
 
 
+def swc_ring_supported(p, W):
+    """Whether scldpc_swc_bp_ring_device takes the classical window W on this ensemble: the pairs (3,6), (4,8) and (5,10)."""
+    return bool(lib().scldpc_swc_bp_ring_supported(C.byref(p), int(W)))
+
+
 def sock16_supported(p):
     """The (4,8) chain with N <= 2048: the second-generation sampler emits the ring window decoder's CN -> socket table."""
     return bool(lib().scldpc_sample_philox_sock16_supported(C.byref(p)))
@@ -433,11 +438,16 @@ def sw_bp(p, d_adj, d_chan, W, max_it, init_it=0, want_erased=False, counters=No
     classical window kept in BPF:627-897 (init_it unused).  ring: None = use the window-state-in-LDS kernel (sw_ring.hip)
     whenever it takes the ensemble (square window, 2-byte tables; the CN -> socket table is built on the fly unless
     d_cn_sock is given), False = the whole-chain kernel, True = insist on the ring kernel.  deg=True: the ring decision and the
-    launch go through scldpc_sw_bp_ring_deg_supported / scldpc_sw_bp_ring_device_deg, which take the pairs (3,6) and (5,10) too."""
+    launch go through scldpc_sw_bp_ring_deg_supported / scldpc_sw_bp_ring_device_deg, which take the pairs (3,6) and (5,10) too.
+    classical=True takes the ring kernel (scldpc_swc_bp_ring_device, all three pairs) only with ring=True."""
     _require_gpu()
     T = d_adj.shape[0]
     use_ring = ring
-    if ring is None or ring:
+    if classical:
+        use_ring = bool(ring)
+        if use_ring and not _is_adj16(d_adj):
+            raise ScldpcError("the classical ring window kernel takes 2-byte tables only")
+    elif ring is None or ring:
         supported = lib().scldpc_sw_bp_ring_deg_supported if deg else lib().scldpc_sw_bp_ring_supported
         ok = (not classical) and _is_adj16(d_adj) and bool(supported(C.byref(p), int(W)))
         if ring and not ok:
@@ -453,6 +463,13 @@ def sw_bp(p, d_adj, d_chan, W, max_it, init_it=0, want_erased=False, counters=No
     erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
     head = (C.byref(p), T, d_adj.data_ptr())
     tail = (counters.data_ptr(), erased.data_ptr() if erased is not None else None)
+    if use_ring and classical:
+        fn = lib().scldpc_swc_bp_ring_device
+        check(fn(C.byref(p), 0, None, None, None, int(W), int(max_it), None, None, None))    # a refusal names its limit before any device work
+        if d_cn_sock is None:
+            d_cn_sock = cn_sockets(p, d_adj)
+        check(fn(*head, d_cn_sock.data_ptr(), d_chan.data_ptr(), int(W), int(max_it), *tail, _stream_ptr(dev)))
+        return {"counters": counters, "erased": erased}
     if use_ring:
         if d_cn_sock is None:
             d_cn_sock = cn_sockets(p, d_adj)

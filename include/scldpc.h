@@ -341,6 +341,15 @@ int scldpc_swc_bp_device_adj16(const scldpc_code_params *p, int32_t ntrials,
                                const uint16_t *d_vn_adj16, const uint32_t *d_chan_bits,
                                int32_t W, int32_t max_it,
                                int32_t *d_counters, uint32_t *d_erased_bits, void *d_workspace, uint64_t workspace_bytes, void *stream);
+/* The classical window with only the window's state on chip (sw_ring.hip's classical instances): a ring of W + 3dv - 2 CN
+ * positions and W + 2dv - 1 VN positions in LDS, no workspace; counters and erased bits of scldpc_swc_bp_device_adj16 bit
+ * for bit.  The pairs (3,6), (4,8) and (5,10); tables as scldpc_sw_bp_ring_device_deg.  scldpc_swc_bp_ring_supported: 1 if
+ * (p, W) is taken — the limits of scldpc_sw_bp_ring_deg_supported with the larger ring's state against the CU's 160 KiB;
+ * otherwise SCLDPC_ERR_TOO_LARGE names the limit. */
+int scldpc_swc_bp_ring_supported(const scldpc_code_params *p, int32_t W);
+int scldpc_swc_bp_ring_device(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                              const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t W, int32_t max_it,
+                              int32_t *d_counters, uint32_t *d_erased_bits, void *stream);
 
 /* Compact adjacency variants.  d_vn_adj16 is uint16 [ntrials][n][dv]: the CN index LOCAL to its position
  * (0 .. cns_pos-1).  Edge i of a VN at position pos always lands in CN position pos+i (BPF:1712), so the
