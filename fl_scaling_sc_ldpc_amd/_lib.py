@@ -53,6 +53,7 @@ EXPORTS = (
     "scldpc_sw_bp_ring_deg_supported", "scldpc_sw_bp_ring_device_deg",
     "scldpc_stream_supported",
     "scldpc_swc_bp_ring_supported", "scldpc_swc_bp_ring_device",
+    "scldpc_sample_philox_adj16_sock_supported", "scldpc_sample_philox_device_adj16_sock",
 )
 
 
@@ -122,6 +123,8 @@ def lib():
     L.scldpc_sample_philox_device_cn16.argtypes = [pp, u64, u64, i32, dbl, i32, vp, vp, vp, vp, vp]
     L.scldpc_sample_philox_sock16_supported.argtypes = [pp]
     L.scldpc_sample_philox_device_sock16.argtypes = [pp, u64, u64, i32, dbl, i32, vp, vp, vp, vp, vp]
+    L.scldpc_sample_philox_adj16_sock_supported.argtypes = [pp]
+    L.scldpc_sample_philox_device_adj16_sock.argtypes = [pp, u64, u64, i32, dbl, i32, vp, vp, vp, vp, vp, u64, vp]
     L.scldpc_full_bp_fixpoint_device_cn16.argtypes = [pp, i32, vp, vp, vp, i32, vp, vp, vp]
     L.scldpc_full_bp_device_cn16.argtypes = [pp, i32, vp, vp, vp, i32, i32, vp, vp, vp]
     L.scldpc_full_bp_sock16_supported.argtypes = [pp]

@@ -39,6 +39,9 @@ more than 65536 CNs (engine.full_bp_caps_wide) and to the pairs (3,6) and (5,10)
 MAX_IT iterations per window, the file name and rows of `bp_lim_iter`.  `--ring on|off|auto` picks the ring window decoder or
 the whole-chain kernel; both write the same file.
 
+`--sampled-table on|off|auto` (bp_lim_iter, bp_traj, sw_lim_iter): where the first-generation sampler is followed by a pass that
+builds the decoder's CN -> socket table, the sampler writes that table in its own launch (engine.sample_philox_sock); same files.
+
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
@@ -162,11 +165,17 @@ CLASSICAL_RING_BY_DEFAULT = False
 # The (4,8) forms of at most 65536 CNs fuse without this switch.
 CAPS_FORMS_BY_DEFAULT = False
 
+# Whether Simulator(sampled_table=None) lets the first-generation sampler write the CN -> socket table with the code
+# (engine.sample_philox_sock) wherever a path would run the cn_sockets pass after it, or leaves the table to engine.sw_bp
+# (tools/sampled_table_speedup.py, profiles/sampled_table_speedup.json).  Same tables as a set per CN, same files.
+SAMPLED_TABLE_BY_DEFAULT = False
+
 
 # The path of a Simulator, decided once in Simulator._select:
 #   adj_dtype    VN -> CN table: torch.int16 (position-local ids) or torch.int32 (the reference's VNdegree)
-#   sampler      what fills a batch: "glibc" (host replay), "first" (first-generation sampler), "cn16" / "sock16" (second
-#                generation, with the CN -> VN / CN -> socket table)
+#   sampler      what fills a batch: "glibc" (host replay), "first" (first-generation sampler), "first_sock" (the same with the
+#                CN -> socket table from its own launch), "cn16" / "sock16" (second generation, with the CN -> VN / CN -> socket
+#                table)
 #   cn_table     the CN table kept next to the VN -> CN one: None, "vn" or "sock"
 #   cn_pass      that table comes from the cn_sockets pass (the sampler does not emit it)
 #   decoder      "sw_ring" / "sw_chain" (E.sw_bp; "sw_ring" with cn_pass: the _deg entry points, pairs (3,6) and (5,10)),
@@ -189,7 +198,7 @@ class Simulator:
 
     def __init__(self, p, decoder="full", W=0, max_it=0, init_it=0, is_term=True, doped=(), batch=2048,
                  rng="philox", seed=1, device=None, rows_cap=0, schedule="flooding", shard_frames=True, index=0,
-                 verbose=False, caps=None, wide=None, deg=None, ring=None, fused_caps=None):
+                 verbose=False, caps=None, wide=None, deg=None, ring=None, fused_caps=None, sampled_table=None):
         # wide: the 1024-thread 4-bit level decoder for trials of more than 65536 CNs (full_bp_small wide).  None = where
         # WIDE_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path, for A/B and tests)
         self.want_wide = wide
@@ -203,6 +212,9 @@ class Simulator:
         # fused_caps: with caps, the cap checkpoints of the wide form and of the pairs (3,6) and (5,10).  None = where
         # CAPS_FORMS_BY_DEFAULT says, True = wherever an instance applies (wide=False / deg=False veto their family), False = never
         self.want_fused_caps = fused_caps
+        # sampled_table: the CN -> socket table from the first-generation sampler's own launch instead of the cn_sockets pass.
+        # None = where SAMPLED_TABLE_BY_DEFAULT says, True = wherever it applies, False = never
+        self.want_sampled_table = sampled_table
         self.p, self.decoder, self.W, self.max_it, self.init_it = p, decoder, W, max_it, init_it
         # caps: several MaxNumIt from one decode (run_point_caps; the level-synchronous 4-bit decoder only)
         self.caps = E.check_caps(caps) if caps is not None else None
@@ -299,11 +311,16 @@ class Simulator:
             else:
                 self.path = Path(adj_dtype, first, None, False, "full_bp", fix)
         path = self.path
+        self.ring_deg = path.decoder == "sw_ring" and path.cn_pass       # (the _deg entry points: decided where the table's pass is)
+        # the table of a path that runs the cn_sockets pass after the first-generation sampler, or leaves it to E.sw_bp, from the
+        # sampler's own launch instead (opt-in)
+        self.sampled_table_reason = sampled_table_reason(p, self.rng, path, self.want_sampled_table)
+        if self.sampled_table_reason is None:
+            path = self.path = path._replace(sampler="first_sock", cn_table="sock", cn_pass=False)
         # the path as the flags it used to be kept in
         self.gen2, self.lvl2, self.wide = path.fix_decoder == "fixpoint16", path.decoder == "level16", path.decoder == "wide"
         self.sock = (self.gen2 or self.lvl2) and path.cn_table == "sock"
         self.ring2 = path.decoder == "sw_ring" and path.cn_table == "sock"
-        self.ring_deg = path.decoder == "sw_ring" and path.cn_pass
         self.wide_sock = self.wide and not path.cn_pass
         self.deg = path.decoder in ("deg16", "degwide")
         fused_form = self.caps is not None and path.decoder in ("wide", "deg16", "degwide")      # reached through _caps_form only
@@ -351,6 +368,9 @@ class Simulator:
     def kernel_choice(self):
         """Which device kernels this configuration runs."""
         path = self.path
+        if path.decoder == "sw_ring" and path.sampler == "first_sock":
+            return ("sampler (first generation, CN->socket table) + sw_ring (window state in LDS"
+                    + (", dv = %d, dc = %d)" % (self.p.dv, self.p.dc) if self.ring_deg else ")"))
         if path.decoder == "sw_ring" and path.cn_pass:
             return ("sampler (first generation) + cn_sockets pass + sw_ring (window state in LDS, dv = %d, dc = %d)"
                     % (self.p.dv, self.p.dc))
@@ -359,7 +379,8 @@ class Simulator:
                     "sampler (first generation) + sw_ring + cn_sockets pass")
         if path.decoder == "sw_chain":
             return "sampler (first generation) + sw_bp (whole chain)"
-        samp = {"glibc": "glibc replay on the host", "first": "sampler (first generation)", "cn16": "sampler_v3 (CN->VN table)",
+        samp = {"glibc": "glibc replay on the host", "first": "sampler (first generation)",
+                "first_sock": "sampler (first generation, CN->socket table)", "cn16": "sampler_v3 (CN->VN table)",
                 "sock16": "sampler_v3 (CN->socket table)"}[path.sampler] + (" + cn_sockets pass" if path.cn_pass else "")
         if path.decoder == "swc_ring":
             return samp + " + sw_ring classical window (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc)
@@ -452,6 +473,9 @@ class Simulator:
                             out=(self.d_adj[:nb], self.d_ch[:nb]))
             if path.cn_pass:                       # more sockets per position than the second-generation sampler takes
                 E.cn_sockets(self.p, self.d_adj[:nb], out=self.d_cn[:nb])
+        elif path.sampler == "first_sock":
+            E.sample_philox_sock(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
+                                 out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
         else:
             sample = E.sample_philox_cn16 if path.sampler == "cn16" else E.sample_philox_sock16
             sample(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
@@ -576,6 +600,27 @@ class Simulator:
             frame0 += R
         bad = bad.cpu().tolist()
         return [PointResult(eps, p.n, p.L, runs[k].cpu().numpy(), bad=bad[k]) for k in range(K)]
+
+
+def sampled_table_reason(p, rng, path, want=True):
+    """Why a configuration whose path (before this switch) is `path` does not take the CN -> socket table from the
+    first-generation sampler's own launch, or None where it does.  want: the Simulator's sampled_table argument (None:
+    SAMPLED_TABLE_BY_DEFAULT)."""
+    if not (SAMPLED_TABLE_BY_DEFAULT if want is None else bool(want)):
+        return "switched off"
+    if rng != "philox":
+        return "--rng %s samples the code on the host" % rng
+    if path.sampler in ("cn16", "sock16"):
+        return "the second-generation sampler takes this ensemble and writes the CN table with the code already"
+    # what runs the cn_sockets pass after the first-generation sampler, and the (4,8) ring whose table E.sw_bp builds per call
+    if not (path.sampler == "first" and path.adj_dtype == torch.int16
+            and (path.cn_pass or (path.decoder == "sw_ring" and path.cn_table is None))):
+        return "the decoder of this configuration (%s) reads no CN -> socket table" % path.decoder
+    if not E.sample_philox_sock_supported(p):
+        return ("the first-generation sampler writes the table for vns_pos * dv <= 65535, cns_pos <= 65536 and, beyond 8192 "
+                "sockets per position, dc <= 255 and cns_pos <= 32768 (dv = %d, dc = %d, L = %d, N = %d)"
+                % (p.dv, p.dc, p.L, p.vns_pos))
+    return None
 
 
 def ring_deg_reason(p, W, rng, want=True):
@@ -708,7 +753,8 @@ def _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, sh
     sim_obj = Simulator(p, decoder="full", W=W, max_it=caps[-1], is_term=True, doped=doped, batch=opts.batch, rng=opts.rng,
                         seed=opts.seed, schedule="flooding", shard_frames=shard == "frames",
                         device=getattr(opts, "device", None), index=index, verbose=verbose, caps=caps, wide=wide, deg=deg,
-                        fused_caps=fused)
+                        fused_caps=fused, sampled_table=switch[getattr(opts, "sampled_table", "auto")])
+    _check_sampled_table(opts, sim_obj)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     paths = {v: os.path.join(outdir, result_filename(prog, p, W, v, 0, index)) for v in file_its}
@@ -861,7 +907,9 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                         verbose=rank == 0 and not opts.quiet,
                         wide={"auto": None, "on": True, "off": False}[getattr(opts, "wide", "auto")],
                         deg={"auto": None, "on": True, "off": False}[getattr(opts, "deg", "auto")],
-                        ring=ring if decoder in ("sw", "swc") else None)
+                        ring=ring if decoder in ("sw", "swc") else None,
+                        sampled_table={"auto": None, "on": True, "off": False}[getattr(opts, "sampled_table", "auto")])
+    _check_sampled_table(opts, sim_obj)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     t0 = time.time()
@@ -930,6 +978,12 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                 abort_invariant()
         report(eps, point)
     return 0
+
+
+def _check_sampled_table(opts, sim_obj):
+    """--sampled-table on where the sampler cannot write the table: exits with the reason."""
+    if getattr(opts, "sampled_table", "auto") == "on" and sim_obj.sampled_table_reason is not None:
+        raise SystemExit("--sampled-table on: " + sim_obj.sampled_table_reason)
 
 
 def _check_window(opts):
@@ -1011,6 +1065,10 @@ def _parser(prog):
                         help="--window classical with --dv/--dc 3/6, 4/8 or 5/10: the ring window decoder (on), the whole-chain "
                              "kernel (off), or the measured default (auto); same files.  'on' where the ring cannot apply is an "
                              "error that names the limit")
+    ap.add_argument("--sampled-table", choices=("auto", "on", "off"), default="auto",
+                    help="where the first-generation sampler is followed by a pass that builds the CN -> socket table: the sampler "
+                         "writes the table itself (on), the separate pass (off), or the measured default (auto); same files.  "
+                         "'on' where no such pass runs is an error that says why")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")

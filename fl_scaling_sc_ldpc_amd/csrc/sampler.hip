@@ -42,6 +42,8 @@ struct SArgs {
     int32_t *vn_adj;            // int32 [T][n][dv]  (or)
     uint16_t *vn_adj16;         // uint16 [T][n][dv], CN index local to its position
     uint32_t *chan;
+    uint16_t *cn_sock16;        // table mode: uint16 [T][nk][dc], the sockets of every CN (0xFFFF: its VN position is off the chain)
+    int nk, tab32;              // tab32: the fused big kernel copies a position's S entries as 32-bit words (S even, 4-byte aligned table)
 };
 
 using scldpc_dev::philox4x32_10;
@@ -61,9 +63,16 @@ using scldpc_dev::wave_inclusive_scan;
 // Two of these 1024-thread workgroups share a CU only if a wave's SGPR allocation lets 8 waves sit on a SIMD: the 800-entry
 // scalar file admits ⌊800 / (⌈sgpr/16⌉·16 + 16)⌋ waves, i.e. at most 80 SGPRs per wave.  Left alone the compiler takes 106
 // (one workgroup per CU, half the throughput); capped, the few extra uniforms live in VGPR lanes.
-template <int KMAX, int ROWS, bool ADJ16, int ENS, bool FINE>
+// TABLE (Olmos chain, 2-byte rows): the CN -> socket table goes out with the code.  A thread holds the rank of each of its
+// sockets when it writes the socket -> CN row, and rank r of CN position p IS entry r of that position's S table entries
+// (CN r / dc, place r % dc): socket s there, or 0xFFFF where its VN position p - s % dv is off the chain.  The entries are stored
+// straight to the table, 2 bytes each.  (Scattered into the room of gkey behind one more barrier and copied out as whole lines
+// they cost the one-call instances 70 VGPRs for 54, i.e. one workgroup per CU for two: 2.38 against 1.78 ms per 2048 trials at
+// (3,6), N = 1000, and within 4 % either way for the two-call instance — DESIGN.md §7.)
+template <int KMAX, int ROWS, bool ADJ16, int ENS, bool FINE, bool TABLE = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(72))) void sample_philox_kernel(const SArgs a)
 {
+    static_assert(!TABLE || (ADJ16 && ENS == 0), "the table mode serves the Olmos chain with 2-byte rows");
     extern __shared__ uint32_t lds[];
     uint32_t *hist = lds;                                           // nb counters → per-slice exclusive prefix
     uint32_t *gkey = lds + a.off_gkey;                              // S keys grouped by bucket
@@ -225,6 +234,18 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(72))) void
                             rank[e] += gidx[g0s[e] + step] < (uint16_t)((tid + (e >> 2) * kThreads) * 4 + (e & 3));
                 }
             }
+            if (TABLE) {
+                uint16_t *tdst = a.cn_sock16 + ((size_t)blockIdx.x * a.nk + (size_t)p * a.cns_pos) * a.dc;
+                const bool ends = p < dv - 1 || p >= a.L;           // some VN position p - i is off the chain
+#pragma unroll
+                for (int e = 0; e < E; e++) {
+                    const int q = tid + (e >> 2) * kThreads, sck = q * 4 + (e & 3);
+                    if (q < ncalls && sck < S && rank[e] < (uint32_t)S) {
+                        const bool off = ends && (unsigned)(p - sck % dv) >= (unsigned)a.L;
+                        tdst[rank[e]] = off ? (uint16_t)0xFFFFu : (uint16_t)sck;
+                    }
+                }
+            }
 #pragma unroll
             for (int k = 0; k < KMAX; k++) {
                 const int q = tid + k * kThreads, s0 = q * 4;
@@ -321,9 +342,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(72))) void
 // (Philox is pure VALU).  Only the keys of straddling buckets (stream_bp.hip's fallback has the same ranking) and the ring of dv
 // permutations live in a per-trial slice of the caller's workspace (L2-resident): the straddlers are ranked from a dense
 // worklist, one trip to the L2 per lane, not one per key and wave.
-template <int ROWS, bool ADJ16, bool FUSED>
-__global__ __launch_bounds__(kThreads, FUSED ? 4 : 8) __attribute__((amdgpu_num_sgpr(72))) void sample_philox_big_kernel(const SArgs a, char *ws, size_t ws_stride)
+// TABLE (2-byte rows): the CN -> socket table goes out with the code.  The fused ranking's stage IS a position's table entries
+// in rank order; after the two rankings without a stage the entries are built from the finished socket -> CN row (table_from_row).
+// The table-mode instance without the fused ranking needs 68 VGPRs where its twin spills two into scratch to keep 64: it is
+// built for one workgroup per CU (no scratch) where the twin runs two.
+template <int ROWS, bool ADJ16, bool FUSED, bool TABLE = false>
+__global__ __launch_bounds__(kThreads, (FUSED || TABLE) ? 4 : 8) __attribute__((amdgpu_num_sgpr(72))) void sample_philox_big_kernel(const SArgs a, char *ws, size_t ws_stride)
 {
+    static_assert(!TABLE || ADJ16, "the table mode serves 2-byte rows");
     extern __shared__ uint32_t lds[];
     uint32_t *hist = lds;                                               // nb / 2 words
     uint32_t *wsum = lds + a.off_wsum;                                  // 16 wave totals, [16] = worklist length
@@ -672,6 +698,21 @@ __global__ __launch_bounds__(kThreads, FUSED ? 4 : 8) __attribute__((amdgpu_num_
         }
         __syncthreads();
         if (wsum[kWaves + 1]) { __syncthreads(); return false; }
+        if constexpr (TABLE) {  // stage[r] = the socket at rank r = entry r of CN position p's table entries: out as whole lines
+            uint16_t *trow = a.cn_sock16 + ((size_t)blockIdx.x * a.nk + (size_t)p * a.cns_pos) * a.dc;
+            const bool ends = p < dv - 1 || p >= a.L;               // some VN position p - i is off the chain
+            auto entry = [&](uint32_t s) { return ends && (unsigned)(p - (int)(s % (uint32_t)dv)) >= (unsigned)a.L ? 0xFFFFu : s; };
+            if (a.tab32) {
+                uint32_t *d32 = reinterpret_cast<uint32_t *>(trow);
+                const uint32_t *s32 = reinterpret_cast<const uint32_t *>(stage);
+                for (int w = tid; w < S / 2; w += kThreads) {
+                    const uint32_t v = s32[w];
+                    d32[w] = entry(v & 0xFFFFu) | (entry(v >> 16) << 16);
+                }
+            } else {
+                for (int r = tid; r < S; r += kThreads) trow[r] = (uint16_t)entry(stage[r]);
+            }
+        }
         // the socket -> CN row (by edge: tp) = the inverse of the stage, half a row at a time over the counters, out as whole lines
         uint16_t *irow = reinterpret_cast<uint16_t *>(hist);
         uint16_t *wp = win + (size_t)(p % dv) * S;
@@ -695,10 +736,31 @@ __global__ __launch_bounds__(kThreads, FUSED ? 4 : 8) __attribute__((amdgpu_num_
         return true;
     };
 
+    // Table mode after rank_nib / rank_wide (no stage; the fused form reaches rank_wide never on real draws): CN position p's table
+    // entries from its finished socket -> CN row, the place within a CN from a fill counter per CN — bytes, four to a word, over
+    // the ranking's counters (dead; at most 32768 CNs per position in the 8192 words every form has).  Every CN of the row holds
+    // exactly dc sockets, so every entry is written; a row that broke that would lose entries, not write outside its CN.
+    auto table_from_row = [&](int p) {
+        const uint32_t C = (uint32_t)a.cns_pos, dc = (uint32_t)a.dc;
+        for (uint32_t b = tid; b < (C + 3u) / 4u; b += kThreads) hist[b] = 0;
+        __syncthreads();
+        const uint16_t *wp = win + (size_t)(p % dv) * S;
+        uint16_t *trow = a.cn_sock16 + ((size_t)blockIdx.x * a.nk + (size_t)p * a.cns_pos) * a.dc;
+        for (uint32_t s = tid; s < (uint32_t)S; s += kThreads) {
+            const uint32_t c = wp[tp(s)];
+            if (c >= C) continue;
+            const uint32_t sh = (c & 3u) * 8u, place = (atomicAdd(&hist[c >> 2], 1u << sh) >> sh) & 0xFFu;
+            const bool off = (unsigned)(p - (int)(s % (uint32_t)dv)) >= (unsigned)a.L;
+            if (place < dc) trow[c * dc + place] = off ? (uint16_t)0xFFFFu : (uint16_t)s;
+        }
+        __syncthreads();
+    };
+
     for (int p = 0; p < a.D; p++) {
         bool ranked;
         if constexpr (FUSED) ranked = rank_fused(p); else ranked = rank_nib(p);
         if (!ranked) rank_wide(p);
+        if constexpr (TABLE) { if (!FUSED || !ranked) table_from_row(p); }
         const int qpos = p - (dv - 1);
         if (qpos >= 0) {
             for (int t = tid; t < a.vns_pos; t += kThreads) {
@@ -744,11 +806,11 @@ __global__ __launch_bounds__(kThreads, FUSED ? 4 : 8) __attribute__((amdgpu_num_
 template <bool ADJ16>
 int launch(const scldpc_code_params *p, int ensemble, uint64_t seed, uint64_t trial0, int32_t ntrials, double eps,
            int32_t ndoped, const int32_t *doped_positions, void *d_adj, uint32_t *d_chan_bits,
-           const scldpc::Scratch &scratch, void *stream, const char *who)
+           const scldpc::Scratch &scratch, void *stream, const char *who, bool table = false, uint16_t *d_cn_sock16 = nullptr)
 {
     if (int rc = scldpc::check_params(p)) return rc;
     if (scratch.query) *scratch.query = 0;
-    if (!scratch.query && (ntrials < 0 || (ntrials > 0 && (!d_adj || !d_chan_bits))))
+    if (!scratch.query && (ntrials < 0 || (ntrials > 0 && (!d_adj || !d_chan_bits || (table && !d_cn_sock16)))))
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
     if (ndoped < 0 || ndoped > kMaxDoped || (ndoped > 0 && !doped_positions))
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: 0 <= ndoped <= %d", who, kMaxDoped);
@@ -821,6 +883,9 @@ int launch(const scldpc_code_params *p, int ensemble, uint64_t seed, uint64_t tr
     a.vn_adj = ADJ16 ? nullptr : static_cast<int32_t *>(d_adj);
     a.vn_adj16 = ADJ16 ? static_cast<uint16_t *>(d_adj) : nullptr;
     a.chan = d_chan_bits;
+    a.cn_sock16 = table ? d_cn_sock16 : nullptr;
+    a.nk = scldpc::nk_of(p);
+    a.tab32 = (a.S & 1) == 0 && (reinterpret_cast<uintptr_t>(d_cn_sock16) & 3u) == 0;
 
     if (big) {
         const size_t stride = (((size_t)a.S * (16 + 2 * p->dv)) + 255) & ~(size_t)255;
@@ -829,6 +894,10 @@ int launch(const scldpc_code_params *p, int ensemble, uint64_t seed, uint64_t tr
         if (int rc = scldpc::take_scratch(who, scratch, stride * (size_t)ntrials, &ws)) return rc;
         void (*kb)(const SArgs, char *, size_t) = a.fused ? (a.nb == 16384 ? sample_philox_big_kernel<16, ADJ16, true> : sample_philox_big_kernel<8, ADJ16, true>)
                                                           : (a.nb == 16384 ? sample_philox_big_kernel<16, ADJ16, false> : sample_philox_big_kernel<8, ADJ16, false>);
+        if constexpr (ADJ16) {
+            if (table) kb = a.fused ? (a.nb == 16384 ? sample_philox_big_kernel<16, true, true, true> : sample_philox_big_kernel<8, true, true, true>)
+                                    : (a.nb == 16384 ? sample_philox_big_kernel<16, true, false, true> : sample_philox_big_kernel<8, true, false, true>);
+        }
         if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kb))) return rc_;
         hipLaunchKernelGGL(kb, dim3(ntrials), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), a,
                            static_cast<char *>(ws), stride);
@@ -850,6 +919,15 @@ int launch(const scldpc_code_params *p, int ensemble, uint64_t seed, uint64_t tr
                                                                                                 : sample_philox_kernel<1, 4, ADJ16, 0, true>;
         else           kern = sample_philox_kernel<2, 8, ADJ16, 0, true>;
         if (kmax == 1 && rows > 4) kern = sample_philox_kernel<2, 8, ADJ16, 0, true>;
+    }
+    if constexpr (ADJ16) {
+        if (table && ensemble == SCLDPC_ENS_OLMOS) {
+            const int form = kmax == 1 && rows <= 4 ? (rows == 1 ? 0 : rows == 2 ? 1 : 2) : 3;
+            static void (*const with_table[4])(const SArgs) = {
+                sample_philox_kernel<1, 1, true, 0, true, true>, sample_philox_kernel<1, 2, true, 0, true, true>,
+                sample_philox_kernel<1, 4, true, 0, true, true>, sample_philox_kernel<2, 8, true, 0, true, true>};
+            kern = with_table[form];
+        }
     }
     if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
     hipLaunchKernelGGL(kern, dim3(ntrials), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), a);
@@ -876,6 +954,46 @@ extern "C" int scldpc_sample_philox_device_adj16(const scldpc_code_params *p, ui
 {
     return launch<true>(p, SCLDPC_ENS_OLMOS, seed, trial0, ntrials, eps, ndoped, doped_positions, d_vn_adj16, d_chan_bits,
                         scldpc::Scratch{d_workspace, workspace_bytes, nullptr}, stream, "scldpc_sample_philox_device_adj16");
+}
+
+// Which limit keeps ensemble p from scldpc_sample_philox_device_adj16_sock beyond those of scldpc_sample_philox_device_adj16;
+// nullptr: none
+static const char *adj16_sock_limit(const scldpc_code_params *p)
+{
+    if ((int64_t)p->vns_pos * p->dv > 65535) return "sockets: vns_pos * dv must fit 16 bits with 0xFFFF free (at most 65535)";
+    if (p->cns_pos > 65536) return "at most 65536 CNs per position (16-bit position-local CN ids)";
+    // beyond 8192 sockets per position the rankings without a stage count a CN's table entries in a byte, four CNs to a word of
+    // the 8192 counter words every form has
+    if ((int64_t)p->cns_pos * p->dc > 8192 && (p->dc > 255 || p->cns_pos > 32768))
+        return "beyond 8192 sockets per position: dc <= 255 and at most 32768 CNs per position";
+    return nullptr;
+}
+
+// 1 when scldpc_sample_philox_device_adj16_sock takes this ensemble: scldpc_sample_philox_device_adj16 does, and the sockets
+// and CN ids fit the table's 16 bits
+extern "C" int scldpc_sample_philox_adj16_sock_supported(const scldpc_code_params *p)
+{
+    if (scldpc::check_params(p) || adj16_sock_limit(p)) return 0;
+    uint64_t need = 0;
+    return launch<true>(p, SCLDPC_ENS_OLMOS, 0, 0, 1, 0.5, 0, nullptr, nullptr, nullptr, scldpc::Scratch{nullptr, 0, &need}, nullptr,
+                        "scldpc_sample_philox_adj16_sock_supported") == SCLDPC_OK;
+}
+
+// scldpc_sample_philox_device_adj16 with the CN -> socket table of the code written by the same launch: rows and channel bit for
+// bit the table-less launch's, the table what scldpc_cn_sockets_device builds from the rows (as a set per CN)
+extern "C" int scldpc_sample_philox_device_adj16_sock(const scldpc_code_params *p, uint64_t seed, uint64_t trial0,
+                                                      int32_t ntrials, double eps, int32_t ndoped,
+                                                      const int32_t *doped_positions, uint16_t *d_vn_adj16,
+                                                      uint16_t *d_cn_sock16, uint32_t *d_chan_bits, void *d_workspace,
+                                                      uint64_t workspace_bytes, void *stream)
+{
+    const char *who = "scldpc_sample_philox_device_adj16_sock";
+    if (int rc = scldpc::check_params(p)) return rc;
+    if (const char *limit = adj16_sock_limit(p))
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s (got dv=%d dc=%d cns_pos=%d vns_pos=%d)", who, limit, p->dv, p->dc,
+                                 p->cns_pos, p->vns_pos);
+    return launch<true>(p, SCLDPC_ENS_OLMOS, seed, trial0, ntrials, eps, ndoped, doped_positions, d_vn_adj16, d_chan_bits,
+                        scldpc::Scratch{d_workspace, workspace_bytes, nullptr}, stream, who, true, d_cn_sock16);
 }
 
 extern "C" int scldpc_sample_philox_ensemble_device(const scldpc_code_params *p, int32_t ensemble, uint64_t seed,

@@ -221,6 +221,30 @@ def sample_philox_sock16(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0
     return _sample_philox_tables(lib().scldpc_sample_philox_device_sock16, p, seed, trial0, ntrials, eps, doped, device, out)
 
 
+def sample_philox_sock_supported(p):
+    """Whether the first-generation sampler writes the CN -> socket table with the code on this ensemble (sample_philox_sock)."""
+    return bool(lib().scldpc_sample_philox_adj16_sock_supported(C.byref(p)))
+
+
+def sample_philox_sock(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0", out=None):
+    """scldpc_sample_philox_device_adj16_sock: (vn_adj16 int16 [T,n,dv], cn_sock16 int16 [T,nk,dc], chan int32 [T,nw]); the first
+    and the last are bit for bit sample_philox(..., adj16=True)'s, cn_sock16 is cn_sockets(p, vn_adj16) as a set per CN — from
+    the sampler's own launch, for every ensemble sample_philox takes with 16-bit sockets."""
+    _require_gpu()
+    if out is None:
+        d_adj = torch.empty((ntrials, p.n, p.dv), dtype=torch.int16, device=device)
+        d_cn = torch.empty((ntrials, p.nk, p.dc), dtype=torch.int16, device=device)
+        d_ch = torch.empty((ntrials, p.nw), dtype=torch.int32, device=device)
+    else:
+        d_adj, d_cn, d_ch = out
+    darr, dptr = _lib.doped_array(doped)
+    ws, wsb, _keep = _workspace(WS_SAMPLE, p, ntrials, d_adj.device)
+    check(lib().scldpc_sample_philox_device_adj16_sock(C.byref(p), int(seed), int(trial0), int(ntrials), float(eps), darr.size, dptr,
+                                                       d_adj.data_ptr(), d_cn.data_ptr(), d_ch.data_ptr(), ws, wsb,
+                                                       _stream_ptr(d_adj.device)))
+    return d_adj, d_cn, d_ch
+
+
 def cn_adj_from_vn_adj(p, adj16):
     """Host: the CN -> VN table (uint16 [.., nk, dc] as int16 bit patterns: the VNs of every CN in ascending order,
     0xFFFF where a chain-end CN has fewer than dc) from the position-local VN -> CN table — for feeding host-sampled

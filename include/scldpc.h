@@ -196,6 +196,20 @@ int scldpc_sample_philox_device_sock16(const scldpc_code_params *p, uint64_t see
 int scldpc_sample_philox_device_cn16(const scldpc_code_params *p, uint64_t seed, uint64_t trial0, int32_t ntrials,
                                      double eps, int32_t ndoped, const int32_t *doped_positions, uint16_t *d_vn_adj16,
                                      uint16_t *d_cn_adj16, uint32_t *d_chan_bits, void *stream);
+/* scldpc_sample_philox_device_adj16 (the first-generation sampler: any dv <= 8, up to 65536 sockets per position) writing the
+ * CN -> socket table of its code in the same launch: d_cn_sock16 uint16 [ntrials][nk][dc], the contents
+ * scldpc_sample_philox_device_sock16 writes and scldpc_cn_sockets_device builds from the rows in a second pass (socket
+ * s = dv*t + i of CN position p is edge i of VN t of position p - i; 0xFFFF where that position is off the chain; order within
+ * a CN unspecified).  d_vn_adj16 and d_chan_bits are bit for bit those of scldpc_sample_philox_device_adj16 with the same key;
+ * arguments, checks, error codes and workspace (SCLDPC_WS_SAMPLE) are that entry point's.  *_supported: 1 where
+ * scldpc_sample_philox_device_adj16 takes the ensemble, vns_pos * dv <= 65535 (sockets in 16 bits with 0xFFFF free),
+ * cns_pos <= 65536 and, beyond 8192 sockets per position, dc <= 255 and cns_pos <= 32768; otherwise SCLDPC_ERR_TOO_LARGE names
+ * the limit. */
+int scldpc_sample_philox_adj16_sock_supported(const scldpc_code_params *p);
+int scldpc_sample_philox_device_adj16_sock(const scldpc_code_params *p, uint64_t seed, uint64_t trial0, int32_t ntrials,
+                                           double eps, int32_t ndoped, const int32_t *doped_positions, uint16_t *d_vn_adj16,
+                                           uint16_t *d_cn_sock16, uint32_t *d_chan_bits, void *d_workspace,
+                                           uint64_t workspace_bytes, void *stream);
 int scldpc_full_bp_cn16_supported(const scldpc_code_params *p);
 int scldpc_full_bp_fixpoint_device_cn16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                         const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t is_term,
