@@ -42,6 +42,10 @@ the whole-chain kernel; both write the same file.
 `--sampled-table on|off|auto` (bp_lim_iter, bp_traj, sw_lim_iter): where the first-generation sampler is followed by a pass that
 builds the decoder's CN -> socket table, the sampler writes that table in its own launch (engine.sample_philox_sock); same files.
 
+`--sampler2 on|off|auto` (bp_lim_iter, bp_traj, sw_lim_iter): with --dv/--dc 3/6 or 5/10 and at most 8192 sockets per position,
+the second-generation sampler of these pairs (engine.sample_philox_deg_sock16) draws the code and writes the CN -> socket table in
+one launch, instead of the first-generation sampler and its table pass; same files.
+
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
@@ -170,12 +174,20 @@ CAPS_FORMS_BY_DEFAULT = False
 # (tools/sampled_table_speedup.py, profiles/sampled_table_speedup.json).  Same tables as a set per CN, same files.
 SAMPLED_TABLE_BY_DEFAULT = False
 
+# Whether Simulator(sampler2=None) takes the second-generation sampler of the pairs (3,6) and (5,10) (engine.sample_philox_deg_sock16)
+# where it applies, instead of the first-generation sampler and the cn_sockets pass: True only if every repetition of the new path
+# beats every repetition of both old forms end to end on every shape of tools/sampler_deg_speedup.py, with equal outputs
+# (profiles/sampler_deg_speedup.json).  Same rows, channel and files; the same table as a set per CN.
+# Measured: the condition holds on all three shapes (1.24-1.32x end to end).  Kept False here because --deg, --ring, --caps-fused
+# and --sampled-table are specified, and tested, as starting from the first-generation sampler: the flip is a change of its own.
+SAMPLER2_DEG_BY_DEFAULT = False
+
 
 # The path of a Simulator, decided once in Simulator._select:
 #   adj_dtype    VN -> CN table: torch.int16 (position-local ids) or torch.int32 (the reference's VNdegree)
 #   sampler      what fills a batch: "glibc" (host replay), "first" (first-generation sampler), "first_sock" (the same with the
 #                CN -> socket table from its own launch), "cn16" / "sock16" (second generation, with the CN -> VN / CN -> socket
-#                table)
+#                table), "deg_sock16" (second generation of the pairs (3,6) and (5,10), with the CN -> socket table)
 #   cn_table     the CN table kept next to the VN -> CN one: None, "vn" or "sock"
 #   cn_pass      that table comes from the cn_sockets pass (the sampler does not emit it)
 #   decoder      "sw_ring" / "sw_chain" (E.sw_bp; "sw_ring" with cn_pass: the _deg entry points, pairs (3,6) and (5,10)),
@@ -198,7 +210,8 @@ class Simulator:
 
     def __init__(self, p, decoder="full", W=0, max_it=0, init_it=0, is_term=True, doped=(), batch=2048,
                  rng="philox", seed=1, device=None, rows_cap=0, schedule="flooding", shard_frames=True, index=0,
-                 verbose=False, caps=None, wide=None, deg=None, ring=None, fused_caps=None, sampled_table=None):
+                 verbose=False, caps=None, wide=None, deg=None, ring=None, fused_caps=None, sampled_table=None,
+                 sampler2=None):
         # wide: the 1024-thread 4-bit level decoder for trials of more than 65536 CNs (full_bp_small wide).  None = where
         # WIDE_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path, for A/B and tests)
         self.want_wide = wide
@@ -215,6 +228,9 @@ class Simulator:
         # sampled_table: the CN -> socket table from the first-generation sampler's own launch instead of the cn_sockets pass.
         # None = where SAMPLED_TABLE_BY_DEFAULT says, True = wherever it applies, False = never
         self.want_sampled_table = sampled_table
+        # sampler2: the second-generation sampler of the pairs (3,6) and (5,10) instead of the first-generation sampler and the
+        # cn_sockets pass.  None = where SAMPLER2_DEG_BY_DEFAULT says, True = wherever it applies, False = never
+        self.want_sampler2 = sampler2
         self.p, self.decoder, self.W, self.max_it, self.init_it = p, decoder, W, max_it, init_it
         # caps: several MaxNumIt from one decode (run_point_caps; the level-synchronous 4-bit decoder only)
         self.caps = E.check_caps(caps) if caps is not None else None
@@ -312,6 +328,12 @@ class Simulator:
                 self.path = Path(adj_dtype, first, None, False, "full_bp", fix)
         path = self.path
         self.ring_deg = path.decoder == "sw_ring" and path.cn_pass       # (the _deg entry points: decided where the table's pass is)
+        # the pairs (3,6) and (5,10): code and CN -> socket table from their second-generation sampler instead of the
+        # first-generation sampler and the cn_sockets pass (opt-in; decided before the next switch, which then finds no
+        # first-generation sampler to take the table from)
+        self.sampler2_deg_reason = sampler2_deg_reason(p, self.rng, path, self.want_sampler2)
+        if self.sampler2_deg_reason is None:
+            path = self.path = path._replace(sampler="deg_sock16", cn_table="sock", cn_pass=False)
         # the table of a path that runs the cn_sockets pass after the first-generation sampler, or leaves it to E.sw_bp, from the
         # sampler's own launch instead (opt-in)
         self.sampled_table_reason = sampled_table_reason(p, self.rng, path, self.want_sampled_table)
@@ -368,6 +390,9 @@ class Simulator:
     def kernel_choice(self):
         """Which device kernels this configuration runs."""
         path = self.path
+        samp2 = "sampler_v2 (dv = %d, dc = %d, CN->socket table)" % (self.p.dv, self.p.dc)
+        if path.decoder == "sw_ring" and path.sampler == "deg_sock16":
+            return samp2 + " + sw_ring (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc)
         if path.decoder == "sw_ring" and path.sampler == "first_sock":
             return ("sampler (first generation, CN->socket table) + sw_ring (window state in LDS"
                     + (", dv = %d, dc = %d)" % (self.p.dv, self.p.dc) if self.ring_deg else ")"))
@@ -381,7 +406,7 @@ class Simulator:
             return "sampler (first generation) + sw_bp (whole chain)"
         samp = {"glibc": "glibc replay on the host", "first": "sampler (first generation)",
                 "first_sock": "sampler (first generation, CN->socket table)", "cn16": "sampler_v3 (CN->VN table)",
-                "sock16": "sampler_v3 (CN->socket table)"}[path.sampler] + (" + cn_sockets pass" if path.cn_pass else "")
+                "sock16": "sampler_v3 (CN->socket table)", "deg_sock16": samp2}[path.sampler] + (" + cn_sockets pass" if path.cn_pass else "")
         if path.decoder == "swc_ring":
             return samp + " + sw_ring classical window (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc)
         if path.decoder == "swc_chain":
@@ -477,7 +502,8 @@ class Simulator:
             E.sample_philox_sock(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
                                  out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
         else:
-            sample = E.sample_philox_cn16 if path.sampler == "cn16" else E.sample_philox_sock16
+            sample = {"cn16": E.sample_philox_cn16, "sock16": E.sample_philox_sock16,
+                      "deg_sock16": E.sample_philox_deg_sock16}[path.sampler]
             sample(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
                    out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
 
@@ -610,7 +636,7 @@ def sampled_table_reason(p, rng, path, want=True):
         return "switched off"
     if rng != "philox":
         return "--rng %s samples the code on the host" % rng
-    if path.sampler in ("cn16", "sock16"):
+    if path.sampler in ("cn16", "sock16", "deg_sock16"):
         return "the second-generation sampler takes this ensemble and writes the CN table with the code already"
     # what runs the cn_sockets pass after the first-generation sampler, and the (4,8) ring whose table E.sw_bp builds per call
     if not (path.sampler == "first" and path.adj_dtype == torch.int16
@@ -620,6 +646,27 @@ def sampled_table_reason(p, rng, path, want=True):
         return ("the first-generation sampler writes the table for vns_pos * dv <= 65535, cns_pos <= 65536 and, beyond 8192 "
                 "sockets per position, dc <= 255 and cns_pos <= 32768 (dv = %d, dc = %d, L = %d, N = %d)"
                 % (p.dv, p.dc, p.L, p.vns_pos))
+    return None
+
+
+def sampler2_deg_reason(p, rng, path, want=True):
+    """Why a configuration whose path (before this switch) is `path` does not take the second-generation sampler of the pairs
+    (3,6) and (5,10), or None where it does.  want: the Simulator's sampler2 argument (None: SAMPLER2_DEG_BY_DEFAULT)."""
+    if not (SAMPLER2_DEG_BY_DEFAULT if want is None else bool(want)):
+        return "switched off"
+    if rng != "philox":
+        return "--rng %s samples the code on the host" % rng
+    if (p.dv, p.dc) == (4, 8):
+        return "dv = 4, dc = 8 has a second-generation sampler of its own, chosen without this switch"
+    if (p.dv, p.dc) not in ((3, 6), (5, 10)):
+        return "the second-generation sampler takes the pairs (3,6), (4,8) and (5,10) (dv = %d, dc = %d)" % (p.dv, p.dc)
+    # what runs the cn_sockets pass after the first-generation sampler, or a ring decoder on a table of sockets
+    if not (path.sampler == "first" and path.adj_dtype == torch.int16
+            and (path.cn_pass or (path.decoder in ("sw_ring", "swc_ring") and path.cn_table == "sock"))):
+        return "the decoder of this configuration (%s) reads no CN -> socket table" % path.decoder
+    if not E.deg_sock16_supported(p):
+        return ("the second-generation sampler of the pairs (3,6) and (5,10) takes at most 8192 sockets per position "
+                "(dv = %d, dc = %d, N = %d: %d sockets)" % (p.dv, p.dc, p.vns_pos, p.cns_pos * p.dc))
     return None
 
 
@@ -753,7 +800,9 @@ def _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, sh
     sim_obj = Simulator(p, decoder="full", W=W, max_it=caps[-1], is_term=True, doped=doped, batch=opts.batch, rng=opts.rng,
                         seed=opts.seed, schedule="flooding", shard_frames=shard == "frames",
                         device=getattr(opts, "device", None), index=index, verbose=verbose, caps=caps, wide=wide, deg=deg,
-                        fused_caps=fused, sampled_table=switch[getattr(opts, "sampled_table", "auto")])
+                        fused_caps=fused, sampled_table=switch[getattr(opts, "sampled_table", "auto")],
+                        sampler2=switch[getattr(opts, "sampler2", "auto")])
+    _check_sampler2(opts, sim_obj)
     _check_sampled_table(opts, sim_obj)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
@@ -908,7 +957,9 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                         wide={"auto": None, "on": True, "off": False}[getattr(opts, "wide", "auto")],
                         deg={"auto": None, "on": True, "off": False}[getattr(opts, "deg", "auto")],
                         ring=ring if decoder in ("sw", "swc") else None,
-                        sampled_table={"auto": None, "on": True, "off": False}[getattr(opts, "sampled_table", "auto")])
+                        sampled_table={"auto": None, "on": True, "off": False}[getattr(opts, "sampled_table", "auto")],
+                        sampler2={"auto": None, "on": True, "off": False}[getattr(opts, "sampler2", "auto")])
+    _check_sampler2(opts, sim_obj)
     _check_sampled_table(opts, sim_obj)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
@@ -984,6 +1035,12 @@ def _check_sampled_table(opts, sim_obj):
     """--sampled-table on where the sampler cannot write the table: exits with the reason."""
     if getattr(opts, "sampled_table", "auto") == "on" and sim_obj.sampled_table_reason is not None:
         raise SystemExit("--sampled-table on: " + sim_obj.sampled_table_reason)
+
+
+def _check_sampler2(opts, sim_obj):
+    """--sampler2 on where the second-generation sampler of the pairs (3,6) and (5,10) does not apply: exits with the reason."""
+    if getattr(opts, "sampler2", "auto") == "on" and sim_obj.sampler2_deg_reason is not None:
+        raise SystemExit("--sampler2 on: " + sim_obj.sampler2_deg_reason)
 
 
 def _check_window(opts):
@@ -1069,6 +1126,11 @@ def _parser(prog):
                     help="where the first-generation sampler is followed by a pass that builds the CN -> socket table: the sampler "
                          "writes the table itself (on), the separate pass (off), or the measured default (auto); same files.  "
                          "'on' where no such pass runs is an error that says why")
+    ap.add_argument("--sampler2", choices=("auto", "on", "off"), default="auto",
+                    help="--dv/--dc 3/6 or 5/10 with at most 8192 sockets per position, where the decoder reads a CN -> socket "
+                         "table: the second-generation sampler draws the code and writes the table in one launch (on), the "
+                         "first-generation sampler and its table pass (off), or the measured default (auto); same files.  'on' "
+                         "where it does not apply is an error that says why")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")

@@ -210,6 +210,17 @@ int scldpc_sample_philox_device_adj16_sock(const scldpc_code_params *p, uint64_t
                                            double eps, int32_t ndoped, const int32_t *doped_positions, uint16_t *d_vn_adj16,
                                            uint16_t *d_cn_sock16, uint32_t *d_chan_bits, void *d_workspace,
                                            uint64_t workspace_bytes, void *stream);
+/* The second-generation sampler for the pairs (dv, dc) = (3,6) and (5,10) (sampler_v2_deg.hip): d_vn_adj16 [ntrials][n][dv] and
+ * d_chan_bits bit for bit those of scldpc_sample_philox_device_adj16 with the same key, d_cn_sock16 [ntrials][nk][dc] the
+ * CN -> socket table as above (NULL: no table; otherwise 4-byte aligned for whole-word stores, any alignment works).  No
+ * workspace.  *_supported (no device needed): 1 for these two pairs with at most 8192 sockets per CN position
+ * (cns_pos * dc <= 8192, odd cns_pos included), else 0 — dv = 4, dc = 8 has scldpc_sample_philox_device_sock16.  The entry
+ * point refuses every other ensemble with SCLDPC_ERR_TOO_LARGE before any device work; argument checks and their
+ * SCLDPC_ERR_BAD_ARG are scldpc_sample_philox_device_sock16's. */
+int scldpc_sample_philox_deg_sock16_supported(const scldpc_code_params *p);
+int scldpc_sample_philox_device_deg_sock16(const scldpc_code_params *p, uint64_t seed, uint64_t trial0, int32_t ntrials,
+                                           double eps, int32_t ndoped, const int32_t *doped_positions, uint16_t *d_vn_adj16,
+                                           uint16_t *d_cn_sock16, uint32_t *d_chan_bits, void *stream);
 int scldpc_full_bp_cn16_supported(const scldpc_code_params *p);
 int scldpc_full_bp_fixpoint_device_cn16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                         const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t is_term,
