@@ -23,12 +23,28 @@
 namespace {
 
 using scldpc_dev::philox4x32_10;
+using scldpc_dev::philox_prefix;
+using scldpc_dev::philox_tail;
+using scldpc_dev::philox_uniform;
+using scldpc_dev::PhiloxPrefix;
+using scldpc_dev::PhiloxUniform;
 using scldpc_dev::wave_inclusive_scan;
 
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxDoped = 32;
 constexpr int kWorkCap = 1024;          // keys of buckets that span two CNs, per position (expected: 0.03 * S <= 250)
+
+// atomicAdd on an LDS word, returning the old value, written as the instruction itself: given a uniform operand under a
+// one-lane branch, the compiler's atomic optimizer wraps an atomicAdd in a lane election, a multiply and a multiply-add
+// of its own (some 20 vector cycles per call).  The caller's barrier orders the word against its readers.
+__device__ __forceinline__ uint32_t lds_add_rtn(uint32_t *p, uint32_t v)
+{
+    const uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)p;
+    uint32_t old;
+    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(old) : "v"(addr), "v"(v) : "memory");
+    return old;
+}
 
 struct S2Args {
     int L, cns_pos, vns_pos, n, S, D, nb, nw;
@@ -43,6 +59,14 @@ struct S2Args {
     uint16_t *vn_adj16;                 // uint16 [T][n][4], CN index local to its position
     uint16_t *cn_adj16;                 // uint16 [T][D*cns_pos][8] VNs of every CN (0xFFFF: none), or null
     uint32_t *chan;
+};
+
+// LDS layout (32-bit words) of the one-call-per-thread instances: a function of ROWS and of whether a stage is kept
+template <int ROWS, int CNMODE>
+struct V2Layout {
+    static constexpr int nb = ROWS * kThreads;                          // histogram words; also the bound of S
+    static constexpr int off_gpk = nb, off_fix = off_gpk + nb, off_stage = off_fix + nb / 2;
+    static constexpr int off_wsum = off_stage + (CNMODE != 0 ? nb / 2 : 0);
 };
 
 // KMAX = Philox calls (4 sockets each) per thread and position: 1 up to 4096 sockets per position, 2 up to 8192
@@ -63,15 +87,21 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
     constexpr bool INCL = KMAX == 1;
     static_assert(ROWS * kThreads == (1 << LG) && (INCL ? ROWS <= 4 : ROWS == 8), "ROWS is 1, 2, 4 (KMAX 1) or 8 (KMAX 2)");
     extern __shared__ uint32_t lds[];
+    // One call per thread: the regions are laid out for nb sockets (S <= nb = 1024 * ROWS), so every LDS address is the
+    // thread's offset plus an immediate and no offset is held in (or reloaded into) a scalar register; launch_v2 sizes the
+    // allocation by the same V2Layout.  Two calls per thread: the offsets come with the arguments, sized by S.
+    using Lay = V2Layout<ROWS, CNMODE>;
+    const int off_gpk = INCL ? Lay::off_gpk : a.off_gpk, off_fix = INCL ? Lay::off_fix : a.off_fix;
+    const int off_stage = INCL ? Lay::off_stage : a.off_stage, off_wsum = INCL ? Lay::off_wsum : a.off_wsum;
     uint32_t *hist = lds;                                               // nb words of four nibble-wide bucket counters
-    uint32_t *gpk = lds + a.off_gpk;                                    // S words: packed keys of straddling buckets
-    uint16_t *fix = reinterpret_cast<uint16_t *>(lds + a.off_fix);      // S CN-local ids of this position's sockets
-    uint16_t *stage = reinterpret_cast<uint16_t *>(lds + a.off_stage);  // the S sockets (or their VNs) in rank order
-    uint32_t *wsum = lds + a.off_wsum;                                  // 16 wave totals + the worklist counter
+    uint32_t *gpk = lds + off_gpk;                                      // S words: packed keys of straddling buckets
+    uint16_t *fix = reinterpret_cast<uint16_t *>(lds + off_fix);        // S CN-local ids of this position's sockets
+    uint16_t *stage = reinterpret_cast<uint16_t *>(lds + off_stage);    // the S sockets (or their VNs) in rank order
+    uint32_t *wsum = lds + off_wsum;                                    // 16 wave totals + the worklist counter
     uint32_t *wl = wsum + 32;                                           // worklist: 2 words per key of a straddling bucket
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int S = a.S, nb = a.nb;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave: kept scalar)
+    const int S = a.S, nb = INCL ? ROWS * kThreads : a.nb;
     const int ncalls = S >> 2;                                          // S % 4 == 0 (checked on the host)
     bool own[KMAX];                                                     // call k of this thread: sockets 4*(tid + 1024 k) .. +3
 #pragma unroll
@@ -127,13 +157,23 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
     uint32_t rowP[KMAX], rowQ[KMAX], rowR[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; k++) rowP[k] = rowQ[k] = rowR[k] = 0;
+    // The draw of position p is philox4x32_10(c0 = thread, c1 = p, c2 | c3 = trial, key = seed).  What its first rounds make
+    // of the thread, the trial and the seed alone (philox.h: four words, three products) is computed once per trial; what
+    // they make of the position, the trial and the seed is uniform and runs on the scalar unit: 15 vector products per
+    // draw are left of 19.
+    PhiloxPrefix pre[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; k++) pre[k] = philox_prefix((uint32_t)(tid + k * kThreads), t_lo, t_hi, a.seed_lo, a.seed_hi);
     uint32_t nxt[E];
+    {
+        const PhiloxUniform un = philox_uniform(0u, t_lo, a.seed_lo, a.seed_hi);
 #pragma unroll
-    for (int k = 0; k < KMAX; k++) {
-        uint32_t r[4] = {0, 0, 0, 0};
-        if (own[k]) philox4x32_10((uint32_t)(tid + k * kThreads), 0u, t_lo, t_hi, a.seed_lo, a.seed_hi, r);
+        for (int k = 0; k < KMAX; k++) {
+            uint32_t r[4] = {0, 0, 0, 0};
+            if (own[k]) philox_tail(pre[k], un, a.seed_lo, a.seed_hi, r);
 #pragma unroll
-        for (int u = 0; u < 4; u++) nxt[4 * k + u] = r[u];
+            for (int u = 0; u < 4; u++) nxt[4 * k + u] = r[u];
+        }
     }
     for (int p = 0; p < a.D; p++) {
         STAMP(0);
@@ -231,7 +271,7 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
         // share the key's top LG + 2 bits, so the shift drops none of the bits that order them.
         if (ranked) {                                                   // (an overflowed histogram has no ranks worth scattering by)
             uint32_t rk[E], g0a[E], g1a[E];
-            bool st[E];
+            bool st[E], sx[E];                                          // straddler; the same before the own[] mask (INCL)
             if constexpr (INCL) {
                 uint32_t h[E];
 #pragma unroll
@@ -242,7 +282,8 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
                     g0a[e] = pre + (t & 0xFu);
                     g1a[e] = pre + ((t >> 4) & 0xFu);
                     rk[e] = g0a[e] + slot[e];
-                    st[e] = own[e >> 2] && ((g0a[e] ^ (g1a[e] - 1u)) >> DC_SHIFT) != 0u;
+                    sx[e] = ((g0a[e] ^ (g1a[e] - 1u)) >> DC_SHIFT) != 0u;
+                    st[e] = own[e >> 2] && sx[e];
                 }
             } else {
                 uint32_t h[E];
@@ -260,28 +301,41 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
             }
             if constexpr (INCL) {
                 // the wave's straddlers (3 % of the keys) take consecutive worklist entries: ballots and one LDS atomic per
-                // wave, no divergent loop
-                unsigned long long vote[E], anyv = 0;
+                // wave, no divergent loop.  The votes are the compares' own masks cut by the owners' mask (a ballot of
+                // `own && straddles` goes through a VGPR and back).
+                const unsigned long long ownv = __builtin_amdgcn_ballot_w64(own[0]);
+                unsigned long long vote[E];
                 int total = 0;
 #pragma unroll
-                for (int e = 0; e < E; e++) { vote[e] = __builtin_amdgcn_ballot_w64(st[e]); anyv |= vote[e]; total += __builtin_popcountll(vote[e]); }
-                if (anyv) {
-                    int base = 0;
-                    if (lane == 0) base = atomicAdd(reinterpret_cast<int *>(&wsum[kWaves]), total);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    // past the list's end the entries are not written: the count still grows, and the exact fallback ranks
-                    // the position
-                    const bool fits = base + total <= kWorkCap;
+                for (int e = 0; e < E; e++) { vote[e] = __builtin_amdgcn_ballot_w64(sx[e]) & ownv; total += __builtin_popcountll(vote[e]); }
+                if (total != 0) {
+                    // (the first lane is found again from tid here, by an instruction the compiler cannot hoist: as a loop
+                    // invariant its 64-bit lane mask is spilled to a VGPR lane under the 72-SGPR cap and costs two
+                    // v_readlane per position)
+                    uint32_t ln, got = 0;
+                    asm volatile("v_and_b32 %0, 63, %1" : "=v"(ln) : "v"(tid));
+                    if (ln == 0u) got = lds_add_rtn(&wsum[kWaves], (uint32_t)total);
+                    int base = __builtin_amdgcn_readfirstlane((int)got);
+                    // past the list's end nothing is written: the count still grows, and the exact fallback ranks the
+                    // position (from the keys, not from gpk)
+                    if (base + total <= kWorkCap) {
+                        // entry w of the list as a word pair of the whole LDS: the list's offset rides in the scalar base
+                        static_assert((Lay::off_wsum + 32) % 2 == 0, "the worklist starts on a word pair");
+                        uint2 *wl2 = reinterpret_cast<uint2 *>(lds);
+                        base += (Lay::off_wsum + 32) / 2;
 #pragma unroll
-                    for (int e = 0; e < E; e++) {
-                        if (st[e]) {
-                            const uint32_t w = __builtin_amdgcn_mbcnt_hi((uint32_t)(vote[e] >> 32),
-                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)vote[e], (uint32_t)base));
-                            const uint32_t pk = (key[e] << LG) | sock(e);
-                            gpk[rk[e]] = pk;
-                            if (fits) { wl[2 * w] = g0a[e] | (g1a[e] << 16); wl[2 * w + 1] = pk; }
+                        for (int e = 0; e < E; e++) {
+                            if (st[e]) {
+                                const uint32_t w = __builtin_amdgcn_mbcnt_hi((uint32_t)(vote[e] >> 32),
+                                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)vote[e], (uint32_t)base));
+                                const uint32_t pk = (key[e] << LG) | sock(e);
+                                gpk[rk[e]] = pk;
+                                uint32_t *ent = reinterpret_cast<uint32_t *>(wl2 + w);
+                                ent[0] = g0a[e] | (g1a[e] << 16);
+                                ent[1] = pk;
+                            }
+                            base += __builtin_popcountll(vote[e]);
                         }
-                        base += __builtin_popcountll(vote[e]);
                     }
                 }
             } else {
@@ -372,11 +426,13 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
             // the round keys are recomputed from the seed here (twenty scalar adds) rather than kept in twenty SGPRs across
             // the whole loop, which the 72-SGPR budget of two workgroups per CU would spill into VGPR lanes
             uint32_t k_lo = a.seed_lo, k_hi = a.seed_hi;
-            asm volatile("" : "+s"(k_lo), "+s"(k_hi));
+            uint32_t tl = t_lo;                                         // (likewise the trial: no product of it is kept either)
+            asm volatile("" : "+s"(k_lo), "+s"(k_hi), "+s"(tl));
+            const PhiloxUniform un = philox_uniform((uint32_t)(p + 1), tl, k_lo, k_hi);
 #pragma unroll
             for (int k = 0; k < KMAX; k++) {
                 uint32_t r[4] = {0, 0, 0, 0};
-                if (own[k]) philox4x32_10((uint32_t)(tid + k * kThreads), (uint32_t)(p + 1), t_lo, t_hi, k_lo, k_hi, r);
+                if (own[k]) philox_tail(pre[k], un, k_lo, k_hi, r);
 #pragma unroll
                 for (int u = 0; u < 4; u++) nxt[4 * k + u] = r[u];
             }
@@ -393,7 +449,8 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
             uint2 c = make_uint2(0u, 0u);                               // [edge 0 | edge 1], [edge 2 | edge 3] of this step
             if (own[k]) c = reinterpret_cast<const uint2 *>(fix)[tid + k * kThreads];
             if (qpos >= 0 && own[k]) {
-                const size_t j = (size_t)tr * a.n + (size_t)qpos * a.vns_pos + (size_t)(tid + k * kThreads);
+                // (the offset inside a trial fits 32 bits: one scalar product, no high half to carry)
+                const size_t j = (size_t)tr * a.n + (size_t)((uint32_t)qpos * (uint32_t)a.vns_pos + (uint32_t)(tid + k * kThreads));
                 uint2 v;
                 v.x = rowP[k];
                 v.y = (rowR[k] >> 16) | (c.y & 0xFFFF0000u);
@@ -413,12 +470,13 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
 
     // ---- channel: 32 VNs per output word, 8 Philox calls
     uint32_t *chan = a.chan + (size_t)tr * a.nw;
+    const PhiloxUniform chun = philox_uniform(0x80000000u, t_lo, a.seed_lo, a.seed_hi);     // once per trial
     for (int w = tid; w < a.nw; w += kThreads) {
         uint32_t word = 0;
 #pragma unroll
         for (int c = 0; c < 8; c++) {
             uint32_t r[4];
-            philox4x32_10((uint32_t)(w * 8 + c), 0x80000000u, t_lo, t_hi, a.seed_lo, a.seed_hi, r);
+            philox_tail(philox_prefix((uint32_t)(w * 8 + c), t_lo, t_hi, a.seed_lo, a.seed_hi), chun, a.seed_lo, a.seed_hi, r);
 #pragma unroll
             for (int u = 0; u < 4; u++) word |= (uint32_t)((r[u] >> 1) < a.thresh) << (c * 4 + u);
         }
@@ -776,10 +834,13 @@ int launch_v2(const char *who, int cnmode, const scldpc_code_params *p, uint64_t
     // it is opt-in (SCLDPC_SAMPLER_GEN=3) and the second generation stays the default.
     const char *gen_env = getenv("SCLDPC_SAMPLER_GEN");
     const bool v3 = a.nb <= 4 * kThreads && gen_env && atoi(gen_env) == 3;
+    // the second generation's one-call instances (nb <= 4096) address their regions by V2Layout's immediates: sized for nb
+    // sockets rather than S
+    const int s_lay = !v3 && a.nb <= 4 * kThreads ? a.nb : a.S;
     int off = ((v3 ? 2 : 1) * a.nb + 3) & ~3;
-    a.off_gpk = off;   off += (a.S + 3) & ~3;
-    a.off_fix = off;   off += (a.S / 2 + 3) & ~3;           // S uint16
-    a.off_stage = off; off += cnmode ? (a.S / 2 + 3) & ~3 : 0;
+    a.off_gpk = off;   off += (s_lay + 3) & ~3;
+    a.off_fix = off;   off += (s_lay / 2 + 3) & ~3;         // S uint16
+    a.off_stage = off; off += cnmode ? (s_lay / 2 + 3) & ~3 : 0;
     a.off_wsum = off;  off += 32 + 2 * kWorkCap;
     size_t lds_bytes = 4u * (size_t)off;
     lds_bytes = std::min(lds_bytes + scldpc::debug_lds_pad("SAMPLER"), std::max(lds_bytes, (size_t)scldpc::kMaxLdsBytes));
