@@ -15,17 +15,17 @@
 // LDS ring, and emits VN position p-dv+1 as whole rows (16 B as int32 CN ids, or 8 B as uint16
 // position-local CN ids), so HBM sees only full-line stores.
 // The exact-replay sampler (glibc stream, identical seeds) is glibc_sampler.cpp.
-#include "common.h"
-#include "kernel_util.h"
+// The steps of a channel word, the erasure threshold and the validation of a call are
+// sampler_common.h's, shared with the second generation.
+#include "sampler_common.h"
 #include "philox.h"
-#include <cstdlib>
 
 namespace {
 
 constexpr int kBuckets = 2048;            // big kernel, fused ranking: straddling buckets listed per position (1200 at N = 10000)
-constexpr int kThreads = 1024;
+constexpr int kThreads = scldpc::kSamplerThreads;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxDoped = 32;
+using scldpc::kMaxDoped;
 
 struct SArgs {
     int force_wide;             // diagnostics / tests: rank every position of the big kernel by the 16-bit-counter fallback
@@ -46,8 +46,10 @@ struct SArgs {
     int nk, tab32;              // tab32: the fused big kernel copies a position's S entries as 32-bit words (S even, 4-byte aligned table)
 };
 
+using scldpc_dev::channel_erased;
+using scldpc_dev::channel_tail;
+using scldpc_dev::channel_undope;
 using scldpc_dev::philox4x32_10;
-
 using scldpc_dev::wave_inclusive_scan;
 
 // KMAX = Philox calls per thread per permutation (4 sockets each); ROWS = 64-counter rows each wave scans
@@ -322,14 +324,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(72))) void
             uint32_t r[4];
             philox4x32_10((uint32_t)(w * 8 + c), 0x80000000u, t_lo, t_hi, a.seed_lo, a.seed_hi, r);
 #pragma unroll
-            for (int u = 0; u < 4; u++) word |= (uint32_t)((r[u] >> 1) < a.thresh) << (c * 4 + u);
+            for (int u = 0; u < 4; u++) word |= channel_erased(r[u], a.thresh) << (c * 4 + u);
         }
         const int j0 = w * 32;
-        if (j0 + 32 > a.n) word &= (1u << (a.n - j0)) - 1u;
-        for (int d = 0; d < a.ndoped; d++) {                        // doped positions are never erased (BPF:1566-1573)
-            const int lo = max(a.doped[d] * a.vns_pos, j0) - j0, hi = min((a.doped[d] + 1) * a.vns_pos, j0 + 32) - j0;
-            if (lo < hi) word &= ~(((hi - lo) == 32 ? 0xFFFFFFFFu : ((1u << (hi - lo)) - 1u)) << lo);
-        }
+        word = channel_tail(word, j0, a.n);
+        for (int d = 0; d < a.ndoped; d++) word = channel_undope(word, j0, a.doped[d], a.vns_pos);
         chan[w] = word;
     }
     STAMP(6);                                       // channel
@@ -791,14 +790,11 @@ __global__ __launch_bounds__(kThreads, (FUSED || TABLE) ? 4 : 8) __attribute__((
             uint32_t r[4];
             philox4x32_10((uint32_t)(w * 8 + c), 0x80000000u, t_lo, t_hi, a.seed_lo, a.seed_hi, r);
 #pragma unroll
-            for (int u = 0; u < 4; u++) word |= (uint32_t)((r[u] >> 1) < a.thresh) << (c * 4 + u);
+            for (int u = 0; u < 4; u++) word |= channel_erased(r[u], a.thresh) << (c * 4 + u);
         }
         const int j0 = w * 32;
-        if (j0 + 32 > a.n) word &= (1u << (a.n - j0)) - 1u;
-        for (int d = 0; d < a.ndoped; d++) {
-            const int lo = max(a.doped[d] * a.vns_pos, j0) - j0, hi = min((a.doped[d] + 1) * a.vns_pos, j0 + 32) - j0;
-            if (lo < hi) word &= ~(((hi - lo) == 32 ? 0xFFFFFFFFu : ((1u << (hi - lo)) - 1u)) << lo);
-        }
+        word = channel_tail(word, j0, a.n);
+        for (int d = 0; d < a.ndoped; d++) word = channel_undope(word, j0, a.doped[d], a.vns_pos);
         chan[w] = word;
     }
 }
@@ -810,15 +806,10 @@ int launch(const scldpc_code_params *p, int ensemble, uint64_t seed, uint64_t tr
 {
     if (int rc = scldpc::check_params(p)) return rc;
     if (scratch.query) *scratch.query = 0;
-    if (!scratch.query && (ntrials < 0 || (ntrials > 0 && (!d_adj || !d_chan_bits || (table && !d_cn_sock16)))))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
-    if (ndoped < 0 || ndoped > kMaxDoped || (ndoped > 0 && !doped_positions))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: 0 <= ndoped <= %d", who, kMaxDoped);
-    if (!(eps >= 0.0 && eps <= 1.0))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: eps=%g outside [0,1]", who, eps);
-    if (ntrials <= 0) return SCLDPC_OK;
-
     SArgs a{};
+    const bool bad_buffers = !scratch.query && (ntrials < 0 || (ntrials > 0 && (!d_adj || !d_chan_bits || (table && !d_cn_sock16))));
+    if (int rc = scldpc::check_sample_call(who, p, bad_buffers, ntrials, eps, ndoped, doped_positions, &a.ndoped, a.doped)) return rc;
+    if (ntrials <= 0) return SCLDPC_OK;
     a.dv = p->dv; a.dc = p->dc; a.L = p->L; a.cns_pos = p->cns_pos; a.vns_pos = p->vns_pos;
     a.n = scldpc::n_of(p); a.S = p->cns_pos * p->dc; a.D = p->L + p->dv - 1; a.nw = scldpc::nw_of(p);
     if (a.S > 65536 || p->dv > 8)
@@ -845,21 +836,9 @@ int launch(const scldpc_code_params *p, int ensemble, uint64_t seed, uint64_t tr
     a.nb = 1 << lg; a.shift = 32 - lg; a.lgchunk = lg - 4;            // 16 waves
     a.dc_shift = -1;
     for (int k = 0; k < 8; k++) if ((1 << k) == p->dc) a.dc_shift = k;
-    a.ndoped = ndoped;
-    for (int d = 0; d < ndoped; d++) {
-        if (doped_positions[d] < 0 || doped_positions[d] >= p->L)
-            return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "doped position %d outside [0,%d)", doped_positions[d], p->L);
-        a.doped[d] = doped_positions[d];
-    }
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
     a.trial0 = trial0;
-    // erased iff r/RAND_MAX < eps with r = 31-bit draw  ⇔  r < ceil(eps * RAND_MAX)   (BPF:370,1554-1562)
-    {
-        const double x = eps * 2147483647.0;
-        double c = (double)(uint64_t)x;
-        if (c < x) c += 1.0;
-        a.thresh = (uint32_t)c;
-    }
+    a.thresh = scldpc::erasure_threshold(eps);
     // nb counter words (4 * nb nibble buckets: 7.6 % of the keys in straddling buckets at N = 10000 instead of 15 %) at one
     // workgroup per CU beat nb / 2 words at two: 105 against 165 ms per 8192 trials (profiles/r03_ab_c3_sampler.txt)
     a.fine = 1;

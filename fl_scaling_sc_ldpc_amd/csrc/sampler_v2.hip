@@ -14,14 +14,22 @@
 //    such CNs with a lower degree, BPF:1703-1716) and read 0xFFFF.  Within a CN the order is unspecified (arrival order
 //    of the histogram atomics for non-straddling buckets): consumers treat the dc entries as a set.
 //    full_bp_small.hip decodes from (vn_adj16, cn_adj16) with 4 bits of LDS per CN.
-#include "common.h"
-#include "kernel_util.h"
+//
+// sampler_common.h holds what this file shares with sampler_v2_deg.hip and sampler.hip: the histogram words of a thread, the
+// scan, the two-calls-per-thread look-up, the worklist's resolve loop, the steps of a channel word, and on the host the
+// validation, the threshold and the LDS layout.  Here stay both worklist pushes, the exact fallback, the row assembly in
+// registers, the split Philox draw and the third generation.
+#include "sampler_common.h"
 #include "philox.h"
-#include <algorithm>
-#include <cstdlib>
 
 namespace {
 
+using scldpc_dev::channel_erased;
+using scldpc_dev::channel_tail;
+using scldpc_dev::channel_undope;
+using scldpc_dev::clear_hist_words;
+using scldpc_dev::load_hist_words;
+using scldpc_dev::store_hist_words;
 using scldpc_dev::philox4x32_10;
 using scldpc_dev::philox_prefix;
 using scldpc_dev::philox_tail;
@@ -30,10 +38,10 @@ using scldpc_dev::PhiloxPrefix;
 using scldpc_dev::PhiloxUniform;
 using scldpc_dev::wave_inclusive_scan;
 
-constexpr int kThreads = 1024;
+constexpr int kThreads = scldpc::kSamplerThreads;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxDoped = 32;
-constexpr int kWorkCap = 1024;          // keys of buckets that span two CNs, per position (expected: 0.03 * S <= 250)
+using scldpc::kMaxDoped;
+using scldpc::kWorkCap;                 // keys of buckets that span two CNs, per position (expected: 0.03 * S <= 250)
 
 // atomicAdd on an LDS word, returning the old value, written as the instruction itself: given a uniform operand under a
 // one-lane branch, the compiler's atomic optimizer wraps an atomicAdd in a lane election, a multiply and a multiply-add
@@ -114,34 +122,7 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
         return CNMODE == 1 ? (uint16_t)((p - u) * a.vns_pos + t) : (uint16_t)sck;
     };
 
-    // hist word while counting = [0:16 | n3:4 | n2:4 | n1:4 | n0:4]: four nibble-wide bucket counters (the atomic's return
-    // value is the key's arrival slot).  After the scan:
-    //   INCL:  [exclusive prefix:12 | i3:4 | i2:4 | i1:4 | i0:4 | 0:4] with ik = n0 + .. + nk, so bucket k's ranks are
-    //          [prefix + (word >> 4k & 15), prefix + (word >> 4k+4 & 15)) — valid while the word holds at most 15 keys;
-    //   else:  [exclusive prefix:16 | n3 n2 n1 n0], the lower buckets' counts summed at look-up time.
-    // Thread t owns words t*ROWS .. t*ROWS+ROWS-1 (wide LDS accesses).
-    auto nib_sum = [](uint32_t x) {                                     // sum of the four nibbles of the low half
-        const uint32_t v = (x & 0x0F0Fu) + ((x >> 4) & 0x0F0Fu);
-        return (v + (v >> 8)) & 0xFFu;
-    };
-    auto load_words = [&](uint32_t (&x)[ROWS]) {
-        if constexpr (ROWS % 4 == 0) {
-#pragma unroll
-            for (int r = 0; r < ROWS / 4; r++) {
-                const uint4 q = reinterpret_cast<const uint4 *>(hist)[tid * (ROWS / 4) + r];
-                x[4 * r] = q.x; x[4 * r + 1] = q.y; x[4 * r + 2] = q.z; x[4 * r + 3] = q.w;
-            }
-        } else if constexpr (ROWS == 2) { const uint2 q = reinterpret_cast<const uint2 *>(hist)[tid]; x[0] = q.x; x[1] = q.y; }
-        else x[0] = hist[tid];
-    };
-    auto store_words = [&](const uint32_t (&x)[ROWS]) {
-        if constexpr (ROWS % 4 == 0) {
-#pragma unroll
-            for (int r = 0; r < ROWS / 4; r++)
-                reinterpret_cast<uint4 *>(hist)[tid * (ROWS / 4) + r] = make_uint4(x[4 * r], x[4 * r + 1], x[4 * r + 2], x[4 * r + 3]);
-        } else if constexpr (ROWS == 2) reinterpret_cast<uint2 *>(hist)[tid] = make_uint2(x[0], x[1]);
-        else hist[tid] = x[0];
-    };
+    // (the layout of a hist word while counting and after the scan: scan_hist, sampler_common.h)
     STAMP_DECL
     for (int b = tid; b < nb; b += kThreads) hist[b] = 0;
     if (tid == 0) { wsum[kWaves] = 0; wsum[kWaves + 1] = 0; }
@@ -199,68 +180,8 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
         __syncthreads();
         STAMP(1);
 
-        // ---- exclusive scan of the bucket counts: every thread scans its ROWS words, the wave scans the thread totals
-        //      (DPP), the 16 wave totals meet in wsum; the global prefix goes into the words' high halves
-        bool ranked;                                                    // the histogram's ranks hold (else: exact fallback)
-        if constexpr (INCL) {
-            // one multiply per word: nibble k+1 of x * 0x111110 is n0 + .. + nk, nibble 5 the word's total again (no carries
-            // while the word holds at most 15 keys; else nibble 5 is below the true count and the grand total shows it)
-            uint32_t x[ROWS], t20[ROWS], tot20 = 0;
-            load_words(x);
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) {
-                x[r] *= 0x111110u;
-                t20[r] = x[r] & 0xF00000u;                              // the word's total << 20
-                tot20 += t20[r];
-            }
-            const uint32_t tot = tot20 >> 20, inc = wave_inclusive_scan(tot);
-            if (lane == 63) wsum[wave] = inc;
-            __syncthreads();
-            uint32_t winc = lane < kWaves ? wsum[lane] : 0u;          // the 16 wave totals: a scan within DPP row 0
-            const uint32_t wt = winc;
-            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x111, 0xF, 0xF, false);
-            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x112, 0xF, 0xF, false);
-            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x114, 0xF, 0xF, false);
-            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x118, 0xF, 0xF, false);
-            ranked = __builtin_amdgcn_readlane((int)winc, kWaves - 1) == S;
-            uint32_t pre20 = (inc - tot + (uint32_t)__builtin_amdgcn_readlane((int)(winc - wt), wave)) << 20;
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) {
-                x[r] = (x[r] & 0xFFFF0u) | pre20;
-                pre20 += t20[r];
-            }
-            store_words(x);
-        } else {
-            uint32_t x[ROWS], v[ROWS], tot = 0;
-            load_words(x);
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) v[r] = 0;
-            if constexpr (ROWS % 2 == 0) {                              // two words' counters (16 bits each) per 32-bit lane
-#pragma unroll
-                for (int r = 0; r < ROWS; r += 2) {
-                    const uint32_t y = x[r] | (x[r + 1] << 16);
-                    const uint32_t sb = (y & 0x0F0F0F0Fu) + ((y >> 4) & 0x0F0F0F0Fu);      // four byte sums <= 30
-                    v[r] = (sb & 0xFFu) + ((sb >> 8) & 0xFFu);
-                    v[r + 1] = ((sb >> 16) & 0xFFu) + (sb >> 24);
-                    tot += v[r] + v[r + 1];
-                }
-            } else {
-                static_assert(ROWS == 1 || ROWS % 2 == 0, "ROWS is 1, 2, 4 or 8");
-                v[0] = nib_sum(x[0]);
-                tot = v[0];
-            }
-            const uint32_t inc = wave_inclusive_scan(tot);
-            if (lane == 63) wsum[wave] = inc;
-            __syncthreads();
-            const uint32_t wt = lane < kWaves ? wsum[lane] : 0u;
-            const uint32_t winc = wave_inclusive_scan(wt);
-            uint32_t pre = inc - tot + (uint32_t)__builtin_amdgcn_readlane((int)(winc - wt), wave);
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) { x[r] |= pre << 16; pre += v[r]; }
-            store_words(x);
-        }
-        __syncthreads();
-        if constexpr (!INCL) ranked = wsum[kWaves + 1] == 0u;
+        // ---- exclusive scan of the bucket counts; false: the histogram's ranks do not hold (exact fallback)
+        const bool ranked = scldpc_dev::scan_hist<ROWS, INCL>(hist, wsum, tid, lane, wave, S);
         STAMP(2);
 
         // ---- classify: every key gets rank g0 + arrival slot — any bijection onto its bucket's ranks gives the right CN
@@ -286,15 +207,9 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
                     st[e] = own[e >> 2] && sx[e];
                 }
             } else {
-                uint32_t h[E];
-#pragma unroll
-                for (int e = 0; e < E; e++) h[e] = hist[own[e >> 2] ? (key[e] >> KSHIFT) >> 2 : 0u];
+                scldpc_dev::bucket_ranges_excl<KSHIFT>(hist, key, [&](int e) { return own[e >> 2]; }, g0a, g1a);
 #pragma unroll
                 for (int e = 0; e < E; e++) {
-                    const uint32_t k4 = ((key[e] >> KSHIFT) & 3u) * 4u, x = h[e];
-                    const uint32_t below = x & ((1u << k4) - 1u);        // the counters of the word's lower buckets
-                    g0a[e] = (x >> 16) + (below & 0xFu) + ((below >> 4) & 0xFu) + ((below >> 8) & 0xFu);
-                    g1a[e] = g0a[e] + ((x >> k4) & 0xFu);
                     rk[e] = g0a[e] + slot[e];
                     st[e] = own[e >> 2] && ((g1a[e] - 1u) >> DC_SHIFT) != (g0a[e] >> DC_SHIFT);
                 }
@@ -377,10 +292,7 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
 
         // ---- the worklist: true rank among the bucket mates; counters cleared for the next position
         {
-            uint32_t z[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) z[r] = 0;
-            store_words(z);
+            clear_hist_words<ROWS>(hist, tid);
             int nwork = (int)wsum[kWaves];                              // 3 % of S on average (<= 250 keys); the list holds 1024
             const bool exact = !ranked || nwork > kWorkCap || a.force_exact == p || a.force_exact == -2;
             if (exact) {
@@ -412,15 +324,8 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
                     }
                 }
             }
-            for (int w = tid; w < nwork; w += kThreads) {
-                const uint32_t ea = wl[2 * w], pk = wl[2 * w + 1];
-                uint32_t r = ea & 0xFFFFu;                              // its rank: the first rank + the mates below it
-#pragma unroll 1
-                for (uint32_t m = ea & 0xFFFFu; m < (ea >> 16); m++) r += gpk[m] < pk;     // (itself included: not below)
-                const uint32_t sck = pk & ((1u << LG) - 1u);
-                if constexpr (CNMODE != 0) stage[r] = stage_entry(p, sck);
-                fix[sck] = (uint16_t)(r >> DC_SHIFT);
-            }
+            scldpc_dev::resolve_worklist<LG, CNMODE != 0>(nwork, tid, wl, gpk, stage, fix, [&](uint32_t sck) { return stage_entry(p, sck); },
+                                                          [](uint32_t r) { return r >> DC_SHIFT; });
         }
         if (p + 1 < a.D) {
             // the round keys are recomputed from the seed here (twenty scalar adds) rather than kept in twenty SGPRs across
@@ -478,14 +383,11 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
             uint32_t r[4];
             philox_tail(philox_prefix((uint32_t)(w * 8 + c), t_lo, t_hi, a.seed_lo, a.seed_hi), chun, a.seed_lo, a.seed_hi, r);
 #pragma unroll
-            for (int u = 0; u < 4; u++) word |= (uint32_t)((r[u] >> 1) < a.thresh) << (c * 4 + u);
+            for (int u = 0; u < 4; u++) word |= channel_erased(r[u], a.thresh) << (c * 4 + u);
         }
         const int j0 = w * 32;
-        if (j0 + 32 > a.n) word &= (1u << (a.n - j0)) - 1u;
-        for (int d = 0; d < a.ndoped; d++) {                            // doped positions are never erased (BPF:1566-1573)
-            const int lo = max(a.doped[d] * a.vns_pos, j0) - j0, hi = min((a.doped[d] + 1) * a.vns_pos, j0 + 32) - j0;
-            if (lo < hi) word &= ~(((hi - lo) == 32 ? 0xFFFFFFFFu : ((1u << (hi - lo)) - 1u)) << lo);
-        }
+        word = channel_tail(word, j0, a.n);
+        for (int d = 0; d < a.ndoped; d++) word = channel_undope(word, j0, a.doped[d], a.vns_pos);
         chan[w] = word;
     }
     STAMP(6);
@@ -611,9 +513,7 @@ __global__ __launch_bounds__(kThreads, 8) __attribute__((amdgpu_num_sgpr(72))) v
                 fix[sck] = (uint16_t)(r >> DC_SHIFT);
             }
             {   // the counters of p-1 are free: every look-up of phase C(p-1) lies behind the last barrier
-                if constexpr (ROWS == 4) reinterpret_cast<uint4 *>(hp)[tid] = make_uint4(0u, 0u, 0u, 0u);
-                else if constexpr (ROWS == 2) reinterpret_cast<uint2 *>(hp)[tid] = make_uint2(0u, 0u);
-                else hp[tid] = 0u;
+                clear_hist_words<ROWS>(hp, tid);
             }
         }
         STAMP(1);                                                       // A: worklist of p-1 + clear
@@ -645,9 +545,7 @@ __global__ __launch_bounds__(kThreads, 8) __attribute__((amdgpu_num_sgpr(72))) v
         if (tid == 0) { wsum[16] = 0; wsum[18 + ((p & 1) ^ 1)] = 0; }  // worklist count and the flag of p-1: consumed in phase A
         if (live) {
             uint32_t x[ROWS], tot = 0, over = 0;
-            if constexpr (ROWS == 4) { const uint4 q = reinterpret_cast<const uint4 *>(hc)[tid]; x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w; }
-            else if constexpr (ROWS == 2) { const uint2 q = reinterpret_cast<const uint2 *>(hc)[tid]; x[0] = q.x; x[1] = q.y; }
-            else x[0] = hc[tid];
+            load_hist_words<ROWS>(hc, tid, x);
             uint32_t v[ROWS];
 #pragma unroll
             for (int r = 0; r < ROWS; r++) {
@@ -664,9 +562,7 @@ __global__ __launch_bounds__(kThreads, 8) __attribute__((amdgpu_num_sgpr(72))) v
             uint32_t pre = inc - tot;
 #pragma unroll
             for (int r = 0; r < ROWS; r++) { x[r] |= pre << 20; pre += v[r]; }
-            if constexpr (ROWS == 4) reinterpret_cast<uint4 *>(hc)[tid] = make_uint4(x[0], x[1], x[2], x[3]);
-            else if constexpr (ROWS == 2) reinterpret_cast<uint2 *>(hc)[tid] = make_uint2(x[0], x[1]);
-            else hc[tid] = x[0];
+            store_hist_words<ROWS>(hc, tid, x);
             if (lane == 63) wsum[wave] = inc;
         }
         if (p > 0) {
@@ -782,14 +678,11 @@ __global__ __launch_bounds__(kThreads, 8) __attribute__((amdgpu_num_sgpr(72))) v
             uint32_t r[4];
             philox4x32_10((uint32_t)(w * 8 + c), 0x80000000u, t_lo, t_hi, c_lo, c_hi, r);
 #pragma unroll
-            for (int u = 0; u < 4; u++) word |= (uint32_t)((r[u] >> 1) < a.thresh) << (c * 4 + u);
+            for (int u = 0; u < 4; u++) word |= channel_erased(r[u], a.thresh) << (c * 4 + u);
         }
         const int j0 = w * 32;
-        if (j0 + 32 > a.n) word &= (1u << (a.n - j0)) - 1u;
-        for (int d = 0; d < a.ndoped; d++) {                            // doped positions are never erased (BPF:1566-1573)
-            const int lo = max(a.doped[d] * a.vns_pos, j0) - j0, hi = min((a.doped[d] + 1) * a.vns_pos, j0 + 32) - j0;
-            if (lo < hi) word &= ~(((hi - lo) == 32 ? 0xFFFFFFFFu : ((1u << (hi - lo)) - 1u)) << lo);
-        }
+        word = channel_tail(word, j0, a.n);
+        for (int d = 0; d < a.ndoped; d++) word = channel_undope(word, j0, a.doped[d], a.vns_pos);
         chan[w] = word;
     }
     STAMP(8);                                                           // channel
@@ -800,56 +693,29 @@ int launch_v2(const char *who, int cnmode, const scldpc_code_params *p, uint64_t
               double eps, int32_t ndoped, const int32_t *doped_positions, uint16_t *d_vn_adj16, uint16_t *d_table,
               uint32_t *d_chan_bits, void *stream)
 {
-    if (ntrials < 0 || (ntrials > 0 && (!d_vn_adj16 || !d_chan_bits)))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
-    if (ndoped < 0 || ndoped > kMaxDoped || (ndoped > 0 && !doped_positions))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: 0 <= ndoped <= %d", who, kMaxDoped);
-    if (!(eps >= 0.0 && eps <= 1.0))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: eps=%g outside [0,1]", who, eps);
+    S2Args a{};
+    if (int rc = scldpc::check_sample_call(who, p, ntrials < 0 || (ntrials > 0 && (!d_vn_adj16 || !d_chan_bits)), ntrials, eps,
+                                           ndoped, doped_positions, &a.ndoped, a.doped)) return rc;
     if (ntrials == 0) return SCLDPC_OK;
     if (!d_table) cnmode = 0;
 
-    S2Args a{};
     a.L = p->L; a.cns_pos = p->cns_pos; a.vns_pos = p->vns_pos;
     a.n = scldpc::n_of(p); a.S = p->cns_pos * p->dc; a.D = p->L + p->dv - 1; a.nw = scldpc::nw_of(p);
-    int lg = 10;                                    // nb = power of two >= max(S, kThreads): the histogram of sampler.hip
-    while ((1 << lg) < a.S) lg++;
-    a.nb = 1 << lg;
-    a.ndoped = ndoped;
-    for (int d = 0; d < ndoped; d++) {
-        if (doped_positions[d] < 0 || doped_positions[d] >= p->L)
-            return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "doped position %d outside [0,%d)", doped_positions[d], p->L);
-        a.doped[d] = doped_positions[d];
-    }
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
     a.trial0 = trial0;
-    {   // erased iff r/RAND_MAX < eps with r = 31-bit draw  ⇔  r < ceil(eps * RAND_MAX)   (BPF:370,1554-1562)
-        const double x = eps * 2147483647.0;
-        double c = (double)(uint64_t)x;
-        if (c < x) c += 1.0;
-        a.thresh = (uint32_t)c;
-    }
+    a.thresh = scldpc::erasure_threshold(eps);
     // Third generation (one Philox call per thread: at most 4096 sockets per position; two histogram buffers): measured equal to
     // the second within +-4 % at N = 1000 (faster without the CN table and at N <= 512, slower with it: DESIGN.md §5), so
     // it is opt-in (SCLDPC_SAMPLER_GEN=3) and the second generation stays the default.
     const char *gen_env = getenv("SCLDPC_SAMPLER_GEN");
-    const bool v3 = a.nb <= 4 * kThreads && gen_env && atoi(gen_env) == 3;
-    // the second generation's one-call instances (nb <= 4096) address their regions by V2Layout's immediates: sized for nb
-    // sockets rather than S
-    const int s_lay = !v3 && a.nb <= 4 * kThreads ? a.nb : a.S;
-    int off = ((v3 ? 2 : 1) * a.nb + 3) & ~3;
-    a.off_gpk = off;   off += (s_lay + 3) & ~3;
-    a.off_fix = off;   off += (s_lay / 2 + 3) & ~3;         // S uint16
-    a.off_stage = off; off += cnmode ? (s_lay / 2 + 3) & ~3 : 0;
-    a.off_wsum = off;  off += 32 + 2 * kWorkCap;
-    size_t lds_bytes = 4u * (size_t)off;
-    lds_bytes = std::min(lds_bytes + scldpc::debug_lds_pad("SAMPLER"), std::max(lds_bytes, (size_t)scldpc::kMaxLdsBytes));
-    if (lds_bytes > (size_t)scldpc::kMaxLdsBytes)
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %zu bytes of LDS per trial", who, lds_bytes);
+    const bool one_call = a.S <= 4 * kThreads;              // nb <= 4096
+    const bool v3 = one_call && gen_env && atoi(gen_env) == 3;
+    // the second generation's one-call instances address their regions by V2Layout's immediates: sized for nb sockets rather than S
+    int lg;
+    size_t lds_bytes;
+    if (int rc = scldpc::v2_lds_layout(who, a.S, v3 ? 2 : 1, one_call && !v3, cnmode != 0, &a, &lg, &lds_bytes)) return rc;
     a.vn_adj16 = d_vn_adj16; a.cn_adj16 = d_table; a.chan = d_chan_bits;
     a.ntrials = ntrials;
-    a.force_exact = -1;
-    if (const char *v = getenv("SCLDPC_DEBUG_SAMPLER_EXACT_POS")) a.force_exact = atoi(v);     // diagnostics / tests only
 
     using Kern = void (*)(const S2Args);
     static const Kern table[4][3] = {

@@ -16,21 +16,22 @@
 // position go out as 32-bit words.
 // Same law, same keys (word s & 3 of philox4x32_10(s >> 2, p, trial, seed)), rank by key, ties by socket: vn_adj16 and the
 // channel words are bit for bit scldpc_sample_philox_device_adj16's, the table is scldpc_cn_sockets_device's as a set per CN.
-#include "common.h"
-#include "kernel_util.h"
+//
+// What is sampler_v2.hip's line for line lives in sampler_common.h: the histogram words of a thread, the scan, the
+// two-calls-per-thread look-up, the worklist's resolve loop, the steps of a channel word, and on the host the validation, the
+// threshold and the LDS layout.  Here stay rank / dc, the worklist pushes, the exact fallback, the pend queues, edge_of /
+// stage_own and the table's copy-out.
+#include "sampler_common.h"
 #include "philox.h"
-#include <algorithm>
-#include <cstdlib>
 
 namespace {
 
 using scldpc_dev::philox4x32_10;
-using scldpc_dev::wave_inclusive_scan;
 
-constexpr int kThreads = 1024;
+constexpr int kThreads = scldpc::kSamplerThreads;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxDoped = 32;
-constexpr int kWorkCap = 1024;          // keys of buckets that span two CNs, per position
+using scldpc::kMaxDoped;
+using scldpc::kWorkCap;                 // keys of buckets that span two CNs, per position
 constexpr int kMaxSockets = 8192;       // per CN position: two Philox calls per thread
 
 struct SDArgs {
@@ -125,31 +126,7 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
         }
     };
 
-    // hist word while counting = [0:16 | n3:4 | n2:4 | n1:4 | n0:4]; after the scan
-    //   INCL:  [exclusive prefix:12 | i3:4 | i2:4 | i1:4 | i0:4 | 0:4] with ik = n0 + .. + nk;
-    //   else:  [exclusive prefix:16 | n3 n2 n1 n0].   Thread t owns words t*ROWS .. t*ROWS+ROWS-1 (sampler_v2.hip).
-    auto nib_sum = [](uint32_t x) {
-        const uint32_t v = (x & 0x0F0Fu) + ((x >> 4) & 0x0F0Fu);
-        return (v + (v >> 8)) & 0xFFu;
-    };
-    auto load_words = [&](uint32_t (&x)[ROWS]) {
-        if constexpr (ROWS % 4 == 0) {
-#pragma unroll
-            for (int r = 0; r < ROWS / 4; r++) {
-                const uint4 q = reinterpret_cast<const uint4 *>(hist)[tid * (ROWS / 4) + r];
-                x[4 * r] = q.x; x[4 * r + 1] = q.y; x[4 * r + 2] = q.z; x[4 * r + 3] = q.w;
-            }
-        } else if constexpr (ROWS == 2) { const uint2 q = reinterpret_cast<const uint2 *>(hist)[tid]; x[0] = q.x; x[1] = q.y; }
-        else x[0] = hist[tid];
-    };
-    auto store_words = [&](const uint32_t (&x)[ROWS]) {
-        if constexpr (ROWS % 4 == 0) {
-#pragma unroll
-            for (int r = 0; r < ROWS / 4; r++)
-                reinterpret_cast<uint4 *>(hist)[tid * (ROWS / 4) + r] = make_uint4(x[4 * r], x[4 * r + 1], x[4 * r + 2], x[4 * r + 3]);
-        } else if constexpr (ROWS == 2) reinterpret_cast<uint2 *>(hist)[tid] = make_uint2(x[0], x[1]);
-        else hist[tid] = x[0];
-    };
+    // (the layout of a hist word while counting and after the scan: scan_hist, sampler_common.h)
     for (int b = tid; b < nb; b += kThreads) hist[b] = 0;
     if (tid == 0) { wsum[kWaves] = 0; wsum[kWaves + 1] = 0; }
     __syncthreads();
@@ -195,64 +172,8 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
         if (!INCL && crowded >= 15u) wsum[kWaves + 1] = 1u;
         __syncthreads();
 
-        // ---- exclusive scan of the bucket counts (sampler_v2.hip)
-        bool ranked;                                                    // the histogram's ranks hold (else: exact fallback)
-        if constexpr (INCL) {
-            uint32_t x[ROWS], t20[ROWS], tot20 = 0;
-            load_words(x);
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) {
-                x[r] *= 0x111110u;
-                t20[r] = x[r] & 0xF00000u;                              // the word's total << 20
-                tot20 += t20[r];
-            }
-            const uint32_t tot = tot20 >> 20, inc = wave_inclusive_scan(tot);
-            if (lane == 63) wsum[wave] = inc;
-            __syncthreads();
-            uint32_t winc = lane < kWaves ? wsum[lane] : 0u;          // the 16 wave totals: a scan within DPP row 0
-            const uint32_t wt = winc;
-            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x111, 0xF, 0xF, false);
-            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x112, 0xF, 0xF, false);
-            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x114, 0xF, 0xF, false);
-            winc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)winc, 0x118, 0xF, 0xF, false);
-            ranked = __builtin_amdgcn_readlane((int)winc, kWaves - 1) == S;
-            uint32_t pre20 = (inc - tot + (uint32_t)__builtin_amdgcn_readlane((int)(winc - wt), wave)) << 20;
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) {
-                x[r] = (x[r] & 0xFFFF0u) | pre20;
-                pre20 += t20[r];
-            }
-            store_words(x);
-        } else {
-            uint32_t x[ROWS], v[ROWS], tot = 0;
-            load_words(x);
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) v[r] = 0;
-            if constexpr (ROWS % 2 == 0) {                              // two words' counters (16 bits each) per 32-bit lane
-#pragma unroll
-                for (int r = 0; r < ROWS; r += 2) {
-                    const uint32_t y = x[r] | (x[r + 1] << 16);
-                    const uint32_t sb = (y & 0x0F0F0F0Fu) + ((y >> 4) & 0x0F0F0F0Fu);      // four byte sums <= 30
-                    v[r] = (sb & 0xFFu) + ((sb >> 8) & 0xFFu);
-                    v[r + 1] = ((sb >> 16) & 0xFFu) + (sb >> 24);
-                    tot += v[r] + v[r + 1];
-                }
-            } else {
-                v[0] = nib_sum(x[0]);
-                tot = v[0];
-            }
-            const uint32_t inc = wave_inclusive_scan(tot);
-            if (lane == 63) wsum[wave] = inc;
-            __syncthreads();
-            const uint32_t wt = lane < kWaves ? wsum[lane] : 0u;
-            const uint32_t winc = wave_inclusive_scan(wt);
-            uint32_t pre = inc - tot + (uint32_t)__builtin_amdgcn_readlane((int)(winc - wt), wave);
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) { x[r] |= pre << 16; pre += v[r]; }
-            store_words(x);
-        }
-        __syncthreads();
-        if constexpr (!INCL) ranked = wsum[kWaves + 1] == 0u;
+        // ---- exclusive scan of the bucket counts; false: the histogram's ranks do not hold (exact fallback)
+        const bool ranked = scldpc_dev::scan_hist<ROWS, INCL>(hist, wsum, tid, lane, wave, S);
 
         // ---- classify: every live key gets rank g0 + arrival slot, which gives the right CN (rank / dc) when its bucket lies
         //      inside one block of dc ranks.  CN ids go into fix, sockets into the rank-ordered stage; keys of buckets that
@@ -273,15 +194,9 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
                     st[e] = live(e) && small_div<DC>(g0a[e]) != small_div<DC>(g1a[e] - 1u);
                 }
             } else {
-                uint32_t h[E];
-#pragma unroll
-                for (int e = 0; e < E; e++) h[e] = hist[live(e) ? (key[e] >> KSHIFT) >> 2 : 0u];
+                scldpc_dev::bucket_ranges_excl<KSHIFT>(hist, key, live, g0a, g1a);
 #pragma unroll
                 for (int e = 0; e < E; e++) {
-                    const uint32_t k4 = ((key[e] >> KSHIFT) & 3u) * 4u, x = h[e];
-                    const uint32_t below = x & ((1u << k4) - 1u);        // the counters of the word's lower buckets
-                    g0a[e] = (x >> 16) + (below & 0xFu) + ((below >> 4) & 0xFu) + ((below >> 8) & 0xFu);
-                    g1a[e] = g0a[e] + ((x >> k4) & 0xFu);
                     rk[e] = g0a[e] + slot[e];
                     st[e] = live(e) && small_div<DC>(g0a[e]) != small_div<DC>(g1a[e] - 1u);
                 }
@@ -315,7 +230,7 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
                 uint32_t smask = 0;
 #pragma unroll
                 for (int e = 0; e < E; e++) smask |= (st[e] ? 1u : 0u) << e;
-                while (smask) {                                         // rare: one short divergent loop
+                while (smask) {                                         // rare (3 % of the keys): one short divergent loop
                     const uint32_t e = (uint32_t)__ffs((int)smask) - 1u;
                     smask &= smask - 1u;
                     uint32_t ky = key[0], r0 = rk[0], g0 = g0a[0], g1 = g1a[0];
@@ -345,10 +260,7 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
 
         // ---- the worklist: true rank among the bucket mates; counters cleared for the next position
         {
-            uint32_t z[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) z[r] = 0;
-            store_words(z);
+            scldpc_dev::clear_hist_words<ROWS>(hist, tid);
             int nwork = (int)wsum[kWaves];
             const bool exact = !ranked || nwork > kWorkCap || a.force_exact == p || a.force_exact == -2;
             if (exact) {
@@ -370,15 +282,8 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
                     if (live(e)) fix[sock(e)] = (uint16_t)small_div<DC>(xr[e]);
                 if constexpr (CNMODE != 0) stage_own(p, ends, xr);
             }
-            for (int w = tid; w < nwork; w += kThreads) {
-                const uint32_t ea = wl[2 * w], pk = wl[2 * w + 1];
-                uint32_t r = ea & 0xFFFFu;                              // its rank: the first rank + the mates below it
-#pragma unroll 1
-                for (uint32_t m = ea & 0xFFFFu; m < (ea >> 16); m++) r += gpk[m] < pk;     // (itself included: not below)
-                const uint32_t sck = pk & ((1u << LG) - 1u);
-                if constexpr (CNMODE != 0) stage[r] = stage_entry(p, ends, sck);
-                fix[sck] = (uint16_t)small_div<DC>(r);
-            }
+            scldpc_dev::resolve_worklist<LG, CNMODE != 0>(nwork, tid, wl, gpk, stage, fix, [&](uint32_t sck) { return stage_entry(p, ends, sck); },
+                                                          [](uint32_t r) { return small_div<DC>(r); });
         }
         if (p + 1 < a.D) {
             // the round keys are recomputed from the seed here rather than kept in twenty SGPRs across the whole loop
@@ -448,14 +353,11 @@ __global__ __launch_bounds__(kThreads, KMAX == 1 ? 8 : 4) __attribute__((amdgpu_
             uint32_t r[4];
             philox4x32_10((uint32_t)(w * 8 + c), 0x80000000u, t_lo, t_hi, a.seed_lo, a.seed_hi, r);
 #pragma unroll
-            for (int u = 0; u < 4; u++) word |= (uint32_t)((r[u] >> 1) < a.thresh) << (c * 4 + u);
+            for (int u = 0; u < 4; u++) word |= scldpc_dev::channel_erased(r[u], a.thresh) << (c * 4 + u);
         }
         const int j0 = w * 32;
-        if (j0 + 32 > a.n) word &= (1u << (a.n - j0)) - 1u;
-        for (int d = 0; d < a.ndoped; d++) {                            // doped positions are never erased (BPF:1566-1573)
-            const int lo = max(a.doped[d] * a.vns_pos, j0) - j0, hi = min((a.doped[d] + 1) * a.vns_pos, j0 + 32) - j0;
-            if (lo < hi) word &= ~(((hi - lo) == 32 ? 0xFFFFFFFFu : ((1u << (hi - lo)) - 1u)) << lo);
-        }
+        word = scldpc_dev::channel_tail(word, j0, a.n);
+        for (int d = 0; d < a.ndoped; d++) word = scldpc_dev::channel_undope(word, j0, a.doped[d], a.vns_pos);
         chan[w] = word;
     }
 }
@@ -478,49 +380,23 @@ int launch_v2_deg(const char *who, const scldpc_code_params *p, uint64_t seed, u
                   int32_t ndoped, const int32_t *doped_positions, uint16_t *d_vn_adj16, uint16_t *d_table, uint32_t *d_chan_bits,
                   void *stream)
 {
-    if (ntrials < 0 || (ntrials > 0 && (!d_vn_adj16 || !d_chan_bits)))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
-    if (ndoped < 0 || ndoped > kMaxDoped || (ndoped > 0 && !doped_positions))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: 0 <= ndoped <= %d", who, kMaxDoped);
-    if (!(eps >= 0.0 && eps <= 1.0))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: eps=%g outside [0,1]", who, eps);
+    SDArgs a{};
+    if (int rc = scldpc::check_sample_call(who, p, ntrials < 0 || (ntrials > 0 && (!d_vn_adj16 || !d_chan_bits)), ntrials, eps,
+                                           ndoped, doped_positions, &a.ndoped, a.doped)) return rc;
     if (ntrials == 0) return SCLDPC_OK;
     const bool table = d_table != nullptr;
 
-    SDArgs a{};
     a.L = p->L; a.cns_pos = p->cns_pos; a.vns_pos = p->vns_pos;
     a.n = scldpc::n_of(p); a.S = p->cns_pos * p->dc; a.D = p->L + p->dv - 1; a.nw = scldpc::nw_of(p);
-    int lg = 10;                                    // nb = power of two >= max(S, kThreads)
-    while ((1 << lg) < a.S) lg++;
-    a.nb = 1 << lg;
-    a.ndoped = ndoped;
-    for (int d = 0; d < ndoped; d++) {
-        if (doped_positions[d] < 0 || doped_positions[d] >= p->L)
-            return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "doped position %d outside [0,%d)", doped_positions[d], p->L);
-        a.doped[d] = doped_positions[d];
-    }
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
     a.trial0 = trial0;
-    {   // erased iff r/RAND_MAX < eps with r = 31-bit draw  ⇔  r < ceil(eps * RAND_MAX)   (BPF:370,1554-1562)
-        const double x = eps * 2147483647.0;
-        double c = (double)(uint64_t)x;
-        if (c < x) c += 1.0;
-        a.thresh = (uint32_t)c;
-    }
-    int off = (a.nb + 3) & ~3;
-    a.off_gpk = off;   off += (a.S + 3) & ~3;
-    a.off_fix = off;   off += (a.S / 2 + 3) & ~3;           // S uint16 (S % 4 == 2: and the two dead ids of the last call)
-    a.off_stage = off; off += table ? (a.S / 2 + 3) & ~3 : 0;
-    a.off_wsum = off;  off += 32 + 2 * kWorkCap;
-    size_t lds_bytes = 4u * (size_t)off;
-    lds_bytes = std::min(lds_bytes + scldpc::debug_lds_pad("SAMPLER"), std::max(lds_bytes, (size_t)scldpc::kMaxLdsBytes));
-    if (lds_bytes > (size_t)scldpc::kMaxLdsBytes)
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %zu bytes of LDS per trial", who, lds_bytes);
+    a.thresh = scldpc::erasure_threshold(eps);
+    int lg;                                         // one histogram, regions sized by S
+    size_t lds_bytes;
+    if (int rc = scldpc::v2_lds_layout(who, a.S, 1, false, table, &a, &lg, &lds_bytes)) return rc;
     a.vn_adj16 = d_vn_adj16; a.cn_sock16 = d_table; a.chan = d_chan_bits;
     const uintptr_t taddr = reinterpret_cast<uintptr_t>(d_table);
     a.tabw = ((a.S & 3) == 0 && (taddr & 7u) == 0) ? 8 : (taddr & 3u) == 0 ? 4 : 2;
-    a.force_exact = -1;
-    if (const char *v = getenv("SCLDPC_DEBUG_SAMPLER_EXACT_POS")) a.force_exact = atoi(v);     // diagnostics / tests only
 
     const int rows = a.nb / kThreads;                       // 1, 2, 4 (one Philox call per thread) or 8 (two)
     void (*kern)(const SDArgs) = p->dv == 3 ? (table ? deg_kernel<3, 6, 2>(rows) : deg_kernel<3, 6, 0>(rows))

@@ -36,6 +36,7 @@
 #include "common.h"
 #include "kernel_util.h"
 #include "philox.h"
+#include "sampler_common.h"
 #include "table_rows.h"
 #include <algorithm>
 #include <cstdlib>
@@ -1037,12 +1038,7 @@ static int stream_run(const scldpc_code_params *p, int32_t nstreams, uint64_t se
         a.doped[d] = doped_positions[d];
     }
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.sid0 = stream0;
-    {
-        const double x = eps * 2147483647.0;
-        double c = (double)(uint64_t)x;
-        if (c < x) c += 1.0;
-        a.thresh = (uint32_t)c;
-    }
+    a.thresh = scldpc::erasure_threshold(eps);
     make_state_layout(p, W, &a.lay);
     a.state = static_cast<char *>(d_state); a.counters_out = reinterpret_cast<long long *>(d_counters); a.trace = d_trace;
     a.ext_inter = d_ext_inter; a.ext_chan = d_ext_chan; a.ext_npos = ext_npos; a.ext_pos0 = ext_pos0;
