@@ -1,4 +1,5 @@
-// CN-word policies shared by the flooding decoders (full_bp.hip, sw_bp.hip): how one check node's residual state —
+// CN-word policies shared by the flooding decoders (full_bp.hip, sw_bp.hip, peel_sweep.hip; flood_common.h holds what they
+// share around the words): how one check node's residual state —
 // cnt = #erased neighbours and a fold of their ids (== the id when cnt == 1) — is stored and updated.
 //   WideT<G> 32 bit [cnt:4 | deg:4 | Σ global VN id:24]; G = true: the words live in a global-memory workspace
 //   Packed   16 bit [cnt:4 | ⊕ local VN id:12], two CNs per 32-bit word; needs dv·vns_pos <= 4096
@@ -24,7 +25,6 @@ template <bool G>
 struct WideT {
     static constexpr bool kGlobal = G;
     static constexpr bool kHasDeg = true;          // the CN degree rides in the word (trajectory mode)
-    static constexpr bool kPacked16 = false;
     static __host__ __device__ int lds_words(int nk) { return G ? 0 : nk; }
     static __host__ __device__ int words(int nk) { return nk; }
     static __device__ __forceinline__ uint32_t ld(const uint32_t *st, int c)
@@ -59,10 +59,10 @@ struct WideT {
 using Wide = WideT<false>;
 using WideG = WideT<true>;
 
+// (peel_fixpoint.h — full_bp_fixpoint_kernel only — updates these words in its own order, fold before count: see there)
 struct Packed {     // two CNs per 32-bit word; CN c lives in half (c & 1) of word c >> 1
     static constexpr bool kGlobal = false;
     static constexpr bool kHasDeg = false;         // trajectory mode keeps the few degrees it needs in a side array
-    static constexpr bool kPacked16 = true;        // peel_fixpoint.h applies
     static __host__ __device__ int lds_words(int nk) { return (nk + 1) / 2; }
     static __host__ __device__ int words(int nk) { return (nk + 1) / 2; }
     static __device__ __forceinline__ void add(uint32_t *st, int c, const Vn &v, int i, int V, bool erased, bool)

@@ -21,9 +21,7 @@
 //   deg_1_iter (BPF:969-978) needs no extra pass:  |F(t+1)| = pushes(t) − (drops_1→0(t) − |F(t)|).
 // Afterwards the size-2 stopping-set expurgation (BPF:1067-1133) from the same CN words: an erased VN a
 // belongs to such a pair iff every one of its CNs has cnt == 2 and the same partner, in a's position.
-#include "common.h"
-#include "kernel_util.h"
-#include "cn_words.h"
+#include "flood_common.h"
 #include "peel_fixpoint.h"
 
 namespace {
@@ -33,10 +31,7 @@ using namespace scldpc_dev;
 // per-iteration counters, rotated three ways so that one barrier per iteration is enough
 enum { S_PUSH = 0, S_DROP = 3, S_REM = 6, S_OVF = 9, S_NE = 12, S_EXTRA0 = 13, S_VALID = 14, S_NSCAL = 16 };
 
-struct Layout {             // offsets in 32-bit words into dynamic LDS
-    int cn_state, U, fbits, q0, q1, pos_cnt, pos_ss, scal, total;
-    int qcap, nw;
-};
+using Layout = scldpc::FloodLayout;      // pos_a = erased VNs per position, pos_b = those in size-2 stopping sets
 
 struct Args : Geo {             // Geo: vns_pos, magic_v, magic_c
     int dv, L, cns_pos, n, nk, cn_lim, max_it, rows_cap;
@@ -63,8 +58,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
     uint32_t *U = lds + a.lay.U;
     uint32_t *fbits = lds + a.lay.fbits;
     uint32_t *q[2] = {lds + a.lay.q0, lds + a.lay.q1};
-    int *pos_cnt = reinterpret_cast<int *>(lds + a.lay.pos_cnt);
-    int *pos_ss = reinterpret_cast<int *>(lds + a.lay.pos_ss);
+    int *pos_cnt = reinterpret_cast<int *>(lds + a.lay.pos_a);
+    int *pos_ss = reinterpret_cast<int *>(lds + a.lay.pos_b);
     int *scal = reinterpret_cast<int *>(lds + a.lay.scal);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -72,18 +67,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
     const int V = a.vns_pos;
     const char *adj = static_cast<const char *>(a.vn_adj) + (size_t)trial * n * dv * (A16 ? 2 : 4);
     const uint32_t *ch = a.chan + (size_t)trial * nw;
-    auto make_vn = [&](int j) { Vn v; v.j = j; v.pos = (int)__umulhi((uint32_t)j, a.magic_v); v.t = j - v.pos * V; return v; };
 
     // ---- load channel bits, clear CN words -------------------------------------------------
     const bool prebuilt = ST::kGlobal && a.prebuilt;
     if (!prebuilt) for (int c = tid; c < ST::words(nk); c += BLOCK) cn_state[c] = 0;
-    int ne_local = 0;
-    for (int w = tid; w < nw; w += BLOCK) {
-        uint32_t x = ch[w];
-        if (w == nw - 1 && (n & 31)) x &= (1u << (n & 31)) - 1u;
-        U[w] = x;
-        ne_local += __popc(x);
-    }
+    int ne_local = load_channel<BLOCK>(ch, U, nw, n, tid);
     if (tid < S_NSCAL) scal[tid] = 0;
     for (int i = tid; i < a.L; i += BLOCK) { pos_cnt[i] = 0; pos_ss[i] = 0; }
     __syncthreads();
@@ -107,34 +95,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
     }
 
     // ---- build: every erased VN adds itself to its dv CNs (TRAJ: every VN also adds to deg) ----
-    // Loads are unconditional so that each wave instruction reads 1 KiB contiguous (dv = 4).
-    for (int j0 = prebuilt ? n : tid; j0 < n; j0 += 4 * BLOCK) {
-        int32_t c[4][8];
-        bool er[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int j = j0 + u * BLOCK;
-            er[u] = false;
-            if (j < n) {
-                load_adj<DV, A16>(adj, dv, j, (int)__umulhi((uint32_t)j, a.magic_v), a.cns_pos, c[u]);
-                er[u] = (U[j >> 5] >> (j & 31)) & 1u;
+    build_cn_words<ST, DV, A16, BLOCK, TRAJ>(a, adj, dv, a.cns_pos, n, prebuilt ? n : tid, U, cn_state,
+                                             [&](const Vn &, const int32_t (&c)[8], bool) {
+        if constexpr (kSideDeg) {
+            for (int i = 0; i < dv; i++) {
+                const int b = boundary(c[i]);
+                if (b >= 0) atomicAdd(&degb[b >> 2], 1u << ((b & 3) * 8));
             }
         }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int j = j0 + u * BLOCK;
-            if (j < n && (TRAJ || er[u])) {
-                const Vn v = make_vn(j);
-                for (int i = 0; i < dv; i++) {
-                    ST::add(cn_state, c[u][i], v, i, V, er[u], TRAJ);
-                    if constexpr (kSideDeg) {
-                        const int b = boundary(c[u][i]);
-                        if (b >= 0) atomicAdd(&degb[b >> 2], 1u << ((b & 3) * 8));
-                    }
-                }
-            }
-        }
-    }
+    });
     __syncthreads();
     STAMP(1);                                                       // build
 
@@ -153,7 +122,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
         auto release = [&](int c) {
             const int j = ST::lone_vn(cn_state, c, a);
             if (j < 0) return;                                      // its VN was just released via another CN
-            const Vn v = make_vn(j);
+            const Vn v = make_vn(a, j);
             int32_t cc[8];
             load_adj<DV, A16>(adj, dv, j, v.pos, a.cns_pos, cc);    // issued before the ownership test: its latency
             const uint32_t bit = 1u << (j & 31);                    // overlaps the LDS round trip below
@@ -181,8 +150,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
         if (scan) {
             // snapshot {c < cn_lim : cnt == 1} first: this round's releases must not promote CNs into it
             int valid = 0, extra = 0;
-            for (int base = 0; base < cn_lim; base += BLOCK) {
-                const int c = base + tid;
+            snapshot_frontier<BLOCK>(fbits, 0, cn_lim, tid, [&](int c) {
                 bool v = false;
                 if (c < cn_lim) {
                     const uint32_t k = ST::cnt(cn_state, c);
@@ -194,13 +162,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
                         extra += (k == 0u && d == 1u);
                     }
                 }
-                const unsigned long long m = __ballot(v);
-                if (c - lane < cn_lim) {                            // this wave's 64-CN slice starts inside the range
-                    if (lane == 0) fbits[c >> 5] = (uint32_t)m;
-                    if (lane == 32) fbits[c >> 5] = (uint32_t)(m >> 32);
-                }
                 valid += v;
-            }
+                return v;
+            });
             if (iter == 0) {
                 valid = wave_sum(valid);
                 if (lane == 0 && valid) atomicAdd(&scal[S_VALID], valid);
@@ -211,10 +175,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
             }
             __syncthreads();
             if (iter == 0) nfront = scal[S_VALID];
-            for (int base = 0; base < cn_lim; base += BLOCK) {
-                const int c = base + tid;
-                if (c < cn_lim && ((fbits[c >> 5] >> (c & 31)) & 1u)) release(c);
-            }
+            sweep_frontier<BLOCK>(fbits, 0, cn_lim, tid, release);
         } else {
             for (int k = tid; k < ncur; k += BLOCK) release((int)qc[k]);
         }
@@ -272,49 +233,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
     STAMP(5);
 
     // ---- per-position erasure counts + size-2 stopping sets (BPF:1067-1133) -----------------
-    if (ne > 0) {
-        for (int w = tid; w < nw; w += BLOCK) {
-            uint32_t x = U[w];
-            while (x) {
-                const int b = __ffs((int)x) - 1;
-                x &= x - 1;
-                const Vn v = make_vn(w * 32 + b);
-                atomicAdd(&pos_cnt[v.pos], 1);
-                int32_t cc[8];
-                load_adj<DV, A16>(adj, dv, v.j, v.pos, a.cns_pos, cc);
-                bool pair = true;
-                int partner = -1;
-                for (int i = 0; i < dv; i++) {
-                    const int b2 = ST::partner(cn_state, cc[i], v, i, a);
-                    if (b2 < 0 || (i > 0 && b2 != partner)) { pair = false; break; }
-                    partner = b2;
-                }
-                if (pair && (int)__umulhi((uint32_t)partner, a.magic_v) == v.pos) atomicAdd(&pos_ss[v.pos], 1);
-            }
-        }
-    }
+    if (ne > 0)
+        count_size2_sets<ST, DV, A16, BLOCK>(a, adj, dv, a.cns_pos, cn_state, U, nw, tid, pos_ss,
+                                             [&](const Vn &v) { atomicAdd(&pos_cnt[v.pos], 1); });
     __syncthreads();
     STAMP(6);                                                       // final counts + expurgation
     STAMP_FLUSH();
-    if (a.erased_out)
-        for (int w = tid; w < nw; w += BLOCK) a.erased_out[(size_t)trial * nw + w] = U[w];
-    if (tid == 0) {
-        int be = 0, ee = 0, bee = 0;
-        for (int pos = 0; pos < a.L; pos++) {
-            if (pos_cnt[pos] > 0) be++;
-            const int e = pos_cnt[pos] - pos_ss[pos];
-            if (e > 0 && bee == 0) { ee = e; bee = 1; }             // only the FIRST such position (BPF:1126-1132)
-        }
-        int32_t *o = a.counters + (size_t)trial * SCLDPC_NCOUNTERS;
-        o[SCLDPC_C_NUM_ERASURES] = ne;
-        o[SCLDPC_C_NUM_BLOCKS_ERR] = be;
-        o[SCLDPC_C_NUM_ERASURES_EXP] = ee;
-        o[SCLDPC_C_NUM_BLOCKS_ERR_EXP] = bee;
-        o[SCLDPC_C_NUM_ERASURES_P1] = 0;
-        o[SCLDPC_C_ITERATIONS] = rows_done;
-        o[SCLDPC_C_STATUS] = status;
-        o[SCLDPC_C_CHANNEL_ERASURES] = nch;
-    }
+    store_bits<BLOCK>(a.erased_out, trial, U, nw, tid);
+    if (tid == 0)
+        write_full_bp_counters(a.counters + (size_t)trial * SCLDPC_NCOUNTERS, pos_cnt, pos_ss, a.L, ne, rows_done, status, nch);
 }
 
 // =================================================================================================
@@ -341,8 +268,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
     uint32_t *U = lds + a.lay.U;
     uint32_t *fbits = lds + a.lay.fbits;
     uint32_t *q[2] = {lds + a.lay.q0, lds + a.lay.q1};
-    int *pos_cnt = reinterpret_cast<int *>(lds + a.lay.pos_cnt);
-    int *pos_ss = reinterpret_cast<int *>(lds + a.lay.pos_ss);
+    int *pos_cnt = reinterpret_cast<int *>(lds + a.lay.pos_a);
+    int *pos_ss = reinterpret_cast<int *>(lds + a.lay.pos_b);
     int *scal = reinterpret_cast<int *>(lds + a.lay.scal);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -350,52 +277,23 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
     const int V = a.vns_pos, C = a.cns_pos, L = a.L;
     const char *adj = static_cast<const char *>(a.vn_adj) + (size_t)trial * n * DV * (A16 ? 2 : 4);
     const uint32_t *ch = a.chan + (size_t)trial * nw;
-    auto make_vn = [&](int j) { Vn v; v.j = j; v.pos = (int)__umulhi((uint32_t)j, a.magic_v); v.t = j - v.pos * V; return v; };
 
-    const bool prebuilt = ST::kGlobal && a.prebuilt;
-    if (!prebuilt) for (int c = tid; c < ST::words(nk); c += BLOCK) cn_state[c] = 0;
-    int ne_local = 0;
-    for (int w = tid; w < nw; w += BLOCK) {
-        uint32_t x = ch[w];
-        if (w == nw - 1 && (n & 31)) x &= (1u << (n & 31)) - 1u;
-        U[w] = x;
-        ne_local += __popc(x);
-    }
+    for (int c = tid; c < ST::words(nk); c += BLOCK) cn_state[c] = 0;
+    int ne_local = load_channel<BLOCK>(ch, U, nw, n, tid);
     if (tid < S_NSCAL) scal[tid] = 0;
     for (int i = tid; i < L; i += BLOCK) { pos_cnt[i] = 0; pos_ss[i] = 0; }
     __syncthreads();
     ne_local = wave_sum(ne_local);
     if (lane == 0 && ne_local) atomicAdd(&scal[S_NE], ne_local);
-    for (int j0 = prebuilt ? n : tid; j0 < n; j0 += 4 * BLOCK) {   // build, as in full_bp_kernel
-        int32_t c[4][8];
-        bool er[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int j = j0 + u * BLOCK;
-            er[u] = false;
-            if (j < n) {
-                load_adj<DV, A16>(adj, DV, j, (int)__umulhi((uint32_t)j, a.magic_v), C, c[u]);
-                er[u] = (U[j >> 5] >> (j & 31)) & 1u;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int j = j0 + u * BLOCK;
-            if (j < n && er[u]) {
-                const Vn v = make_vn(j);
-#pragma unroll
-                for (int i = 0; i < DV; i++) ST::add(cn_state, c[u][i], v, i, V, true, false);
-            }
-        }
-    }
+    build_cn_words<ST, DV, A16, BLOCK, false>(a, adj, DV, C, n, tid, U, cn_state, [](const Vn &, const int32_t (&)[8], bool) {});
     __syncthreads();
     STAMP_DECL
     STAMP(0);                                                       // channel + build
     const int nch = scal[S_NE];
 
     int removed = 0;
-    PeelCtx x{L, V, C, n, cn_lim, qcap, adj, cn_state, U, fbits, q[0], q[1], &scal[S_PUSH], &scal[S_OVF]};
-    const int rounds = peel_to_fixpoint<A16, BLOCK>(a, x, removed, [](int, int, bool one) { return one; });
+    PeelCtx x{L, V, C, cn_lim, qcap, adj, cn_state, U, fbits, q[0], q[1], &scal[S_PUSH], &scal[S_OVF]};
+    const int rounds = peel_to_fixpoint<A16, BLOCK>(a, x, removed);
     STAMP(1);                                                       // peeling (barrier rounds + barrier-free phase)
     removed = wave_sum(removed);
     if (lane == 0 && removed) atomicAdd(&scal[S_REM], removed);
@@ -403,74 +301,21 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(72))) void fu
     const int ne = nch - scal[S_REM];
 
     // ---- per-position erasure counts + size-2 stopping sets (BPF:1067-1133), as in full_bp_kernel ----
-    if (ne > 0) {
-        for (int w = tid; w < nw; w += BLOCK) {
-            uint32_t x = U[w];
-            while (x) {
-                const int b = __ffs((int)x) - 1;
-                x &= x - 1;
-                const Vn v = make_vn(w * 32 + b);
-                atomicAdd(&pos_cnt[v.pos], 1);
-                int32_t cc[8];
-                load_adj<DV, A16>(adj, DV, v.j, v.pos, C, cc);
-                bool pair = true;
-                int partner = -1;
-                for (int i = 0; i < DV; i++) {
-                    const int b2 = ST::partner(cn_state, cc[i], v, i, a);
-                    if (b2 < 0 || (i > 0 && b2 != partner)) { pair = false; break; }
-                    partner = b2;
-                }
-                if (pair && (int)__umulhi((uint32_t)partner, a.magic_v) == v.pos) atomicAdd(&pos_ss[v.pos], 1);
-            }
-        }
-    }
+    if (ne > 0)
+        count_size2_sets<ST, DV, A16, BLOCK>(a, adj, DV, C, cn_state, U, nw, tid, pos_ss,
+                                             [&](const Vn &v) { atomicAdd(&pos_cnt[v.pos], 1); });
     __syncthreads();
     STAMP(2);                                                       // final counts + expurgation
     STAMP_FLUSH();
-    if (a.erased_out)
-        for (int w = tid; w < nw; w += BLOCK) a.erased_out[(size_t)trial * nw + w] = U[w];
-    if (tid == 0) {
-        int be = 0, ee = 0, bee = 0;
-        for (int pos = 0; pos < L; pos++) {
-            if (pos_cnt[pos] > 0) be++;
-            const int e = pos_cnt[pos] - pos_ss[pos];
-            if (e > 0 && bee == 0) { ee = e; bee = 1; }             // only the FIRST such position (BPF:1126-1132)
-        }
-        int32_t *o = a.counters + (size_t)trial * SCLDPC_NCOUNTERS;
-        o[SCLDPC_C_NUM_ERASURES] = ne;
-        o[SCLDPC_C_NUM_BLOCKS_ERR] = be;
-        o[SCLDPC_C_NUM_ERASURES_EXP] = ee;
-        o[SCLDPC_C_NUM_BLOCKS_ERR_EXP] = bee;
-        o[SCLDPC_C_NUM_ERASURES_P1] = 0;
-        o[SCLDPC_C_ITERATIONS] = rounds;                            // barrier rounds, NOT flooding iterations
-        o[SCLDPC_C_STATUS] = 0;
-        o[SCLDPC_C_CHANNEL_ERASURES] = nch;
-    }
+    store_bits<BLOCK>(a.erased_out, trial, U, nw, tid);
+    if (tid == 0)                                                   // ITERATIONS = barrier rounds, NOT flooding iterations
+        write_full_bp_counters(a.counters + (size_t)trial * SCLDPC_NCOUNTERS, pos_cnt, pos_ss, L, ne, rounds, 0, nch);
 }
 
-// LDS carve.  `budget` = bytes this workgroup may take (160 KiB alone on the CU, 80 KiB when two share it).
-template <class ST>
-int make_layout(const scldpc_code_params *p, int budget_bytes, Layout *lay)
+// what a workgroup keeps in LDS for a CN-word form (scldpc::FloodWords)
+scldpc::FloodRegions regions_of(const scldpc_code_params *p, int words)
 {
-    const int n = scldpc::n_of(p), nk = scldpc::nk_of(p);
-    int off = 0;
-    auto take = [&](int words) { int o = off; off += (words + 3) & ~3; return o; };   // keep 16-B alignment
-    lay->nw = (n + 31) / 32;
-    lay->cn_state = take(ST::lds_words(nk));
-    lay->U = take(lay->nw);
-    lay->fbits = take(((nk + 63) / 64) * 2);
-    lay->pos_cnt = take(p->L);
-    lay->pos_ss = take(p->L);
-    lay->scal = take(S_NSCAL);
-    const int left = budget_bytes / 4 - off;
-    int qcap = (left / 2) & ~3;
-    if (qcap > 8192) qcap = 8192;
-    if (qcap < 256) return -1;
-    lay->qcap = qcap;
-    lay->q0 = take(qcap);
-    lay->q1 = take(qcap);
-    lay->total = off;
-    return 0;
+    return {scldpc::flood_cn_lds_words(words, scldpc::nk_of(p)), false, p->L, p->L, 256};
 }
 
 bool packed_ok(const scldpc_code_params *p)
@@ -482,12 +327,13 @@ bool packed_ok(const scldpc_code_params *p)
 
 extern "C" int64_t scldpc_full_bp_lds_bytes(const scldpc_code_params *p)
 {
-    if (int rc = scldpc::check_params(p)) return rc;
+    using namespace scldpc;
+    if (int rc = check_params(p)) return rc;
     Layout lay;
-    if (packed_ok(p) && make_layout<Packed>(p, scldpc::kMaxLdsBytes / 2 - 1024, &lay) == 0) return 4ll * lay.total;
-    if (make_layout<Wide>(p, scldpc::kMaxLdsBytes, &lay) == 0) return 4ll * lay.total;
-    if (make_layout<WideG>(p, scldpc::kMaxLdsBytes, &lay) == 0) return 4ll * lay.total;   // CN words in the workspace
-    return 4ll * scldpc::nw_of(p) + (64 << 10);
+    if (packed_ok(p) && flood_carve(p, regions_of(p, kWordsPacked), kHalfLdsBytes, &lay) == 0) return 4ll * lay.total;
+    if (flood_carve(p, regions_of(p, kWordsWide), kMaxLdsBytes, &lay) == 0) return 4ll * lay.total;
+    if (flood_carve(p, regions_of(p, kWordsGlobal), kMaxLdsBytes, &lay) == 0) return 4ll * lay.total;   // CN words in the workspace
+    return 4ll * nw_of(p) + (64 << 10);
 }
 
 static int launch_full_bp(const scldpc_code_params *p, int32_t ntrials, const void *d_vn_adj, bool adj16,
@@ -495,73 +341,46 @@ static int launch_full_bp(const scldpc_code_params *p, int32_t ntrials, const vo
                           int32_t *d_counters, int32_t *d_rows, int32_t rows_cap,
                           uint32_t *d_erased_bits, const scldpc::Scratch &scratch, void *stream)
 {
-    if (int rc = scldpc::check_params(p)) return rc;
-    if (scratch.query) *scratch.query = 0;
-    if (!scratch.query && (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj || !d_chan_bits))))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_device: null buffer or negative ntrials");
+    using namespace scldpc;
+    const char *who = "scldpc_full_bp_device";
+    if (int rc = check_params(p)) return rc;
+    if (int rc = flood_check_call(who, scratch, ntrials, !d_counters || !d_vn_adj || !d_chan_bits)) return rc;
     if (d_rows && rows_cap <= 0)
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_device: d_rows given but rows_cap <= 0");
+        return set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_device: d_rows given but rows_cap <= 0");
     if (ntrials <= 0) return SCLDPC_OK;
-    const int n = scldpc::n_of(p), nk = scldpc::nk_of(p);
-    if (p->dc > 15 || p->dv > 8 || (int64_t)p->dc * n >= (1ll << kDegShift))
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE,
-                                 "scldpc_full_bp_device: needs dc <= 15, dv <= 8, dc*n < 2^24 (got dc=%d dv=%d n=%d)",
-                                 p->dc, p->dv, n);
+    const int n = n_of(p), nk = nk_of(p);
+    if (!flood_limits_ok(p))
+        return set_error(SCLDPC_ERR_TOO_LARGE,
+                         "scldpc_full_bp_device: needs dc <= 15, dv <= 8, dc*n < 2^24 (got dc=%d dv=%d n=%d)", p->dc, p->dv, n);
     const bool traj = d_rows != nullptr;
     Args a{};
-    // two workgroups per CU with the packed CN words when the ensemble allows it
-    // (trajectory rows: the side array of boundary degrees must fit queue 1)
-    const bool packed = packed_ok(p) && make_layout<Packed>(p, scldpc::kMaxLdsBytes / 2 - 1024, &a.lay) == 0 &&
-                        (!traj || 2 * (p->dv - 1) * p->cns_pos <= 4 * a.lay.qcap);
-    bool global_ws = false;
-    // Wide words: two workgroups per CU when everything (with queues of >= 1024 entries) fits half the LDS, else one
-    auto fits = [&](auto tag, Layout *lay) {
-        using ST = decltype(tag);
-        if (make_layout<ST>(p, scldpc::kMaxLdsBytes / 2 - 1024, lay) == 0 && lay->qcap >= 1024) return true;
-        return make_layout<ST>(p, scldpc::kMaxLdsBytes, lay) == 0;
+    int words;
+    auto carve = [&](int w) {
+        // packed words: always two workgroups per CU (trajectory rows: the side array of boundary degrees must fit queue 1)
+        if (w == kWordsPacked)
+            return flood_carve(p, regions_of(p, w), kHalfLdsBytes, &a.lay) == 0 &&
+                   (!traj || 2 * (p->dv - 1) * p->cns_pos <= 4 * a.lay.qcap);
+        return flood_carve_roomy(p, regions_of(p, w), &a.lay);
     };
-    if (!packed && !fits(Wide{}, &a.lay)) {
-        // CN words to a global workspace; the VN bitmap, scan bitmap and queues must still fit the LDS
-        if (!fits(WideG{}, &a.lay))
-            return scldpc::set_error(SCLDPC_ERR_TOO_LARGE,
-                                     "scldpc_full_bp_device: n=%d VN bits + nk=%d scan bits do not fit 160 KiB of LDS", n, nk);
-        global_ws = true;
-        const size_t need = (size_t)ntrials * nk * sizeof(uint32_t);
-        if (scratch.query) { *scratch.query = need; return SCLDPC_OK; }
-        void *ws = nullptr;
-        if (int rc = scldpc::take_scratch("scldpc_full_bp_device", scratch, need, &ws)) return rc;
-        a.ws = static_cast<uint32_t *>(ws);
-    }
-    if (scratch.query) return SCLDPC_OK;
-    a.dv = p->dv; a.L = p->L; a.vns_pos = p->vns_pos; a.cns_pos = p->cns_pos; a.n = n; a.nk = nk;
+    if (int rc = flood_choose_words(who, "scldpc_full_bp_device: n=%d VN bits + nk=%d scan bits do not fit 160 KiB of LDS", p,
+                                    ntrials, scratch, packed_ok(p), carve, &words, &a.ws)) return rc;
+    if (words == kWordsQueryDone) return SCLDPC_OK;
+    a.dv = p->dv; a.L = p->L; a.cns_pos = p->cns_pos; a.n = n; a.nk = nk;
     a.cn_lim = is_term ? nk : p->L * p->cns_pos;                    // BPT:944-948
     a.max_it = max_it; a.rows_cap = traj ? rows_cap : 0;
-    if (!scldpc::magic_of(p->vns_pos, n, &a.magic_v) || !scldpc::magic_of(p->cns_pos, nk, &a.magic_c))
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_full_bp_device: reciprocal division inexact for this size");
+    if (int rc = flood_geo("scldpc_full_bp_device: reciprocal division inexact for this size", p, n, &a)) return rc;
     a.vn_adj = d_vn_adj; a.chan = d_chan_bits; a.counters = d_counters; a.rows = d_rows;
     a.erased_out = d_erased_bits;
 
-    void (*kern)(const Args) = nullptr;
-    int block = 1024;
-    const bool d4 = p->dv == 4;
-#define PICK(ST, TRAJ, BLK) (d4 ? (adj16 ? full_bp_kernel<ST, TRAJ, 4, true, BLK> : full_bp_kernel<ST, TRAJ, 4, false, BLK>) \
-                                : (adj16 ? full_bp_kernel<ST, TRAJ, 0, true, BLK> : full_bp_kernel<ST, TRAJ, 0, false, BLK>))
-    if (packed) kern = traj ? PICK(Packed, true, 1024) : PICK(Packed, false, 1024);
-    else if (global_ws) kern = traj ? PICK(WideG, true, 1024) : PICK(WideG, false, 1024);
-    else if (traj) kern = PICK(Wide, true, 1024);
-    else kern = PICK(Wide, false, 1024);
-#undef PICK
-    // the workspace's CN words through an LDS ring (cn_build.hip) instead of one global atomic per edge
-    if (global_ws && adj16) {
-        bool pre = true;
-        if (const char *v = getenv("SCLDPC_DEBUG_FULLBP_PREBUILD")) pre = atoi(v) != 0;                     // A/B, tests
-        a.prebuilt = pre && scldpc::cn_build_launch(p, ntrials, static_cast<const uint16_t *>(d_vn_adj), d_chan_bits, a.ws, traj, stream) ? 1 : 0;
-    }
-    const size_t lds_bytes = 4u * (size_t)a.lay.total;
-    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
-    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(block), lds_bytes, static_cast<hipStream_t>(stream), a);
-    SCLDPC_HIP_CHECK(hipGetLastError());
-    return SCLDPC_OK;
+    void (*kern)(const Args) = flood_pick(words, p->dv == 4, adj16, [&](auto st, auto dv, auto a16) -> void (*)(const Args) {
+        using ST = decltype(st);
+        constexpr int DV = decltype(dv)::value;
+        constexpr bool A16 = decltype(a16)::value;
+        return traj ? full_bp_kernel<ST, true, DV, A16, 1024> : full_bp_kernel<ST, false, DV, A16, 1024>;
+    });
+    if (words == kWordsGlobal && adj16)
+        a.prebuilt = flood_prebuild("SCLDPC_DEBUG_FULLBP_PREBUILD", p, ntrials, d_vn_adj, d_chan_bits, a.ws, traj, stream);
+    return flood_launch(kern, ntrials, 1024, stream, a);
 }
 
 extern "C" int scldpc_full_bp_device(const scldpc_code_params *p, int32_t ntrials,
@@ -600,27 +419,25 @@ static int launch_full_bp_fixpoint(const scldpc_code_params *p, int32_t ntrials,
                                    const uint32_t *d_chan_bits, int32_t is_term, int32_t *d_counters,
                                    uint32_t *d_erased_bits, const scldpc::Scratch &scratch, void *stream)
 {
-    if (int rc = scldpc::check_params(p)) return rc;
+    using namespace scldpc;
+    if (int rc = check_params(p)) return rc;
     Args a{};
-    const bool ok = p->dv == 4 && packed_ok(p) && make_layout<Packed>(p, scldpc::kMaxLdsBytes / 2 - 1024, &a.lay) == 0;
+    const bool ok = p->dv == 4 && packed_ok(p) && flood_carve(p, regions_of(p, kWordsPacked), kHalfLdsBytes, &a.lay) == 0;
     if (!ok)
         return launch_full_bp(p, ntrials, d_vn_adj, adj16, d_chan_bits, 0, is_term, d_counters, nullptr, 0, d_erased_bits,
                               scratch, stream);
-    if (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj || !d_chan_bits)))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_full_bp_fixpoint_device: null buffer or negative ntrials");
+    if (int rc = flood_check_call("scldpc_full_bp_fixpoint_device", Scratch{}, ntrials, !d_counters || !d_vn_adj || !d_chan_bits))
+        return rc;
     if (ntrials == 0) return SCLDPC_OK;
-    const int n = scldpc::n_of(p), nk = scldpc::nk_of(p);
-    a.dv = p->dv; a.L = p->L; a.vns_pos = p->vns_pos; a.cns_pos = p->cns_pos; a.n = n; a.nk = nk;
+    const int n = n_of(p), nk = nk_of(p);
+    a.dv = p->dv; a.L = p->L; a.cns_pos = p->cns_pos; a.n = n; a.nk = nk;
     a.cn_lim = is_term ? nk : p->L * p->cns_pos;                    // BPT:944-948
-    if (!scldpc::magic_of(p->vns_pos, n > 4096 ? n : 4096, &a.magic_v) || !scldpc::magic_of(p->cns_pos, nk, &a.magic_c))
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_full_bp_fixpoint_device: reciprocal division inexact for this size");
+    // peel_to_fixpoint divides a local id (< dv*vns_pos <= 4096) by vns_pos as well
+    if (int rc = flood_geo("scldpc_full_bp_fixpoint_device: reciprocal division inexact for this size", p, n > 4096 ? n : 4096, &a))
+        return rc;
     a.vn_adj = d_vn_adj; a.chan = d_chan_bits; a.counters = d_counters; a.erased_out = d_erased_bits;
     void (*kern)(const Args) = adj16 ? full_bp_fixpoint_kernel<true, 1024> : full_bp_fixpoint_kernel<false, 1024>;
-    const size_t lds_bytes = 4u * (size_t)a.lay.total;
-    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
-    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(1024), lds_bytes, static_cast<hipStream_t>(stream), a);
-    SCLDPC_HIP_CHECK(hipGetLastError());
-    return SCLDPC_OK;
+    return flood_launch(kern, ntrials, 1024, stream, a);
 }
 
 extern "C" int scldpc_full_bp_fixpoint_device(const scldpc_code_params *p, int32_t ntrials,

@@ -115,8 +115,7 @@ __global__ __launch_bounds__(BLOCK, OCC ? OCC : WIDE ? 4 : PERSIST ? 8 : 7) __at
     for (int c = tid; c < a.ncw; c += BLOCK) cnt[c] = 0;
     int ne_local = 0;
     for (int w = tid; w < nw; w += BLOCK) {
-        uint32_t x = ch[w];
-        if (w == nw - 1 && (n & 31)) x &= (1u << (n & 31)) - 1u;
+        const uint32_t x = chan_tail(ch[w], w, nw, n);
         U[w] = x;
         ne_local += __popc(x);
     }

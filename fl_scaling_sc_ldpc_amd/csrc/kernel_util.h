@@ -22,7 +22,6 @@ namespace scldpc_dev {
 constexpr uint32_t kCntShift = 28, kDegShift = 24;
 constexpr uint32_t kCntOne = 1u << kCntShift, kDegOne = 1u << kDegShift;
 constexpr uint32_t kSumMask = (1u << kDegShift) - 1, kDegMask = 0xFu;
-constexpr uint32_t kInvalid = 0xFFFFFFFFu;
 
 __device__ __forceinline__ int wave_sum(int v)
 {
@@ -41,6 +40,13 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x)
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);
+    return x;
+}
+
+// word w of the nw channel words of a trial of n VNs: no bit at or past n
+__device__ __forceinline__ uint32_t chan_tail(uint32_t x, int w, int nw, int n)
+{
+    if (w == nw - 1 && (n & 31)) x &= (1u << (n & 31)) - 1u;
     return x;
 }
 

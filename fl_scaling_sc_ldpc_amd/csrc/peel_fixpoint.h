@@ -1,5 +1,5 @@
-// Peeling to the fixpoint without a barrier per level (dv = 4, packed 16-bit CN words in LDS) — shared by
-// full_bp_fixpoint_kernel (full_bp.hip) and the packed path of peel_sweep_kernel (peel_sweep.hip).
+// Peeling to the fixpoint without a barrier per level (dv = 4, packed 16-bit CN words in LDS): the round loop of
+// full_bp_fixpoint_kernel (full_bp.hip), its only user.  peel_sweep_kernel keeps level-synchronous rounds for every CN-word form.
 //
 // The closure of "a CN with exactly one erased neighbour resolves it" does not depend on the order in which CNs fire, so:
 //   phase A  barrier rounds over a shared queue while the frontier is wide (a scan of the CN words opens the run and
@@ -15,31 +15,28 @@
 //     An unclaimed erased neighbour of the CN can only be X itself, so nothing is ever released wrongly, and if the claim
 //     fails X is on its way out anyway.
 #pragma once
-#include "cn_words.h"
+#include "flood_common.h"
 
 namespace scldpc_dev {
 
 struct PeelCtx {                // everything the loop touches; LDS pointers unless said otherwise
-    int L, V, C, n, cn_lim, qcap;
+    int L, V, C, cn_lim, qcap;
     const char *adj;            // this trial's VN→CN table (global)
     uint32_t *cn_state, *U, *fbits, *q0, *q1;
     int *push3, *ovf3;          // two rotating triples of counters (zeroed by the caller)
 };
 
-// may_fire(c, round, one): may CN c be started from a SCAN in this round?  `one` = c < cn_lim and c shows one erased
-// neighbour.  Called by every thread of every 64-CN slice of a scan round, in wave-uniform control flow (it may ballot).
 // Returns the number of barrier rounds; `removed` += the VNs this thread released.
-template <bool A16, int BLOCK, class MayFire>
-__device__ __forceinline__ int peel_to_fixpoint(const Geo &a, const PeelCtx &x, int &removed, MayFire may_fire)
+template <bool A16, int BLOCK>
+__device__ __forceinline__ int peel_to_fixpoint(const Geo &a, const PeelCtx &x, int &removed)
 {
     using ST = Packed;
     constexpr int DV = 4;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int L = x.L, V = x.V, C = x.C, n = x.n, cn_lim = x.cn_lim, qcap = x.qcap;
+    const int L = x.L, V = x.V, C = x.C, cn_lim = x.cn_lim, qcap = x.qcap;
     const char *adj = x.adj;
     uint32_t *cn_state = x.cn_state, *U = x.U, *fbits = x.fbits;
     uint32_t *q[2] = {x.q0, x.q1};
-    (void)n;
     int rounds = 0, ncur = 0;
     bool overflow = false;
     // One release step.  `e` = [half-word : 16 | CN : 16]: CN c believed to have exactly one erased neighbour, and the
@@ -99,21 +96,10 @@ __device__ __forceinline__ int peel_to_fixpoint(const Geo &a, const PeelCtx &x, 
             }
         };
         if (scan) {
-            // every CN < cn_lim that shows one erased neighbour right now and may fire (a stale entry dies in step())
-            for (int base = 0; base < cn_lim; base += BLOCK) {
-                const int c = base + tid;
-                const bool v = may_fire(c, rounds, c < cn_lim && ST::cnt(cn_state, c) == 1u);
-                const unsigned long long m = __ballot(v);
-                if (c - lane < cn_lim) {
-                    if (lane == 0) fbits[c >> 5] = (uint32_t)m;
-                    if (lane == 32) fbits[c >> 5] = (uint32_t)(m >> 32);
-                }
-            }
+            // every CN < cn_lim that shows one erased neighbour right now (a stale entry dies in step())
+            snapshot_frontier<BLOCK>(fbits, 0, cn_lim, tid, [&](int c) { return c < cn_lim && ST::cnt(cn_state, c) == 1u; });
             __syncthreads();
-            for (int base = 0; base < cn_lim; base += BLOCK) {
-                const int c = base + tid;
-                if (c < cn_lim && ((fbits[c >> 5] >> (c & 31)) & 1u)) { uint32_t out[DV]; step(entry_of(c), out); push_shared(out); }
-            }
+            sweep_frontier<BLOCK>(fbits, 0, cn_lim, tid, [&](int c) { uint32_t out[DV]; step(entry_of(c), out); push_shared(out); });
         } else if (ncur > kSwitch || wcap < 128) {
             for (int k = tid; k < ncur; k += BLOCK) { uint32_t out[DV]; step(qc[k], out); push_shared(out); }
         } else {

@@ -82,8 +82,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SCLDPC_PICK_
     if (tid < 64) blk[tid] = 0;
     int ne_local = 0;
     for (int w = tid; w < a.nw; w += kBlock) {
-        uint32_t x = a.chan[(size_t)trial * a.nw + w];
-        if (w == a.nw - 1 && (n & 31)) x &= (1u << (n & 31)) - 1u;
+        const uint32_t x = chan_tail(a.chan[(size_t)trial * a.nw + w], w, a.nw, n);
         ne_local += __popc(x);
     }
     if (a.rng_mode == 0)
@@ -296,8 +295,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SCLDPC_PICK_
     if (valid) {
         if (!a.prebuilt) for (int c = sl; c < a.ncn; c += LPT) cn[c] = 0;
         for (int w = sl; w < a.nw; w += LPT) {
-            uint32_t x = chan[w];
-            if (w == a.nw - 1 && (n & 31)) x &= (1u << (n & 31)) - 1u;
+            const uint32_t x = chan_tail(chan[w], w, a.nw, n);
             ne += __popc(x);
         }
     }

@@ -17,10 +17,7 @@
 // VNs, or its CNs name two different partners, or its single partner b has a CN with >= 3 lost VNs or a partner other
 // than a.  No union–find, so the 16-bit packed CN words serve here too (two workgroups per CU) — for position-structured
 // graphs only, i.e. the 2-byte adjacency; arbitrary graphs (tail-biting, uncoupled) keep the 32-bit words.
-#include "common.h"
-#include "kernel_util.h"
-#include "cn_words.h"
-#include <cstdlib>
+#include "flood_common.h"
 
 namespace {
 
@@ -29,7 +26,7 @@ using namespace scldpc_dev;
 constexpr int kBlock = 1024;
 enum { S_PUSH = 0, S_OVF = 3, S_REM = 6, S_NE = 9, S_LOST = 10, S_LOST_EXP = 11, S_NSCAL = 16 };
 
-struct Layout { int cn_state, U, fbits, frozen, q0, q1, pos_flag, scal, total, qcap, nw; };
+using Layout = scldpc::FloodLayout;      // pos_a = pos_flag: positions with a VN of a component of more than two
 
 struct Args : Geo {             // Geo: vns_pos, magic_v, magic_c
     int dv, L, cns_pos, n, ncn, total_size, sweep_start, lost_lo, lost_hi;
@@ -51,7 +48,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void p
     uint32_t *fbits = lds + a.lay.fbits;
     uint32_t *frozen = lds + a.lay.frozen;
     uint32_t *q[2] = {lds + a.lay.q0, lds + a.lay.q1};
-    int *pos_flag = reinterpret_cast<int *>(lds + a.lay.pos_flag);
+    int *pos_flag = reinterpret_cast<int *>(lds + a.lay.pos_a);
     int *scal = reinterpret_cast<int *>(lds + a.lay.scal);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -63,14 +60,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void p
 
     const bool prebuilt = ST::kGlobal && a.prebuilt;
     if (!prebuilt) for (int c = tid; c < ST::words(ncn); c += kBlock) cn_state[c] = 0;
-    auto make_vn = [&](int j) { Vn v; v.j = j; v.pos = pos_of(j); v.t = j - v.pos * a.vns_pos; return v; };
-    int ne_local = 0;
-    for (int w = tid; w < nw; w += kBlock) {
-        uint32_t x = ch[w];
-        if (w == nw - 1 && (n & 31)) x &= (1u << (n & 31)) - 1u;
-        U[w] = x;
-        ne_local += __popc(x);
-    }
+    const int ne_local = load_channel<kBlock>(ch, U, nw, n, tid);
     if (tid < S_NSCAL) scal[tid] = 0;
     for (int i = tid; i < a.L; i += kBlock) pos_flag[i] = 0;
     __syncthreads();
@@ -78,27 +68,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void p
         const uint32_t tot = wave_inclusive_scan((uint32_t)ne_local);
         if (lane == 63 && tot) atomicAdd(&scal[S_NE], (int)tot);
     }
-    for (int j0 = prebuilt ? n : tid; j0 < n; j0 += 4 * kBlock) {
-        int32_t c[4][8];
-        bool er[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int j = j0 + u * kBlock;
-            er[u] = false;
-            if (j < n) {
-                load_adj<DV, A16>(adj, dv, j, pos_of(j), a.cns_pos, c[u]);
-                er[u] = (U[j >> 5] >> (j & 31)) & 1u;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int j = j0 + u * kBlock;
-            if (j < n && er[u]) {
-                const Vn v = make_vn(j);
-                for (int i = 0; i < dv; i++) ST::add(cn_state, c[u][i], v, i, a.vns_pos, true, false);
-            }
-        }
-    }
+    build_cn_words<ST, DV, A16, kBlock, false>(a, adj, dv, a.cns_pos, n, prebuilt ? n : tid, U, cn_state,
+                                               [](const Vn &, const int32_t (&)[8], bool) {});
     __syncthreads();
 
     // ---- peeling to the fixpoint (rounds as in full_bp.hip; the order is irrelevant for the residual) ----
@@ -112,7 +83,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void p
         auto release = [&](int c) {
             const int j = ST::lone_vn(cn_state, c, a);
             if (j < 0) return;
-            const Vn v = make_vn(j);
+            const Vn v = make_vn(a, j);
             int32_t cc[8];
             load_adj<DV, A16>(adj, dv, j, v.pos, a.cns_pos, cc);
             const uint32_t bit = 1u << (j & 31);
@@ -132,6 +103,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void p
             // Round 0: only swept CNs may fire from the outset (PD:656, 273-277); CNs below the sweep start that
             // hold one VN at the outset are remembered in `frozen` and never fire.  A later re-scan (queue
             // overflow) takes every other CN < total_size holding one VN: those got there by a transition.
+            // (snapshot_frontier's loop with a second bitmap: kept here)
             for (int base = 0; base < cn_lim; base += kBlock) {
                 const int c = base + tid;
                 const bool one = c < cn_lim && ST::cnt(cn_state, c) == 1u;
@@ -145,10 +117,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void p
                 }
             }
             __syncthreads();
-            for (int base = 0; base < cn_lim; base += kBlock) {
-                const int c = base + tid;
-                if (c < cn_lim && ((fbits[c >> 5] >> (c & 31)) & 1u)) release(c);
-            }
+            sweep_frontier<kBlock>(fbits, 0, cn_lim, tid, release);
         } else {
             for (int k = tid; k < ncur; k += kBlock) release((int)qc[k]);
         }
@@ -187,7 +156,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void p
             int32_t cc[8];
             if (is_lost(w * 32 + b, cc)) {
                 keep |= 1u << b;
-                const Vn v = make_vn(w * 32 + b);
+                const Vn v = make_vn(a, w * 32 + b);
                 for (int i = 0; i < dv; i++) ST::add(cn_state, cc[i], v, i, a.vns_pos, true, false);
             }
         }
@@ -214,13 +183,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void p
         while (x) {
             const int b = __ffs((int)x) - 1;
             x &= x - 1;
-            const Vn va = make_vn(w * 32 + b);
+            const Vn va = make_vn(a, w * 32 + b);
             int32_t cc[8], cb[8];
             load_adj<DV, A16>(adj, dv, va.j, va.pos, a.cns_pos, cc);
             lost++;
             int pa = neighbourhood(va, cc);
             if (pa >= 0) {                                          // one partner: is {a, partner} closed?
-                const Vn vb = make_vn(pa);
+                const Vn vb = make_vn(a, pa);
                 load_adj<DV, A16>(adj, dv, vb.j, vb.pos, a.cns_pos, cb);
                 const int pb = neighbourhood(vb, cb);
                 if (pb != va.j) pa = -2;
@@ -237,8 +206,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void p
         if (lane == 63 && t2) atomicAdd(&scal[S_LOST_EXP], (int)t2);
     }
     __syncthreads();
-    if (a.lost_out)
-        for (int w = tid; w < nw; w += kBlock) a.lost_out[(size_t)trial * nw + w] = U[w];
+    store_bits<kBlock>(a.lost_out, trial, U, nw, tid);
     if (tid == 0) {
         int blocks = 0;
         for (int pos = 0; pos < a.L; pos++) blocks += pos_flag[pos];
@@ -254,73 +222,34 @@ static int launch_peel_sweep(const scldpc_code_params *p, int32_t ntrials, const
                              const uint32_t *d_chan_bits, int32_t total_size, int32_t sweep_start,
                              int32_t lost_lo, int32_t lost_hi, int32_t *d_out, uint32_t *d_lost_bits, const scldpc::Scratch &scratch, void *stream)
 {
-    if (int rc = scldpc::check_params(p)) return rc;
-    if (scratch.query) *scratch.query = 0;
-    if (!scratch.query && (ntrials < 0 || (ntrials > 0 && (!d_out || !d_vn_adj || !d_chan_bits))))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_peel_sweep_device: null buffer or negative ntrials");
-    const int n = scldpc::n_of(p), ncn = scldpc::nk_of(p);
+    using namespace scldpc;
+    const char *who = "scldpc_peel_sweep_device";
+    if (int rc = check_params(p)) return rc;
+    if (int rc = flood_check_call(who, scratch, ntrials, !d_out || !d_vn_adj || !d_chan_bits)) return rc;
+    const int n = n_of(p), ncn = nk_of(p);
     if (total_size < 0 || total_size > ncn || sweep_start < 0 || lost_lo < 0 || lost_hi > ncn)
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_peel_sweep_device: CN ranges outside [0,%d]", ncn);
+        return set_error(SCLDPC_ERR_BAD_ARG, "scldpc_peel_sweep_device: CN ranges outside [0,%d]", ncn);
     if (ntrials <= 0) return SCLDPC_OK;
-    if (p->dc > 15 || p->dv > 8 || (int64_t)p->dc * n >= (1ll << kDegShift))
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_peel_sweep_device: needs dc <= 15, dv <= 8, dc*n < 2^24");
+    if (!flood_limits_ok(p))
+        return set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_peel_sweep_device: needs dc <= 15, dv <= 8, dc*n < 2^24");
     Args a{};
-    int off = 0;
-    auto take = [&](int words) { int o = off; off += (words + 3) & ~3; return o; };
-    a.lay.nw = (n + 31) / 32;
-    // CN words: packed 16 bit (position-structured graphs only = the 2-byte adjacency), else 32 bit in LDS, else 32 bit in
-    // the workspace.  Two workgroups per CU (half the LDS each) when queues of >= 1024 entries still fit.
-    const bool can_pack = adj16 && (int64_t)p->dv * p->vns_pos <= 4096;
-    int mode = -1, qcap = 0;                                        // 0 packed, 1 wide, 2 wide in the workspace
-    for (int m = can_pack ? 0 : 1; m < 3 && mode < 0; m++) {
-        off = 0;
-        a.lay.cn_state = take(m == 0 ? Packed::lds_words(ncn) : m == 1 ? ncn : 0);
-        a.lay.U = take(a.lay.nw);
-        a.lay.fbits = take(((ncn + 63) / 64) * 2);
-        a.lay.frozen = take(((ncn + 63) / 64) * 2);
-        a.lay.pos_flag = take(p->L + p->dv);
-        a.lay.scal = take(S_NSCAL);
-        int left = scldpc::kMaxLdsBytes / 4 - off;
-        if (scldpc::kMaxLdsBytes / 8 - 256 - off >= 2 * 1024) left = scldpc::kMaxLdsBytes / 8 - 256 - off;
-        qcap = (left / 2) & ~3;
-        if (qcap > 8192) qcap = 8192;
-        if (qcap >= 256) mode = m;
-    }
-    if (mode < 0)
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE,
-                                 "scldpc_peel_sweep_device: %d VN bits + %d scan bits do not fit 160 KiB of LDS", n, ncn);
-    const bool global_ws = mode == 2;
-    a.lay.qcap = qcap; a.lay.q0 = take(qcap); a.lay.q1 = take(qcap); a.lay.total = off;
-    if (global_ws) {
-        const size_t need = (size_t)ntrials * ncn * sizeof(uint32_t);
-        if (scratch.query) { *scratch.query = need; return SCLDPC_OK; }
-        void *ws = nullptr;
-        if (int rc = scldpc::take_scratch("scldpc_peel_sweep_device", scratch, need, &ws)) return rc;
-        a.ws = static_cast<uint32_t *>(ws);
-    }
-    if (scratch.query) return SCLDPC_OK;
-    a.dv = p->dv; a.L = p->L; a.vns_pos = p->vns_pos; a.cns_pos = p->cns_pos; a.n = n; a.ncn = ncn;
+    int words;
+    // packed 16-bit words for position-structured graphs only = the 2-byte adjacency
+    auto carve = [&](int w) { return flood_carve_roomy(p, {flood_cn_lds_words(w, ncn), true, p->L + p->dv, 0, 256}, &a.lay); };
+    if (int rc = flood_choose_words(who, "scldpc_peel_sweep_device: %d VN bits + %d scan bits do not fit 160 KiB of LDS", p, ntrials,
+                                    scratch, adj16 && (int64_t)p->dv * p->vns_pos <= 4096, carve, &words, &a.ws)) return rc;
+    if (words == kWordsQueryDone) return SCLDPC_OK;
+    a.dv = p->dv; a.L = p->L; a.cns_pos = p->cns_pos; a.n = n; a.ncn = ncn;
     a.total_size = total_size; a.sweep_start = sweep_start; a.lost_lo = lost_lo; a.lost_hi = lost_hi;
-    if (!scldpc::magic_of(p->vns_pos, n > 4096 ? n : 4096, &a.magic_v) || !scldpc::magic_of(p->cns_pos, ncn, &a.magic_c))
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_peel_sweep_device: reciprocal division inexact");
+    if (int rc = flood_geo("scldpc_peel_sweep_device: reciprocal division inexact", p, n > 4096 ? n : 4096, &a)) return rc;
     a.vn_adj = d_vn_adj; a.chan = d_chan_bits; a.out = d_out; a.lost_out = d_lost_bits;
-    void (*kern)(const Args) = nullptr;
-#define PICK(ST) (p->dv == 4 ? (adj16 ? peel_sweep_kernel<4, true, ST> : peel_sweep_kernel<4, false, ST>) \
-                             : (adj16 ? peel_sweep_kernel<0, true, ST> : peel_sweep_kernel<0, false, ST>))
-    kern = mode == 0 ? PICK(Packed) : mode == 1 ? PICK(Wide) : PICK(WideG);
-#undef PICK
-    if (global_ws && adj16) {
-        // the first build (every erased VN into its dv CNs) through an LDS ring of dv CN positions — see cn_build.hip; the
-        // second one, over the lost VNs alone, stays in the kernel (a few VNs)
-        bool pre = true;
-        if (const char *v = getenv("SCLDPC_DEBUG_SWEEP_PREBUILD")) pre = atoi(v) != 0;                      // A/B, tests
-        a.prebuilt = pre && scldpc::cn_build_launch(p, ntrials, static_cast<const uint16_t *>(d_vn_adj), d_chan_bits, a.ws, false, stream) ? 1 : 0;
-    }
-    const size_t lds_bytes = 4u * (size_t)a.lay.total;
-    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
-    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(kBlock), lds_bytes, static_cast<hipStream_t>(stream), a);
-    SCLDPC_HIP_CHECK(hipGetLastError());
-    return SCLDPC_OK;
+    void (*kern)(const Args) = flood_pick(words, p->dv == 4, adj16, [](auto st, auto dv, auto a16) -> void (*)(const Args) {
+        return peel_sweep_kernel<decltype(dv)::value, decltype(a16)::value, decltype(st)>;
+    });
+    // the first build only (every erased VN into its dv CNs); the second one, over the lost VNs alone, stays in the kernel
+    if (words == kWordsGlobal && adj16)
+        a.prebuilt = flood_prebuild("SCLDPC_DEBUG_SWEEP_PREBUILD", p, ntrials, d_vn_adj, d_chan_bits, a.ws, false, stream);
+    return flood_launch(kern, ntrials, kBlock, stream, a);
 }
 
 extern "C" int scldpc_peel_sweep_device(const scldpc_code_params *p, int32_t ntrials,

@@ -13,10 +13,7 @@
 // released (older positions are frozen).  One flooding iteration == one frontier round:
 //     every CN of Cw with cnt == 1 at the start of the round releases its VN (if not frozen).
 // The frontier is found by a scan of Cw when a window opens and kept in an LDS queue afterwards.
-#include "common.h"
-#include "kernel_util.h"
-#include "cn_words.h"
-#include <cstdlib>
+#include "flood_common.h"
 
 namespace {
 
@@ -26,10 +23,7 @@ constexpr int kBlock = 1024;
 
 enum { S_CNT = 0, S_OVF = 3, S_REM = 6, S_NCH = 9, S_NSCAL = 16 };
 
-struct Layout {             // offsets in 32-bit words into dynamic LDS
-    int cn_state, S, fbits, q0, q1, pos_cnt, pos_ss, scal, total;
-    int qcap, nw;
-};
+using Layout = scldpc::FloodLayout;      // U holds S; pos_a = erased VNs per position, pos_b = those in size-2 stopping sets
 
 struct Args : Geo {             // Geo: vns_pos, magic_v, magic_c
     int dv, L, cns_pos, n, nk, W, max_it, init_it;
@@ -52,11 +46,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void s
     uint32_t *cn_state;
     if constexpr (ST::kGlobal) cn_state = a.ws + (size_t)blockIdx.x * a.nk;
     else                       cn_state = lds + a.lay.cn_state;
-    uint32_t *S = lds + a.lay.S;
+    uint32_t *S = lds + a.lay.U;
     uint32_t *fbits = lds + a.lay.fbits;
     uint32_t *q[2] = {lds + a.lay.q0, lds + a.lay.q1};
-    int *pos_cnt = reinterpret_cast<int *>(lds + a.lay.pos_cnt);
-    int *pos_ss = reinterpret_cast<int *>(lds + a.lay.pos_ss);
+    int *pos_cnt = reinterpret_cast<int *>(lds + a.lay.pos_a);
+    int *pos_ss = reinterpret_cast<int *>(lds + a.lay.pos_b);
     int *scal = reinterpret_cast<int *>(lds + a.lay.scal);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -68,12 +62,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void s
 
     const bool prebuilt = ST::kGlobal && a.prebuilt;
     if (!prebuilt) for (int c = tid; c < ST::words(nk); c += kBlock) cn_state[c] = 0;
-    auto make_vn = [&](int j) { Vn v; v.j = j; v.pos = (int)__umulhi((uint32_t)j, a.magic_v); v.t = j - v.pos * V; return v; };
-    for (int w = tid; w < nw; w += kBlock) {
-        uint32_t x = ch[w];
-        if (w == nw - 1 && (n & 31)) x &= (1u << (n & 31)) - 1u;
-        S[w] = x;
-    }
+    load_channel<kBlock>(ch, S, nw, n, tid);
     if (tid < S_NSCAL) scal[tid] = 0;
     for (int i = tid; i < L; i += kBlock) { pos_cnt[i] = 0; pos_ss[i] = 0; }
     __syncthreads();
@@ -93,29 +82,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void s
             if (__popc(x) - lo) atomicAdd(&pos_cnt[p0 + 1], __popc(x) - lo);
         }
     }
-    for (int j0 = prebuilt ? n : tid; j0 < n; j0 += 4 * kBlock) {
-        int32_t c[4][8];
-        bool er[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int j = j0 + u * kBlock;
-            er[u] = false;
-            if (j < n) {
-                load_adj<DV, A16>(adj, dv, j, j / V, C, c[u]);
-                er[u] = (S[j >> 5] >> (j & 31)) & 1u;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int j = j0 + u * kBlock;
-            if (j < n && er[u]) {
-                nch++;
-                atomicAdd(&pos_cnt[j / V], 1);
-                const Vn v = make_vn(j);
-                for (int i = 0; i < dv; i++) ST::add(cn_state, c[u][i], v, i, V, true, false);
-            }
-        }
-    }
+    build_cn_words<ST, DV, A16, kBlock, false>(a, adj, dv, C, n, prebuilt ? n : tid, S, cn_state,
+                                               [&](const Vn &v, const int32_t (&)[8], bool) {
+        nch++;
+        atomicAdd(&pos_cnt[v.pos], 1);
+    });
     nch = wave_sum(nch);
     if (lane == 0 && nch) atomicAdd(&scal[S_NCH], nch);
     __syncthreads();
@@ -150,7 +121,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void s
                 const uint32_t bit = 1u << (j & 31);
                 const uint32_t old = atomicAnd(&S[j >> 5], ~bit);
                 if (!(old & bit)) return;
-                const Vn v = make_vn(j);
+                const Vn v = make_vn(a, j);
                 atomicSub(&pos_cnt[v.pos], 1);
                 removed++;
                 int32_t cc[8];
@@ -172,7 +143,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void s
             if (tid == 0) { scal[S_CNT + (gen + 2) % 3] = 0; scal[S_OVF + (gen + 2) % 3] = 0; scal[S_REM + (gen + 1) % 3] = 0; }
             if (scan) {
                 // snapshot {c in Cw : cnt == 1} into fbits first: releases of this round must not
-                // promote CNs into the round's own frontier
+                // promote CNs into the round's own frontier.  (snapshot_frontier's loop, kept here: a window opens with a scan,
+                // and with the helper this kernel ran 0.6 % slower — DESIGN.md, profiles/flood_common_ab.txt)
                 for (int base = c0 & ~63; base < c1; base += kBlock) {
                     const int c = base + tid;
                     const bool v = c >= c0 && c < c1 && ST::cnt(cn_state, c) == 1u;
@@ -183,10 +155,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void s
                     }
                 }
                 __syncthreads();
-                for (int base = c0 & ~63; base < c1; base += kBlock) {
-                    const int c = base + tid;
-                    if (c < c1 && ((fbits[c >> 5] >> (c & 31)) & 1u)) release((uint32_t)c);
-                }
+                sweep_frontier<kBlock>(fbits, c0, c1, tid, release);
             } else {
                 for (int k = tid; k < ncur; k += kBlock) release(qc[k]);
             }
@@ -207,28 +176,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void s
     __syncthreads();
 
     // ---- totals, expurgation over every position (BPW:841-847, 850-908) ---------------------
-    for (int w = tid; w < nw; w += kBlock) {
-        uint32_t x = S[w];
-        while (x) {
-            const int b = __ffs((int)x) - 1;
-            x &= x - 1;
-            const int va = w * 32 + b, pos = va / V;
-            int32_t cc[8];
-            load_adj<DV, A16>(adj, dv, va, pos, C, cc);
-            bool pair = true;
-            int partner = -1;
-            const Vn v = make_vn(va);
-            for (int i = 0; i < dv; i++) {
-                const int b2 = ST::partner(cn_state, cc[i], v, i, a);
-                if (b2 < 0 || (i > 0 && b2 != partner)) { pair = false; break; }
-                partner = b2;
-            }
-            if (pair && partner / V == pos) atomicAdd(&pos_ss[pos], 1);
-        }
-    }
+    count_size2_sets<ST, DV, A16, kBlock>(a, adj, dv, C, cn_state, S, nw, tid, pos_ss, [](const Vn &) {});
     __syncthreads();
-    if (a.erased_out)
-        for (int w = tid; w < nw; w += kBlock) a.erased_out[(size_t)trial * nw + w] = S[w];
+    store_bits<kBlock>(a.erased_out, trial, S, nw, tid);
     if (tid == 0) {
         int ne = 0, be = 0, ee = 0, bee = 0, p1 = 0;
         const int ms = a.dv - 1;
@@ -253,91 +203,40 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(72))) void s
     }
 }
 
-template <class ST>
-int make_layout(const scldpc_code_params *p, int W, Layout *lay)
-{
-    const int n = scldpc::n_of(p), nk = scldpc::nk_of(p);
-    int off = 0;
-    auto take = [&](int words) { int o = off; off += (words + 3) & ~3; return o; };
-    lay->nw = (n + 31) / 32;
-    lay->cn_state = take(ST::lds_words(nk));
-    lay->S = take(lay->nw);
-    lay->fbits = take(((nk + 63) / 64) * 2);
-    lay->pos_cnt = take(p->L);
-    lay->pos_ss = take(p->L);
-    lay->scal = take(S_NSCAL);
-    // Two workgroups per CU (half the LDS each) whenever queues of at least 1024 entries still fit: the kernel waits on
-    // LDS / L2 round trips most of the time and a second trial on the CU hides them.  Otherwise the whole LDS.
-    int left = scldpc::kMaxLdsBytes / 4 - off;
-    {
-        const int half = scldpc::kMaxLdsBytes / 8 - 256 - off;
-        if (half >= 2 * 1024) left = half;
-    }
-    int qcap = (left / 2) & ~3;
-    if (qcap > 8192) qcap = 8192;
-    if (qcap < 64) return -1;
-    (void)W;
-    lay->qcap = qcap;
-    lay->q0 = take(qcap);
-    lay->q1 = take(qcap);
-    lay->total = off;
-    return 0;
-}
-
 }  // namespace
 
 static int launch_sw_bp(const scldpc_code_params *p, int32_t ntrials, const void *d_vn_adj, bool adj16, bool classical,
                         const uint32_t *d_chan_bits, int32_t W, int32_t max_it, int32_t init_it,
                         int32_t *d_counters, uint32_t *d_erased_bits, const scldpc::Scratch &scratch, void *stream)
 {
-    if (int rc = scldpc::check_params(p)) return rc;
-    if (scratch.query) *scratch.query = 0;
-    if (!scratch.query && (ntrials < 0 || (ntrials > 0 && (!d_counters || !d_vn_adj || !d_chan_bits))))
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_sw_bp_device: null buffer or negative ntrials");
+    using namespace scldpc;
+    const char *who = "scldpc_sw_bp_device";
+    if (int rc = check_params(p)) return rc;
+    if (int rc = flood_check_call(who, scratch, ntrials, !d_counters || !d_vn_adj || !d_chan_bits)) return rc;
     if (W < 1 || max_it < 0 || init_it < 0)
-        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_sw_bp_device: need W >= 1, max_it >= 0, init_it >= 0");
+        return set_error(SCLDPC_ERR_BAD_ARG, "scldpc_sw_bp_device: need W >= 1, max_it >= 0, init_it >= 0");
     if (ntrials <= 0) return SCLDPC_OK;
-    const int n = scldpc::n_of(p), nk = scldpc::nk_of(p);
-    if (p->dc > 15 || p->dv > 8 || (int64_t)p->dc * n >= (1ll << kDegShift))
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_sw_bp_device: needs dc <= 15, dv <= 8, dc*n < 2^24");
+    const int n = n_of(p), nk = nk_of(p);
+    if (!flood_limits_ok(p))
+        return set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_sw_bp_device: needs dc <= 15, dv <= 8, dc*n < 2^24");
     Args a{};
-    // packed 16-bit CN words when the ensemble allows them (two workgroups per CU), else 32-bit words in LDS, else in the workspace
-    const bool packed = (int64_t)p->dv * p->vns_pos <= 4096 && make_layout<Packed>(p, W, &a.lay) == 0;
-    bool gws = false;
-    if (!packed && make_layout<Wide>(p, W, &a.lay)) {
-        if (make_layout<WideG>(p, W, &a.lay))
-            return scldpc::set_error(SCLDPC_ERR_TOO_LARGE,
-                                     "scldpc_sw_bp_device: n=%d VN bits + nk=%d scan bits do not fit 160 KiB of LDS", n, nk);
-        gws = true;
-        const size_t need = (size_t)ntrials * nk * sizeof(uint32_t);
-        if (scratch.query) { *scratch.query = need; return SCLDPC_OK; }
-        void *ws = nullptr;
-        if (int rc = scldpc::take_scratch("scldpc_sw_bp_device", scratch, need, &ws)) return rc;
-        a.ws = static_cast<uint32_t *>(ws);
-    }
-    if (scratch.query) return SCLDPC_OK;
-    if (!scldpc::magic_of(p->vns_pos, n > 4096 ? n : 4096, &a.magic_v) || !scldpc::magic_of(p->cns_pos, nk, &a.magic_c))
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_sw_bp_device: reciprocal division inexact for this size");
-    a.dv = p->dv; a.L = p->L; a.vns_pos = p->vns_pos; a.cns_pos = p->cns_pos; a.n = n; a.nk = nk;
+    int words;
+    auto carve = [&](int w) { return flood_carve_roomy(p, {flood_cn_lds_words(w, nk), false, p->L, p->L, 64}, &a.lay); };
+    if (int rc = flood_choose_words(who, "scldpc_sw_bp_device: n=%d VN bits + nk=%d scan bits do not fit 160 KiB of LDS", p, ntrials,
+                                    scratch, (int64_t)p->dv * p->vns_pos <= 4096, carve, &words, &a.ws)) return rc;
+    if (words == kWordsQueryDone) return SCLDPC_OK;
+    if (int rc = flood_geo("scldpc_sw_bp_device: reciprocal division inexact for this size", p, n > 4096 ? n : 4096, &a)) return rc;
+    a.dv = p->dv; a.L = p->L; a.cns_pos = p->cns_pos; a.n = n; a.nk = nk;
     a.W = W; a.max_it = max_it; a.init_it = init_it ? init_it : max_it;     // BPW:2101-2102
     a.classical = classical ? 1 : 0;
     a.vn_adj = d_vn_adj; a.chan = d_chan_bits; a.counters = d_counters; a.erased_out = d_erased_bits;
 
-    void (*kern)(const Args);
-#define PICK(ST) (p->dv == 4 ? (adj16 ? sw_bp_kernel<4, true, ST> : sw_bp_kernel<4, false, ST>) \
-                             : (adj16 ? sw_bp_kernel<0, true, ST> : sw_bp_kernel<0, false, ST>))
-    kern = packed ? PICK(Packed) : gws ? PICK(WideG) : PICK(Wide);
-#undef PICK
-    if (gws && adj16 && p->vns_pos >= 32) {
-        bool pre = true;
-        if (const char *v = getenv("SCLDPC_DEBUG_SW_PREBUILD")) pre = atoi(v) != 0;                         // A/B, tests
-        a.prebuilt = pre && scldpc::cn_build_launch(p, ntrials, static_cast<const uint16_t *>(d_vn_adj), d_chan_bits, a.ws, false, stream) ? 1 : 0;
-    }
-    const size_t lds_bytes = 4u * (size_t)a.lay.total;
-    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(kern))) return rc_;
-    hipLaunchKernelGGL(kern, dim3(ntrials), dim3(kBlock), lds_bytes, static_cast<hipStream_t>(stream), a);
-    SCLDPC_HIP_CHECK(hipGetLastError());
-    return SCLDPC_OK;
+    void (*kern)(const Args) = flood_pick(words, p->dv == 4, adj16, [](auto st, auto dv, auto a16) -> void (*)(const Args) {
+        return sw_bp_kernel<decltype(dv)::value, decltype(a16)::value, decltype(st)>;
+    });
+    if (words == kWordsGlobal && adj16 && p->vns_pos >= 32)
+        a.prebuilt = flood_prebuild("SCLDPC_DEBUG_SW_PREBUILD", p, ntrials, d_vn_adj, d_chan_bits, a.ws, false, stream);
+    return flood_launch(kern, ntrials, kBlock, stream, a);
 }
 
 extern "C" int scldpc_sw_bp_device(const scldpc_code_params *p, int32_t ntrials,
