@@ -55,6 +55,7 @@ EXPORTS = (
     "scldpc_swc_bp_ring_supported", "scldpc_swc_bp_ring_device",
     "scldpc_sample_philox_adj16_sock_supported", "scldpc_sample_philox_device_adj16_sock",
     "scldpc_sample_philox_deg_sock16_supported", "scldpc_sample_philox_device_deg_sock16",
+    "scldpc_sample_philox_wide_sock16_supported", "scldpc_sample_philox_device_wide_sock16",
 )
 
 
@@ -126,6 +127,8 @@ def lib():
     L.scldpc_sample_philox_device_sock16.argtypes = [pp, u64, u64, i32, dbl, i32, vp, vp, vp, vp, vp]
     L.scldpc_sample_philox_deg_sock16_supported.argtypes = [pp]
     L.scldpc_sample_philox_device_deg_sock16.argtypes = [pp, u64, u64, i32, dbl, i32, vp, vp, vp, vp, vp]
+    L.scldpc_sample_philox_wide_sock16_supported.argtypes = [pp]
+    L.scldpc_sample_philox_device_wide_sock16.argtypes = [pp, u64, u64, i32, dbl, i32, vp, vp, vp, vp, vp]
     L.scldpc_sample_philox_adj16_sock_supported.argtypes = [pp]
     L.scldpc_sample_philox_device_adj16_sock.argtypes = [pp, u64, u64, i32, dbl, i32, vp, vp, vp, vp, vp, u64, vp]
     L.scldpc_full_bp_fixpoint_device_cn16.argtypes = [pp, i32, vp, vp, vp, i32, vp, vp, vp]

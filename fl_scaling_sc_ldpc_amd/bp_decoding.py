@@ -46,6 +46,11 @@ builds the decoder's CN -> socket table, the sampler writes that table in its ow
 the second-generation sampler of these pairs (engine.sample_philox_deg_sock16) draws the code and writes the CN -> socket table in
 one launch, instead of the first-generation sampler and its table pass; same files.
 
+`--sampler2-wide on|off|auto` (bp_lim_iter, bp_traj, sw_lim_iter): with --dv/--dc 3/6, 4/8 or 5/10 and more than 8192 but at most
+20480 sockets per position (bp_traj's default N = 5000), the wide second-generation sampler (engine.sample_philox_wide_sock16)
+draws the code and writes the CN -> socket table in one launch, instead of the first-generation sampler and its table pass; same
+files.
+
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
@@ -182,12 +187,20 @@ SAMPLED_TABLE_BY_DEFAULT = False
 # and --sampled-table are specified, and tested, as starting from the first-generation sampler: the flip is a change of its own.
 SAMPLER2_DEG_BY_DEFAULT = False
 
+# Whether Simulator(sampler2_wide=None) takes the wide second-generation sampler (engine.sample_philox_wide_sock16: the pairs (3,6),
+# (4,8) and (5,10) with more than 8192 and at most 20480 sockets per position) where it applies, instead of the first-generation
+# sampler and the cn_sockets pass: SAMPLER2_DEG_BY_DEFAULT's rule on the shapes of tools/sampler_wide_speedup.py
+# (profiles/sampler_wide_speedup.json).  Same rows, channel and files; the same table as a set per CN.  Kept False
+# here whatever is measured: the selection tests specify the default path, and the flip is a change of its own.
+SAMPLER2_WIDE_BY_DEFAULT = False
+
 
 # The path of a Simulator, decided once in Simulator._select:
 #   adj_dtype    VN -> CN table: torch.int16 (position-local ids) or torch.int32 (the reference's VNdegree)
 #   sampler      what fills a batch: "glibc" (host replay), "first" (first-generation sampler), "first_sock" (the same with the
 #                CN -> socket table from its own launch), "cn16" / "sock16" (second generation, with the CN -> VN / CN -> socket
-#                table), "deg_sock16" (second generation of the pairs (3,6) and (5,10), with the CN -> socket table)
+#                table), "deg_sock16" (second generation of the pairs (3,6) and (5,10), with the CN -> socket table), "wide_sock16"
+#                (second generation beyond 8192 sockets per position, with the CN -> socket table)
 #   cn_table     the CN table kept next to the VN -> CN one: None, "vn" or "sock"
 #   cn_pass      that table comes from the cn_sockets pass (the sampler does not emit it)
 #   decoder      "sw_ring" / "sw_chain" (E.sw_bp; "sw_ring" with cn_pass: the _deg entry points, pairs (3,6) and (5,10)),
@@ -211,7 +224,7 @@ class Simulator:
     def __init__(self, p, decoder="full", W=0, max_it=0, init_it=0, is_term=True, doped=(), batch=2048,
                  rng="philox", seed=1, device=None, rows_cap=0, schedule="flooding", shard_frames=True, index=0,
                  verbose=False, caps=None, wide=None, deg=None, ring=None, fused_caps=None, sampled_table=None,
-                 sampler2=None):
+                 sampler2=None, sampler2_wide=None):
         # wide: the 1024-thread 4-bit level decoder for trials of more than 65536 CNs (full_bp_small wide).  None = where
         # WIDE_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path, for A/B and tests)
         self.want_wide = wide
@@ -231,6 +244,9 @@ class Simulator:
         # sampler2: the second-generation sampler of the pairs (3,6) and (5,10) instead of the first-generation sampler and the
         # cn_sockets pass.  None = where SAMPLER2_DEG_BY_DEFAULT says, True = wherever it applies, False = never
         self.want_sampler2 = sampler2
+        # sampler2_wide: the wide second-generation sampler (more than 8192 sockets per position) instead of the first-generation
+        # sampler and the cn_sockets pass.  None = where SAMPLER2_WIDE_BY_DEFAULT says, True = wherever it applies, False = never
+        self.want_sampler2_wide = sampler2_wide
         self.p, self.decoder, self.W, self.max_it, self.init_it = p, decoder, W, max_it, init_it
         # caps: several MaxNumIt from one decode (run_point_caps; the level-synchronous 4-bit decoder only)
         self.caps = E.check_caps(caps) if caps is not None else None
@@ -334,6 +350,11 @@ class Simulator:
         self.sampler2_deg_reason = sampler2_deg_reason(p, self.rng, path, self.want_sampler2)
         if self.sampler2_deg_reason is None:
             path = self.path = path._replace(sampler="deg_sock16", cn_table="sock", cn_pass=False)
+        # beyond 8192 sockets per position: code and CN -> socket table from the wide second-generation sampler (opt-in; decided
+        # behind sampler2, whose shapes it does not take, and before the next switch, as sampler2 is)
+        self.sampler2_wide_reason = sampler2_wide_reason(p, self.rng, path, self.want_sampler2_wide)
+        if self.sampler2_wide_reason is None:
+            path = self.path = path._replace(sampler="wide_sock16", cn_table="sock", cn_pass=False)
         # the table of a path that runs the cn_sockets pass after the first-generation sampler, or leaves it to E.sw_bp, from the
         # sampler's own launch instead (opt-in)
         self.sampled_table_reason = sampled_table_reason(p, self.rng, path, self.want_sampled_table)
@@ -391,8 +412,12 @@ class Simulator:
         """Which device kernels this configuration runs."""
         path = self.path
         samp2 = "sampler_v2 (dv = %d, dc = %d, CN->socket table)" % (self.p.dv, self.p.dc)
+        samp2w = "sampler_v2 wide (dv = %d, dc = %d, CN->socket table)" % (self.p.dv, self.p.dc)
         if path.decoder == "sw_ring" and path.sampler == "deg_sock16":
             return samp2 + " + sw_ring (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc)
+        if path.decoder == "sw_ring" and path.sampler == "wide_sock16":
+            return samp2w + (" + sw_ring (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc) if self.ring_deg else
+                             " + sw_ring (window state in LDS)")
         if path.decoder == "sw_ring" and path.sampler == "first_sock":
             return ("sampler (first generation, CN->socket table) + sw_ring (window state in LDS"
                     + (", dv = %d, dc = %d)" % (self.p.dv, self.p.dc) if self.ring_deg else ")"))
@@ -406,7 +431,8 @@ class Simulator:
             return "sampler (first generation) + sw_bp (whole chain)"
         samp = {"glibc": "glibc replay on the host", "first": "sampler (first generation)",
                 "first_sock": "sampler (first generation, CN->socket table)", "cn16": "sampler_v3 (CN->VN table)",
-                "sock16": "sampler_v3 (CN->socket table)", "deg_sock16": samp2}[path.sampler] + (" + cn_sockets pass" if path.cn_pass else "")
+                "sock16": "sampler_v3 (CN->socket table)", "deg_sock16": samp2,
+                "wide_sock16": samp2w}[path.sampler] + (" + cn_sockets pass" if path.cn_pass else "")
         if path.decoder == "swc_ring":
             return samp + " + sw_ring classical window (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc)
         if path.decoder == "swc_chain":
@@ -503,7 +529,7 @@ class Simulator:
                                  out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
         else:
             sample = {"cn16": E.sample_philox_cn16, "sock16": E.sample_philox_sock16,
-                      "deg_sock16": E.sample_philox_deg_sock16}[path.sampler]
+                      "deg_sock16": E.sample_philox_deg_sock16, "wide_sock16": E.sample_philox_wide_sock16}[path.sampler]
             sample(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
                    out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
 
@@ -636,7 +662,7 @@ def sampled_table_reason(p, rng, path, want=True):
         return "switched off"
     if rng != "philox":
         return "--rng %s samples the code on the host" % rng
-    if path.sampler in ("cn16", "sock16", "deg_sock16"):
+    if path.sampler in ("cn16", "sock16", "deg_sock16", "wide_sock16"):
         return "the second-generation sampler takes this ensemble and writes the CN table with the code already"
     # what runs the cn_sockets pass after the first-generation sampler, and the (4,8) ring whose table E.sw_bp builds per call
     if not (path.sampler == "first" and path.adj_dtype == torch.int16
@@ -667,6 +693,29 @@ def sampler2_deg_reason(p, rng, path, want=True):
     if not E.deg_sock16_supported(p):
         return ("the second-generation sampler of the pairs (3,6) and (5,10) takes at most 8192 sockets per position "
                 "(dv = %d, dc = %d, N = %d: %d sockets)" % (p.dv, p.dc, p.vns_pos, p.cns_pos * p.dc))
+    return None
+
+
+def sampler2_wide_reason(p, rng, path, want=True):
+    """Why a configuration whose path (before this switch) is `path` does not take the wide second-generation sampler (more than
+    8192 sockets per position), or None where it does.  want: the Simulator's sampler2_wide argument (None:
+    SAMPLER2_WIDE_BY_DEFAULT)."""
+    if not (SAMPLER2_WIDE_BY_DEFAULT if want is None else bool(want)):
+        return "switched off"
+    if rng != "philox":
+        return "--rng %s samples the code on the host" % rng
+    if path.sampler in ("cn16", "sock16", "deg_sock16"):
+        return ("the second-generation sampler of at most 8192 sockets per position takes this ensemble and writes the CN table "
+                "with the code already")
+    if not E.wide_sock16_supported(p):
+        return ("the wide second-generation sampler takes the pairs (3,6), (4,8) and (5,10) with more than 8192 and at most 20480 "
+                "sockets per position (dv = %d, dc = %d, N = %d: %d sockets)" % (p.dv, p.dc, p.vns_pos, p.cns_pos * p.dc))
+    # what runs the cn_sockets pass after the first-generation sampler, a ring decoder on a table of sockets, and the (4,8) ring
+    # whose table E.sw_bp builds per call
+    if not (path.sampler == "first" and path.adj_dtype == torch.int16
+            and (path.cn_pass or (path.decoder in ("sw_ring", "swc_ring") and path.cn_table == "sock")
+                 or (path.decoder == "sw_ring" and path.cn_table is None))):
+        return "the decoder of this configuration (%s) reads no CN -> socket table" % path.decoder
     return None
 
 
@@ -801,8 +850,10 @@ def _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, sh
                         seed=opts.seed, schedule="flooding", shard_frames=shard == "frames",
                         device=getattr(opts, "device", None), index=index, verbose=verbose, caps=caps, wide=wide, deg=deg,
                         fused_caps=fused, sampled_table=switch[getattr(opts, "sampled_table", "auto")],
-                        sampler2=switch[getattr(opts, "sampler2", "auto")])
+                        sampler2=switch[getattr(opts, "sampler2", "auto")],
+                        sampler2_wide=switch[getattr(opts, "sampler2_wide", "auto")])
     _check_sampler2(opts, sim_obj)
+    _check_sampler2_wide(opts, sim_obj)
     _check_sampled_table(opts, sim_obj)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
@@ -958,8 +1009,10 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                         deg={"auto": None, "on": True, "off": False}[getattr(opts, "deg", "auto")],
                         ring=ring if decoder in ("sw", "swc") else None,
                         sampled_table={"auto": None, "on": True, "off": False}[getattr(opts, "sampled_table", "auto")],
-                        sampler2={"auto": None, "on": True, "off": False}[getattr(opts, "sampler2", "auto")])
+                        sampler2={"auto": None, "on": True, "off": False}[getattr(opts, "sampler2", "auto")],
+                        sampler2_wide={"auto": None, "on": True, "off": False}[getattr(opts, "sampler2_wide", "auto")])
     _check_sampler2(opts, sim_obj)
+    _check_sampler2_wide(opts, sim_obj)
     _check_sampled_table(opts, sim_obj)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
@@ -1041,6 +1094,12 @@ def _check_sampler2(opts, sim_obj):
     """--sampler2 on where the second-generation sampler of the pairs (3,6) and (5,10) does not apply: exits with the reason."""
     if getattr(opts, "sampler2", "auto") == "on" and sim_obj.sampler2_deg_reason is not None:
         raise SystemExit("--sampler2 on: " + sim_obj.sampler2_deg_reason)
+
+
+def _check_sampler2_wide(opts, sim_obj):
+    """--sampler2-wide on where the wide second-generation sampler does not apply: exits with the reason."""
+    if getattr(opts, "sampler2_wide", "auto") == "on" and sim_obj.sampler2_wide_reason is not None:
+        raise SystemExit("--sampler2-wide on: " + sim_obj.sampler2_wide_reason)
 
 
 def _check_window(opts):
@@ -1131,6 +1190,11 @@ def _parser(prog):
                          "table: the second-generation sampler draws the code and writes the table in one launch (on), the "
                          "first-generation sampler and its table pass (off), or the measured default (auto); same files.  'on' "
                          "where it does not apply is an error that says why")
+    ap.add_argument("--sampler2-wide", choices=("auto", "on", "off"), default="auto",
+                    help="--dv/--dc 3/6, 4/8 or 5/10 with more than 8192 and at most 20480 sockets per position (e.g. the default "
+                         "N = 5000), where the decoder reads a CN -> socket table: the wide second-generation sampler draws the "
+                         "code and writes the table in one launch (on), the first-generation sampler and its table pass (off), or "
+                         "the measured default (auto); same files.  'on' where it does not apply is an error that says why")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")

@@ -1,4 +1,4 @@
-// What the Philox samplers share (sampler.hip, sampler_v2.hip, sampler_v2_deg.hip): on the device the steps of a channel word,
+// What the Philox samplers share (sampler.hip, sampler_v2.hip, sampler_v2_deg.hip, sampler_v2_wide.hip): on the device the steps of a channel word,
 // the histogram words of a thread, the exclusive scan of the bucket counts, the two-calls-per-thread look-up and the worklist's
 // resolve loop; on the host the erasure threshold, the validation of a sampling call and the second generation's LDS layout.
 // Every device function is inlined into its kernel, and cut so that the kernels' code stays what it was when each carried its
@@ -255,6 +255,35 @@ inline int v2_lds_layout(const char *who, int S, int hist_bufs, bool by_nb, bool
         return set_error(SCLDPC_ERR_TOO_LARGE, "%s: %zu bytes of LDS per trial", who, *bytes);
     a->force_exact = -1;
     if (const char *v = getenv("SCLDPC_DEBUG_SAMPLER_EXACT_POS")) a->force_exact = atoi(v);
+    return SCLDPC_OK;
+}
+
+// LDS of the wide second generation (sampler_v2_wide.hip, more than 8192 sockets per position), which ranks a position in one
+// part (up to kWidePartCap sockets) or in two, by the top key bit: one histogram of kWideHistWords words over the next 15 key
+// bits and the packed keys of one part (kWidePartCap entries, by part-local rank) — the two lie side by side and together hold
+// the S keys of the exact fallback — then the stage of one part, the S CN ids of the position and two sets of wave totals,
+// worklist counter and overflow flag (parts alternate between them, 32 words each) with the worklist behind them.  Sets the
+// offsets, a->force_exact as above and a->part_cap (SCLDPC_DEBUG_SAMPLER_PART_CAP lowers it: diagnostics / tests only).
+constexpr int kWideHistWords = 8192;
+constexpr int kWidePartCap = 12288;
+constexpr int kWideMaxSockets = kWideHistWords + kWidePartCap;  // the exact fallback's keys: histogram + packed keys
+
+template <class Args>
+inline int v2_wide_lds_layout(const char *who, int S, Args *a, size_t *bytes)
+{
+    int off = kWideHistWords;                                   // the histogram at word 0
+    a->off_gpk = off;   off += kWidePartCap;
+    a->off_stage = off; off += kWidePartCap / 2;
+    a->off_fix = off;   off += (S / 2 + 3) & ~3;
+    a->off_wsum = off;  off += 64 + 2 * kWorkCap;
+    *bytes = 4u * (size_t)off;
+    *bytes = std::min(*bytes + debug_lds_pad("SAMPLER"), std::max(*bytes, (size_t)kMaxLdsBytes));
+    if (S > kWideMaxSockets || *bytes > (size_t)kMaxLdsBytes)
+        return set_error(SCLDPC_ERR_TOO_LARGE, "%s: %zu bytes of LDS per trial", who, *bytes);
+    a->force_exact = -1;
+    if (const char *v = getenv("SCLDPC_DEBUG_SAMPLER_EXACT_POS")) a->force_exact = atoi(v);
+    a->part_cap = kWidePartCap;
+    if (const char *v = getenv("SCLDPC_DEBUG_SAMPLER_PART_CAP")) a->part_cap = std::min(kWidePartCap, std::max(0, atoi(v)));
     return SCLDPC_OK;
 }
 

@@ -174,7 +174,7 @@ def cn16_supported(p):
 
 
 def _sample_philox_tables(fn, p, seed, trial0, ntrials, eps, doped, device, out, want_cn=True):
-    """The one body of sample_philox_cn16 / sample_philox_sock16 / sample_philox_deg_sock16: both tables and the channel from the
+    """The one body of sample_philox_cn16 / sample_philox_sock16 / sample_philox_deg_sock16 / sample_philox_wide_sock16: both tables and the channel from the
     second-generation sampler."""
     _require_gpu()
     if out is None:
@@ -233,6 +233,19 @@ def sample_philox_deg_sock16(p, seed, trial0, ntrials, eps, doped=(), device="cu
     and the last are bit for bit sample_philox(..., adj16=True)'s, cn_sock16 is cn_sockets(p, vn_adj16) as a set per CN.
     out = (vn_adj16, None, chan): no table."""
     return _sample_philox_tables(lib().scldpc_sample_philox_device_deg_sock16, p, seed, trial0, ntrials, eps, doped, device, out)
+
+
+def wide_sock16_supported(p):
+    """The pairs (3,6), (4,8) and (5,10) with more than 8192 and at most 20480 sockets per CN position: the wide second-generation
+    sampler (sampler_v2_wide.hip) takes the ensemble.  Needs no device."""
+    return bool(lib().scldpc_sample_philox_wide_sock16_supported(C.byref(p)))
+
+
+def sample_philox_wide_sock16(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0", out=None):
+    """scldpc_sample_philox_device_wide_sock16: (vn_adj16 int16 [T,n,dv], cn_sock16 int16 [T,nk,dc], chan int32 [T,nw]); the first
+    and the last are bit for bit sample_philox(..., adj16=True)'s, cn_sock16 is cn_sockets(p, vn_adj16) as a set per CN.
+    out = (vn_adj16, None, chan): no table."""
+    return _sample_philox_tables(lib().scldpc_sample_philox_device_wide_sock16, p, seed, trial0, ntrials, eps, doped, device, out)
 
 
 def sample_philox_sock_supported(p):

@@ -221,6 +221,15 @@ int scldpc_sample_philox_deg_sock16_supported(const scldpc_code_params *p);
 int scldpc_sample_philox_device_deg_sock16(const scldpc_code_params *p, uint64_t seed, uint64_t trial0, int32_t ntrials,
                                            double eps, int32_t ndoped, const int32_t *doped_positions, uint16_t *d_vn_adj16,
                                            uint16_t *d_cn_sock16, uint32_t *d_chan_bits, void *stream);
+/* The second-generation sampler beyond 8192 sockets per CN position (sampler_v2_wide.hip), for the pairs (dv, dc) = (3,6), (4,8)
+ * and (5,10): buffers, law and keys as scldpc_sample_philox_device_deg_sock16 (d_cn_sock16 NULL: no table).  One launch, no
+ * workspace.  *_supported (no device needed): 1 for these three pairs with vns_pos * dv == cns_pos * dc and
+ * 8192 < cns_pos * dc <= 20480, else 0.  The entry point refuses every other ensemble with SCLDPC_ERR_TOO_LARGE before any
+ * device work (ntrials == 0 included); argument checks and their SCLDPC_ERR_BAD_ARG are scldpc_sample_philox_device_sock16's. */
+int scldpc_sample_philox_wide_sock16_supported(const scldpc_code_params *p);
+int scldpc_sample_philox_device_wide_sock16(const scldpc_code_params *p, uint64_t seed, uint64_t trial0, int32_t ntrials,
+                                            double eps, int32_t ndoped, const int32_t *doped_positions, uint16_t *d_vn_adj16,
+                                            uint16_t *d_cn_sock16, uint32_t *d_chan_bits, void *stream);
 int scldpc_full_bp_cn16_supported(const scldpc_code_params *p);
 int scldpc_full_bp_fixpoint_device_cn16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                         const uint16_t *d_cn_adj16, const uint32_t *d_chan_bits, int32_t is_term,
