@@ -48,6 +48,11 @@ int allow_max_lds(const void *kernel);
 bool cn_build_launch(const scldpc_code_params *p, int ntrials, const uint16_t *d_vn_adj16, const uint32_t *d_chan_bits,
                      uint32_t *d_words, bool deg, void *stream);
 
+// full_bp_small.hip: which limit keeps this ensemble from the narrow socket-table forms of the 4-bit decoders' _deg entry
+// points (the pairs (3,6), (4,8), (5,10); 16-bit sockets; at most 65536 CNs per trial); nullptr: none.  peel_sweep_small.hip
+// takes the same shapes.
+const char *small_deg_shape_limit(const scldpc_code_params *p);
+
 // Diagnostics only (tools/ab_occupancy.py): extra bytes of dynamic LDS per workgroup from the environment variable
 // SCLDPC_DEBUG_LDS_PAD_<which>, to measure a kernel at fewer workgroups per CU than its own footprint allows.  0 if unset.
 size_t debug_lds_pad(const char *which);

@@ -663,6 +663,8 @@ const char *shape_limit(const scldpc_code_params *p, bool wide, bool sock, bool 
 
 }  // namespace
 
+const char *scldpc::small_deg_shape_limit(const scldpc_code_params *p) { return shape_limit(p, false, true, true); }
+
 // 1 when the _wide forms take this ensemble: 32-bit queue entries, one 1024-thread workgroup per CU
 extern "C" int scldpc_full_bp_wide_supported(const scldpc_code_params *p) { return shape_limit(p, true, true) == nullptr; }
 

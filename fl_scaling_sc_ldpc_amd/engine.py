@@ -601,6 +601,32 @@ def peel_sweep(p, d_adj, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=N
     return {"out": out, "lost": lost}
 
 
+def peel_sweep_sock16_supported(p):
+    """The pairs (3,6), (4,8), (5,10) with 16-bit sockets and at most 65536 CNs per trial: peel_sweep_sock16 takes the ensemble
+    (scldpc_peel_sweep_sock16_supported).  Needs no device."""
+    return bool(lib().scldpc_peel_sweep_sock16_supported(C.byref(p)))
+
+
+def peel_sweep_sock16(p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=None, want_lost=False):
+    """scldpc_peel_sweep_device_sock16: peel_sweep from the 2-byte VN -> CN table and the CN -> socket table (cn_sockets(p,
+    d_adj16) or a second-generation sampler's) with 4 bits of LDS per CN — the same dict, columns 0, 1, 2, 7 of `out` and the
+    `lost` bits bit for bit; column 5 counts this kernel's rounds, column 6 its re-scans.  No workspace, no fallback: an
+    ensemble it does not take raises."""
+    _require_gpu()
+    T = d_adj16.shape[0]
+    assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous() and tuple(d_adj16.shape[1:]) == (p.n, p.dv)
+    assert d_cn_sock.is_cuda and d_cn_sock.dtype == torch.int16 and d_cn_sock.is_contiguous() and tuple(d_cn_sock.shape) == (T, p.nk, p.dc)
+    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous() and tuple(d_chan.shape) == (T, p.nw)
+    dev = d_adj16.device
+    out = torch.empty((T, 8), dtype=torch.int32, device=dev)
+    lost = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_lost else None
+    check(lib().scldpc_peel_sweep_device_sock16(C.byref(p), T, d_adj16.data_ptr(), d_cn_sock.data_ptr(), d_chan.data_ptr(),
+                                                int(total_size), int(sweep_start), int(lost_lo),
+                                                int(total_size if lost_hi is None else lost_hi), out.data_ptr(),
+                                                lost.data_ptr() if lost is not None else None, _stream_ptr(dev)))
+    return {"out": out, "lost": lost}
+
+
 def peel_pick(p, d_adj, d_chan, total_size, num_steps, mt_state=None, seed=0, trial0=0, want_r1=True, moments=None):
     """One trial of simulate_peeling_decoder_ldpc's loop body per batch entry (PD:750-785).
     mt_state: int32/uint32-as-int32 tensor [T,625] (CPython MT19937 state, updated in place) or None (Philox)."""

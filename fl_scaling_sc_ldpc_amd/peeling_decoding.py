@@ -169,12 +169,75 @@ class _Geometry:
         self.lost_hi = self.total_size - self.cpp * self.ignored_tail
 
 
+# Whether simulate_sc_ldpc(sweep="auto") takes the 4-bit sweep decoder (engine.peel_sweep_sock16, peel_sweep_small.hip) and the
+# sampler that writes its CN -> socket table where select_sweep allows it, instead of sample_philox(adj16=True) + peel_sweep:
+# True only if every repetition of the new path beats every repetition of the old one on every shape of
+# tools/sweep_small_speedup.py, with equal outputs (profiles/sweep_small_speedup.json).  Kept False here whatever
+# is measured: the flip is a change of its own.
+SWEEP_SMALL_BY_DEFAULT = False
+
+SWEEP_SAMPLERS = ("sample_philox_sock16", "sample_philox_deg_sock16", "sample_philox+cn_sockets")
+
+
+def select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, sweep="auto"):
+    """Which sampler and sweep decoder a simulate_sc_ldpc run takes: ("first", reason) — sample_philox / the host streams and
+    peel_sweep — or ("small", sampler) — peel_sweep_sock16 behind one of SWEEP_SAMPLERS.  A pure function of its arguments:
+    p the _Geometry's parameters, ensemble "olmos" | "tail_biting" | "protograph", decoder_ok / sock16_ok / deg_sock16_ok the
+    answers of engine.peel_sweep_sock16_supported / sock16_supported / deg_sock16_supported, sweep the requested mode."""
+    if sweep not in ("auto", "first", "small"):
+        raise ValueError("sweep must be 'auto', 'first' or 'small'")
+    if sweep == "first":
+        return "first", "sweep='first'"
+    if sweep == "auto" and not SWEEP_SMALL_BY_DEFAULT:
+        return "first", "sweep='auto' is 'first' (SWEEP_SMALL_BY_DEFAULT)"
+    if rng != "philox":
+        return "first", "rng=%r draws the codes on the host: the 4-bit sweep decoder reads the device samplers' tables" % (rng,)
+    if ensemble != "olmos":
+        return "first", "the %s tables hold global CN ids: the 4-bit sweep decoder reads position-local 2-byte rows" % ensemble
+    if not decoder_ok:
+        return "first", ("the 4-bit sweep decoder takes the pairs (3,6), (4,8), (5,10) with vns_pos * dv <= 65535 and at most "
+                         "65536 CNs per trial (dv = %d, dc = %d, L = %d, M = %d: %d CNs)" % (p.dv, p.dc, p.L, p.vns_pos, p.nk))
+    if (p.dv, p.dc) == (4, 8) and sock16_ok:
+        return "small", "sample_philox_sock16"
+    if (p.dv, p.dc) in ((3, 6), (5, 10)) and deg_sock16_ok:
+        return "small", "sample_philox_deg_sock16"
+    return "small", "sample_philox+cn_sockets"
+
+
+def _sweep_choice(p, rng, ensemble, sweep):
+    """select_sweep with the library's answers; sweep='small' on a run it refuses raises."""
+    # the default path asks the library nothing it did not ask before
+    asked = sweep == "small" or (sweep == "auto" and SWEEP_SMALL_BY_DEFAULT)
+    answers = (E.peel_sweep_sock16_supported(p), E.sock16_supported(p), E.deg_sock16_supported(p)) if asked else (False,) * 3
+    kind, what = select_sweep(p, rng, ensemble, *answers, sweep)
+    if sweep == "small" and kind != "small":
+        raise ValueError("sweep='small': " + what)
+    if sweep != "auto" or kind == "small":
+        line = (what.replace("+", " + ") + " + peel_sweep_small (4-bit CN counts)" if kind == "small" else
+                "%s + peel_sweep (16- or 32-bit CN words): %s" % ("sampler (first generation)" if rng == "philox" else
+                                                                  "host streams", what))
+        print("[scldpc] kernels: " + line, file=sys.stderr, flush=True)
+    return kind, what
+
+
+def _sample_small(sampler, p, seed, trial0, ntrials, e, doped, device):
+    """(vn_adj16, cn_sock16, chan) from the sampler select_sweep named."""
+    if sampler == "sample_philox_sock16":
+        return E.sample_philox_sock16(p, seed, trial0, ntrials, e, doped, device=device)
+    if sampler == "sample_philox_deg_sock16":
+        return E.sample_philox_deg_sock16(p, seed, trial0, ntrials, e, doped, device=device)
+    d_adj, d_ch = E.sample_philox(p, seed, trial0, ntrials, e, doped, device=device, adj16=True)
+    return d_adj, E.cn_sockets(p, d_adj), d_ch
+
+
 def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats=int(1e5),
-                     max_fuckups=2000, doping_points=[], rng="numpy", seed=0, batch=None, device=None):
+                     max_fuckups=2000, doping_points=[], rng="numpy", seed=0, batch=None, device=None, sweep="auto"):
     """Error-rate Monte-Carlo of the sweep peeling decoder (PD:591-701); returns the reference's 13-tuple.
     rng="philox" under torch.distributed: every round of world*batch trials is split evenly over the ranks, the
     per-trial result rows (32 B each) are all-gathered and every rank runs the same ordered accumulation, so the stop
-    rule (max_fuckups, PD:698) cuts at the same trial and every rank returns the same tuple as a single rank would."""
+    rule (max_fuckups, PD:698) cuts at the same trial and every rank returns the same tuple as a single rank would.
+    sweep: "first" = peel_sweep, "small" = the 4-bit sweep decoder and the sampler select_sweep names (ValueError where it
+    does not apply), "auto" = what SWEEP_SMALL_BY_DEFAULT says; the same 13-tuple either way."""
     _check_flags(is_protograph, is_tail_biting)
     device = _device(device)
     dist, rank, world = _dist()
@@ -182,6 +245,8 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
         raise ValueError("rng='numpy' replays the reference's one sequential stream: single rank only")
     g = _Geometry(l, r, L, M, is_terminated, is_bounded, doping_points)
     p = g.params
+    ens = "protograph" if is_protograph else "tail_biting" if is_tail_biting else "olmos"
+    kind, small_sampler = _sweep_choice(p, rng, ens, sweep)
     if batch is None:
         batch = 64 if rng == "numpy" else 2048
     # The reference's per-trial bookkeeping and its stop rule (PD:668-699) run on the device, in trial order
@@ -208,15 +273,21 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
         elif rng == "philox":
             if soft and is_protograph:
                 raise NameError("name 'position' is not defined")   # the reference's own failure for soft doping (PD:228)
-            ens = "protograph" if is_protograph else "tail_biting" if is_tail_biting else "olmos"
-            d_adj, d_ch = E.sample_philox(p, seed, done + lo, mine, e, [] if soft else _doped_positions(doping_points),
-                                          device=device, adj16=(ens == "olmos"), ensemble=ens)
+            doped = [] if soft else _doped_positions(doping_points)
+            if kind == "small":
+                d_adj, d_cn, d_ch = _sample_small(small_sampler, p, seed, done + lo, mine, e, doped, device)
+            else:
+                d_adj, d_ch = E.sample_philox(p, seed, done + lo, mine, e, doped, device=device, adj16=(ens == "olmos"),
+                                              ensemble=ens)
             if soft:                                        # PD:176-183: the first int(alpha*M) VNs of the position are known
                 for pos, alpha in doping_points.items():
                     E.clear_channel_range(p, d_ch, pos * M, pos * M + int(alpha * M))
         else:
             raise ValueError("rng must be 'numpy' or 'philox'")
-        d_out = E.peel_sweep(p, d_adj, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
+        if kind == "small":
+            d_out = E.peel_sweep_sock16(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
+        else:
+            d_out = E.peel_sweep(p, d_adj, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
         if world > 1:
             m = max(offs[r + 1] - offs[r] for r in range(world))
             pad = torch.zeros((m, d_out.shape[1]), dtype=d_out.dtype, device=d_out.device)
@@ -450,12 +521,15 @@ def _safe_eval(text):
 def _cli_options(args, kw):
     """The reference's command lines are positional only.  This mirror also takes, anywhere among them,
     `--rng philox|numpy`, `--seed S`, `--batch B`, `--device D` — the keyword arguments of the simulators (throughput mode:
-    device sampling, trials sharded over the ranks of a torch.distributed.run job)."""
+    device sampling, trials sharded over the ranks of a torch.distributed.run job) — and `--sweep first|small|auto`, which
+    only ber_sim (simulate_sc_ldpc) takes."""
     kw, pos, it = dict(kw), [], iter(args)
     for x in it:
-        if isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device"):
+        if isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device", "--sweep"):
             v = next(it)
-            kw[x[2:]] = v if x in ("--rng", "--device") else int(v)
+            if x == "--sweep" and v not in ("first", "small", "auto"):
+                raise SystemExit("--sweep takes first, small or auto (got %r)" % (v,))
+            kw[x[2:]] = v if x in ("--rng", "--device", "--sweep") else int(v)
         else:
             pos.append(x)
     return pos, kw
@@ -529,6 +603,9 @@ def main_simulate_variance(argv=None, **kw):
     """simulate_variance.py: OUT l r L M e T|N U|P num_runs num_runs_batch THEORY (PD:1264-1294): writes
     pickle.dump((ssquares, counts))."""
     a, kw = _cli_options(sys.argv if argv is None else [None] + list(argv), kw)
+    if "sweep" in kw:
+        raise SystemExit("--sweep chooses the sweep decoder of ber_sim (simulate_sc_ldpc): simulate_variance runs the "
+                         "random-pick decoder and takes no such option")
     joined = _join_job(kw)
     try:
         return _main_simulate_variance(a, kw)

@@ -425,6 +425,20 @@ int scldpc_peel_sweep_device_adj16(const scldpc_code_params *p, int32_t ntrials,
                                    int32_t total_size, int32_t sweep_start, int32_t lost_lo, int32_t lost_hi,
                                    int32_t *d_out, uint32_t *d_lost_bits, void *d_workspace, uint64_t workspace_bytes, void *stream);
 
+/* The same trial with 4 bits of LDS per CN (peel_sweep_small.hip): 256-thread workgroups, up to seven trials per CU, for the
+ * pairs (3,6), (4,8), (5,10) with vns_pos * dv <= 65535 and at most 65536 CNs per trial — the shapes of
+ * scldpc_full_bp_deg_supported.  Reads the 2-byte VN -> CN table and the CN -> socket table [ntrials][nk][dc] of
+ * scldpc_sample_philox_device_sock16 / _deg_sock16 / scldpc_cn_sockets_device; no workspace.  d_out columns 0, 1, 2, 7 and
+ * d_lost_bits equal scldpc_peel_sweep_device_adj16's bit for bit; [5] counts this kernel's barrier rounds, [6] its scans after
+ * the first (0 unless a queue overflowed).  total_size in [0, nk], any sweep_start >= 0.  Checks in a fixed order: parameters,
+ * CN ranges (SCLDPC_ERR_BAD_ARG), shape (SCLDPC_ERR_TOO_LARGE, also for ntrials == 0), buffers.  There is no form for more
+ * than 65536 CNs, for the CN -> VN table, or for tail-biting / protograph tables (global CN ids). */
+int scldpc_peel_sweep_sock16_supported(const scldpc_code_params *p);
+int scldpc_peel_sweep_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                    const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t total_size,
+                                    int32_t sweep_start, int32_t lost_lo, int32_t lost_hi, int32_t *d_out,
+                                    uint32_t *d_lost_bits, void *stream);
+
 /* One trial of simulate_peeling_decoder_ldpc's loop body (PD:750-785): random-pick peeling with the
  * degree-1-CN trajectory.  num_steps = int(M*num_positions*(e+0.1)) (PD:721).
  * Generator: d_mt_state != NULL ⇒ uint32 [ntrials][625] = CPython `random` MT19937 state (624 words + index,
