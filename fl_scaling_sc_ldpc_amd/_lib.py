@@ -57,6 +57,7 @@ EXPORTS = (
     "scldpc_sample_philox_deg_sock16_supported", "scldpc_sample_philox_device_deg_sock16",
     "scldpc_sample_philox_wide_sock16_supported", "scldpc_sample_philox_device_wide_sock16",
     "scldpc_peel_sweep_sock16_supported", "scldpc_peel_sweep_device_sock16",
+    "scldpc_peel_sweep_wide_supported", "scldpc_peel_sweep_device_sock16_wide",
 )
 
 
@@ -163,6 +164,8 @@ def lib():
     L.scldpc_peel_sweep_device_adj16.argtypes = L.scldpc_peel_sweep_device.argtypes
     L.scldpc_peel_sweep_sock16_supported.argtypes = [pp]
     L.scldpc_peel_sweep_device_sock16.argtypes = [pp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.scldpc_peel_sweep_wide_supported.argtypes = [pp]
+    L.scldpc_peel_sweep_device_sock16_wide.argtypes = L.scldpc_peel_sweep_device_sock16.argtypes
     L.scldpc_peel_pick_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, u64, u64, vp, vp, vp, vp, u64, vp]
     L.scldpc_peel_pick_device_adj16.argtypes = L.scldpc_peel_pick_device.argtypes
     L.scldpc_r1_moments_device.argtypes = [i32, i32, vp, vp, vp]

@@ -23,11 +23,27 @@
 //     component iff one of its CNs counts >= 3, or its count-2 CNs name two different partners, or its single partner b has a
 //     CN counting >= 3 or a partner other than a.  The partner at a count-2 CN is the other socket of its row whose U bit is set.
 // The residual of the peeling does not depend on its order, so rows and lost bits equal peel_sweep_kernel's bit for bit.
+//
+// The WIDE form (scldpc_peel_sweep_device_sock16_wide) is the same kernel for trials of more than 65 536 CNs: queue entries are
+// 32-bit CN ids, and one 1024-thread workgroup (16 waves, four per SIMD, at most 128 VGPRs) owns the CU's LDS, one trial per CU.
+// Its carve (make_args with wide = true), in this order and each region rounded up to 16 bytes:
+//     ceil(nk / 8) count words | ceil(n / 32) VN words | ceil(fz_lim / 8) frozen bytes | L position flags | 16 scalars
+// and then two queues that share what is left of 160 KiB - 512 B evenly, in 32-bit entries, with no upper cap.  The shape rule
+// (wide_shape_limit; host side, pure): the pairs (3,6), (4,8), (5,10); vns_pos * dv <= 65 535 (16-bit sockets) and cns_pos <=
+// 65 536 (16-bit position-local CN ids); an exact multiply-high division for vns_pos and cns_pos (magic_of); and at least
+// kWideMinQueue = 1024 entries per queue.  No lower bound on nk: small shapes run through it too.  (4,8), L = 50, M = 5000 keeps
+// about 8 000 entries per queue; (4,8), L = 90, M = 5000 (172.5 KB of state) is refused.
+// The 16-wave private-queue phase: the waves go private below kSwitchWidthWide = 512 frontier entries, 32 per wave as in the
+// narrow form (128 over four waves).  Wave v's part of the idle queue is wcap = (qcap / 16) & ~1 entries, two halves of
+// half_cap = wcap / 2 between which its levels alternate; it takes entries v, v + 16, ... (at most 32) into the first half, so
+// the phase needs half_cap >= 32 (the narrow form asks 64 of its four waves), which every supported shape has (qcap >= 1024).
+// What a half cannot take spills behind the first 512 entries of the queue being read, as in the narrow form.
 #include "common.h"
 #include "kernel_util.h"
 #include "table_rows.h"
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -38,7 +54,11 @@ constexpr int kPerCu = 7;               // workgroups per CU the LDS carve aims 
 constexpr int kSwitchWidth = 128;       // frontier entries below which the waves go private
 constexpr int kMinQueueWords = 128;     // a queue shorter than 256 entries is no fast path: take fewer workgroups per CU
 constexpr int kMinDebugQcap = 8;        // floor of SCLDPC_DEBUG_SWEEP_QCAP
+constexpr int kBlockWide = 1024;        // the wide form: one workgroup per CU, four waves per SIMD
+constexpr int kSwitchWidthWide = 512;   // 32 frontier entries per wave, as kSwitchWidth
+constexpr int kWideMinQueue = 1024;     // entries per queue below which the wide form refuses the shape
 static_assert(kSwitchWidth <= 64 * (kBlock / 64), "a wave takes at most one frontier entry per lane into its private queue");
+static_assert(kSwitchWidthWide <= 64 * (kBlockWide / 64), "a wave takes at most one frontier entry per lane into its private queue");
 
 enum { S_NE = 0, S_N0, S_N1, S_OVF, S_Q, S_MORE, S_ANY, S_LOST, S_EXP, S_BLK, S_N = 16 };
 
@@ -47,7 +67,7 @@ struct SwArgs {
     int cn_lim, fz_lim, lost_lo, lost_hi;           // cn_lim = total_size; fz_lim = min(sweep_start, total_size)
     uint32_t magic_v, magic_c;
     int kswitch;
-    int off_U, off_fz, off_q0, off_q1, off_pos, off_scal, total, qcap;      // LDS offsets in 32-bit words; qcap in u16 entries
+    int off_U, off_fz, off_q0, off_q1, off_pos, off_scal, total, qcap;      // LDS offsets in 32-bit words; qcap in queue entries
     const uint16_t *vn_adj16;                       // [T][n][dv]  CN index local to its position
     const uint16_t *cn_sock16;                      // [T][nk][dc] sockets dv*t + i of every CN (0xFFFF: none)
     const uint32_t *chan;
@@ -72,12 +92,15 @@ __device__ __forceinline__ uint32_t spread8(uint32_t b)
 
 // DV, DC: the degree pair, fixed at compile time (the rows of both tables are unrolled; table_rows.h).
 // OCC: waves per SIMD the registers are bounded for where an instance cannot hold kPerCu (0: kPerCu).
-template <int DV, int DC, int OCC = 0>
-__global__ __launch_bounds__(kBlock, OCC ? OCC : kPerCu) __attribute__((amdgpu_num_sgpr(96))) void peel_sweep_small_kernel(const SwArgs a)
+// WIDE: 32-bit queue entries and a 1024-thread workgroup, one per CU (the header comment).
+template <int DV, int DC, int OCC = 0, bool WIDE = false>
+__global__ __launch_bounds__(WIDE ? kBlockWide : kBlock, WIDE ? kBlockWide / 256 : OCC ? OCC : kPerCu) __attribute__((amdgpu_num_sgpr(96)))
+void peel_sweep_small_kernel(const SwArgs a)
 {
     static_assert(DC <= 15 && DC % 2 == 0 && DV < DC, "a CN's count of erased neighbours is a nibble; CN rows are read as 32-bit words");
-    constexpr int BLOCK = kBlock, kWaves = BLOCK / 64;
-    using QT = uint16_t;
+    constexpr int BLOCK = WIDE ? kBlockWide : kBlock, kWaves = BLOCK / 64;
+    constexpr int kMinHalf = WIDE ? kSwitchWidthWide / kWaves : 64;      // a wave's half-queue below this keeps the waves shared
+    using QT = std::conditional_t<WIDE, uint32_t, uint16_t>;
     extern __shared__ uint32_t lds[];
     uint32_t *cnt = lds;                                                 // nk nibbles
     uint32_t *U = lds + a.off_U;
@@ -266,7 +289,7 @@ __global__ __launch_bounds__(kBlock, OCC ? OCC : kPerCu) __attribute__((amdgpu_n
             // entries a wave's private half-queue cannot take go to the part of qc behind the kSwitch entries the waves start from
             QT *spill = qc + kSwitch;
             const int spill_cap = cap_c - kSwitch;
-            const bool shared = pending || ncur > kSwitch || half_cap < 64 || spill_cap < 0;
+            const bool shared = pending || ncur > kSwitch || half_cap < kMinHalf || spill_cap < 0;
             if (shared) {
                 for (int k0 = wave * 64; k0 < ncur; k0 += BLOCK) {
                     uint32_t out[DV] = {};
@@ -323,7 +346,9 @@ __global__ __launch_bounds__(kBlock, OCC ? OCC : kPerCu) __attribute__((amdgpu_n
                 ncur = min(pushed, spill_cap); rd_off += kSwitch;        // the spilled entries, where they lie in q[cur]
             }
             if (!pending && ncur == 0) break;
-            if (tid == 0) { scal[S_OVF] = 0; scal[S_Q] = ncur; }
+            // (wide: S_OVF is cleared only where it was set; then a scan is pending and the barrier below stands between this
+            // store and the next round's overflow flags, whichever of the sixteen waves runs ahead)
+            if (tid == 0) { if (!WIDE || dropped) scal[S_OVF] = 0; scal[S_Q] = ncur; }
             if (pending) __syncthreads();                                // the scan appends behind scal[S_Q]
         }
     }
@@ -422,8 +447,9 @@ __global__ __launch_bounds__(kBlock, OCC ? OCC : kPerCu) __attribute__((amdgpu_n
 }
 
 // The LDS carve for `per_cu` workgroups per CU: counts, U, the frozen bitmap (sized by fz_lim, not by nk), the position flags,
-// the scalars, then two queues of what is left (at most 2048 words each, as full_bp_small.hip's)
-int make_args(const scldpc_code_params *p, int fz_lim, int per_cu, SwArgs *a)
+// the scalars, then two queues of what is left (narrow: at most 2048 words each, as full_bp_small.hip's, two entries per word;
+// wide: per_cu = 1, one entry per word, no cap, at least kWideMinQueue entries)
+int make_args(const scldpc_code_params *p, int fz_lim, int per_cu, SwArgs *a, bool wide = false)
 {
     const int n = scldpc::n_of(p), nk = scldpc::nk_of(p);
     a->L = p->L; a->V = p->vns_pos; a->C = p->cns_pos; a->n = n; a->nk = nk;
@@ -437,10 +463,10 @@ int make_args(const scldpc_code_params *p, int fz_lim, int per_cu, SwArgs *a)
     a->off_pos = take(p->L);
     a->off_scal = take(S_N);
     const int budget = scldpc::kMaxLdsBytes / per_cu / 4 - 128;           // words per workgroup
-    int qwords = ((budget - off) / 2) & ~3;                              // per queue; two uint16 entries per word
-    if (qwords > 2048) qwords = 2048;
-    if (qwords < kMinQueueWords) return -1;
-    a->qcap = 2 * qwords;
+    int qwords = ((budget - off) / 2) & ~3;                              // per queue
+    if (qwords > 2048 && !wide) qwords = 2048;
+    if (qwords < (wide ? kWideMinQueue : kMinQueueWords)) return -1;
+    a->qcap = wide ? qwords : 2 * qwords;
     a->off_q0 = take(qwords);
     a->off_q1 = take(qwords);
     a->total = off;
@@ -458,8 +484,14 @@ using Kernel = void (*)(const SwArgs);
 // The instances with their VGPRs / SGPRs at -O3 for gfx950 (make resources), and the workgroups per CU each is
 // bounded for
 struct Instance { Kernel kern; int per_cu; };
-Instance instance_of(int dv, int dc)
+Instance instance_of(int dv, int dc, bool wide = false)
 {
+    if (wide) {
+        if (dv == 4 && dc == 8) return {peel_sweep_small_kernel<4, 8, 0, true>, 1};
+        if (dv == 3 && dc == 6) return {peel_sweep_small_kernel<3, 6, 0, true>, 1};
+        if (dv == 5 && dc == 10) return {peel_sweep_small_kernel<5, 10, 0, true>, 1};
+        return {nullptr, 0};
+    }
     if (dv == 4 && dc == 8) return {peel_sweep_small_kernel<4, 8>, kPerCu};
     if (dv == 3 && dc == 6) return {peel_sweep_small_kernel<3, 6>, kPerCu};
     if (dv == 5 && dc == 10) return {peel_sweep_small_kernel<5, 10, 6>, 6};        // six waves per SIMD (12 B of scratch at seven)
@@ -475,10 +507,78 @@ const char *shape_limit(const scldpc_code_params *p, int fz_lim)
     return nullptr;
 }
 
+// The shape rule of the wide form (the header comment): the pair, 16-bit sockets and position-local CN ids, exact division,
+// and a carve at one workgroup per CU that leaves kWideMinQueue entries per queue.  No bound on nk either way.
+const char *wide_shape_limit(const scldpc_code_params *p, int fz_lim)
+{
+    if (scldpc::check_params(p)) return "invalid code parameters";
+    if (p->dc > 15) return "dc must be at most 15 (a CN's count of erased neighbours is kept in 4 bits)";
+    if (!instance_of(p->dv, p->dc, true).kern) {
+        static thread_local char text[96];
+        snprintf(text, sizeof text, "no instance for dv = %d, dc = %d (takes (3,6), (4,8) and (5,10))", p->dv, p->dc);
+        return text;
+    }
+    if ((int64_t)p->vns_pos * p->dv > 65535) return "sockets: vns_pos * dv must fit 16 bits (at most 65535)";
+    if (p->cns_pos > 65536) return "at most 65536 CNs per position (16-bit position-local CN ids)";
+    const char *lds = "LDS: the CN counts, the VN bits and the bitmap of sweep_start CNs leave fewer than 1024 entries per queue "
+                      "(160 KiB - 512 B per trial)";
+    const int64_t n64 = (int64_t)p->L * p->vns_pos, nk64 = (int64_t)(p->L + p->dv - 1) * p->cns_pos;
+    if (n64 / 8 + nk64 / 2 > scldpc::kMaxLdsBytes) return lds;          // (also keeps n and nk far inside 32 bits)
+    uint32_t m;
+    if (!scldpc::magic_of(p->vns_pos, scldpc::n_of(p) + 32, &m) || !scldpc::magic_of(p->cns_pos, scldpc::nk_of(p), &m))
+        return "no exact multiply-high division for this vns_pos / cns_pos";
+    SwArgs a{};
+    if (make_args(p, fz_lim, 1, &a, true) != 0) return lds;
+    return nullptr;
+}
+
+// The one body of the two entry points.  The checks come in one fixed order: the parameters, the CN ranges, the shape (judged
+// even for an empty batch), the buffers; nothing is dereferenced before all have passed.
+int sweep_launch(const char *who, bool wide, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                 const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t total_size, int32_t sweep_start, int32_t lost_lo,
+                 int32_t lost_hi, int32_t *d_out, uint32_t *d_lost_bits, void *stream)
+{
+    using namespace scldpc;
+    if (int rc = check_params(p)) return rc;
+    const int64_t nk64 = (int64_t)(p->L + p->dv - 1) * p->cns_pos;
+    if (total_size < 0 || total_size > nk64 || sweep_start < 0 || lost_lo < 0 || lost_hi > nk64)
+        return set_error(SCLDPC_ERR_BAD_ARG, "%s: CN ranges outside [0,%lld]", who, (long long)nk64);
+    const int fz_lim = std::min(sweep_start, total_size);
+    if (const char *why = wide ? wide_shape_limit(p, fz_lim) : shape_limit(p, fz_lim))
+        return set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
+    if (ntrials < 0 || (ntrials > 0 && (!d_out || !d_vn_adj16 || !d_cn_sock16 || !d_chan_bits)))
+        return set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
+    if (ntrials == 0) return SCLDPC_OK;
+
+    SwArgs a{};
+    const Instance inst = instance_of(p->dv, p->dc, wide);
+    int per_cu = inst.per_cu;
+    // A/B only (tools/sweep_small_speedup.py): aim the carve at fewer workgroups per CU, i.e. at longer queues
+    if (const char *v = getenv("SCLDPC_DEBUG_SWEEP_PER_CU")) per_cu = std::max(1, std::min(atoi(v), per_cu));
+    if (!inst.kern || (wide ? make_args(p, fz_lim, 1, &a, true) : carve(p, fz_lim, per_cu, &a)) < 0)
+        return set_error(SCLDPC_ERR_TOO_LARGE, "%s: LDS: the CN counts and VN bits do not fit", who);
+    magic_of(p->vns_pos, a.n + 32, &a.magic_v);
+    magic_of(p->cns_pos, a.nk, &a.magic_c);
+    a.cn_lim = total_size; a.lost_lo = lost_lo; a.lost_hi = lost_hi;
+    a.vn_adj16 = d_vn_adj16; a.cn_sock16 = d_cn_sock16; a.chan = d_chan_bits; a.out = d_out; a.lost_out = d_lost_bits;
+    a.kswitch = wide ? kSwitchWidthWide : kSwitchWidth;
+    // tests and A/B only: a shorter queue, so that small shapes overflow and re-scan (a private half-queue below 64 entries,
+    // wide: 32, keeps the waves on the shared queue).  The LDS taken stays that of the full carve.
+    if (const char *v = getenv("SCLDPC_DEBUG_SWEEP_QCAP")) a.qcap = std::max(kMinDebugQcap, std::min(atoi(v), a.qcap));
+    if (int rc = allow_max_lds(reinterpret_cast<const void *>(inst.kern))) return rc;
+    hipLaunchKernelGGL(inst.kern, dim3(ntrials), dim3(wide ? kBlockWide : kBlock), 4u * (size_t)a.total,
+                       static_cast<hipStream_t>(stream), a);
+    SCLDPC_HIP_CHECK(hipGetLastError());
+    return SCLDPC_OK;
+}
+
 }  // namespace
 
 // 1 when scldpc_peel_sweep_device_sock16 takes this ensemble (for sweep_start = 0; a launch judges its own sweep_start)
 extern "C" int scldpc_peel_sweep_sock16_supported(const scldpc_code_params *p) { return shape_limit(p, 0) == nullptr; }
+
+// 1 when scldpc_peel_sweep_device_sock16_wide takes this ensemble (for sweep_start = 0; a launch judges its own sweep_start)
+extern "C" int scldpc_peel_sweep_wide_supported(const scldpc_code_params *p) { return wide_shape_limit(p, 0) == nullptr; }
 
 // One trial of simulate_sc_ldpc's loop body per batch entry (PD:650-691) from the 2-byte VN -> CN table and the CN -> socket
 // table: d_out and d_lost_bits as scldpc_peel_sweep_device_adj16 writes them (columns 0, 1, 2, 7 and the bitmap bit for bit;
@@ -489,35 +589,17 @@ extern "C" int scldpc_peel_sweep_device_sock16(const scldpc_code_params *p, int3
                                                int32_t sweep_start, int32_t lost_lo, int32_t lost_hi, int32_t *d_out,
                                                uint32_t *d_lost_bits, void *stream)
 {
-    using namespace scldpc;
-    const char *who = "scldpc_peel_sweep_device_sock16";
-    if (int rc = check_params(p)) return rc;
-    const int64_t nk64 = (int64_t)(p->L + p->dv - 1) * p->cns_pos;
-    if (total_size < 0 || total_size > nk64 || sweep_start < 0 || lost_lo < 0 || lost_hi > nk64)
-        return set_error(SCLDPC_ERR_BAD_ARG, "%s: CN ranges outside [0,%lld]", who, (long long)nk64);
-    const int fz_lim = std::min(sweep_start, total_size);
-    if (const char *why = shape_limit(p, fz_lim)) return set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
-    if (ntrials < 0 || (ntrials > 0 && (!d_out || !d_vn_adj16 || !d_cn_sock16 || !d_chan_bits)))
-        return set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
-    if (ntrials == 0) return SCLDPC_OK;
+    return sweep_launch("scldpc_peel_sweep_device_sock16", false, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, total_size,
+                        sweep_start, lost_lo, lost_hi, d_out, d_lost_bits, stream);
+}
 
-    SwArgs a{};
-    const Instance inst = instance_of(p->dv, p->dc);
-    int per_cu = inst.per_cu;
-    // A/B only (tools/sweep_small_speedup.py): aim the carve at fewer workgroups per CU, i.e. at longer queues
-    if (const char *v = getenv("SCLDPC_DEBUG_SWEEP_PER_CU")) per_cu = std::max(1, std::min(atoi(v), per_cu));
-    if (!inst.kern || carve(p, fz_lim, per_cu, &a) < 0)
-        return set_error(SCLDPC_ERR_TOO_LARGE, "%s: LDS: the CN counts and VN bits do not fit", who);
-    magic_of(p->vns_pos, a.n + 32, &a.magic_v);
-    magic_of(p->cns_pos, a.nk, &a.magic_c);
-    a.cn_lim = total_size; a.lost_lo = lost_lo; a.lost_hi = lost_hi;
-    a.vn_adj16 = d_vn_adj16; a.cn_sock16 = d_cn_sock16; a.chan = d_chan_bits; a.out = d_out; a.lost_out = d_lost_bits;
-    a.kswitch = kSwitchWidth;
-    // tests and A/B only: a shorter queue, so that small shapes overflow and re-scan (a private half-queue below 64 entries
-    // keeps the waves on the shared queue)
-    if (const char *v = getenv("SCLDPC_DEBUG_SWEEP_QCAP")) a.qcap = std::max(kMinDebugQcap, std::min(atoi(v), a.qcap));
-    if (int rc = allow_max_lds(reinterpret_cast<const void *>(inst.kern))) return rc;
-    hipLaunchKernelGGL(inst.kern, dim3(ntrials), dim3(kBlock), 4u * (size_t)a.total, static_cast<hipStream_t>(stream), a);
-    SCLDPC_HIP_CHECK(hipGetLastError());
-    return SCLDPC_OK;
+// The same from the wide form: 32-bit queue entries, one 1024-thread workgroup per CU, any number of CNs per trial whose 4-bit
+// state leaves 1024 entries per queue in one CU's LDS (wide_shape_limit).  Same outputs, same order of the checks.
+extern "C" int scldpc_peel_sweep_device_sock16_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                                    const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t total_size,
+                                                    int32_t sweep_start, int32_t lost_lo, int32_t lost_hi, int32_t *d_out,
+                                                    uint32_t *d_lost_bits, void *stream)
+{
+    return sweep_launch("scldpc_peel_sweep_device_sock16_wide", true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, total_size,
+                        sweep_start, lost_lo, lost_hi, d_out, d_lost_bits, stream);
 }

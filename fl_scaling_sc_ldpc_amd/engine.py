@@ -607,11 +607,8 @@ def peel_sweep_sock16_supported(p):
     return bool(lib().scldpc_peel_sweep_sock16_supported(C.byref(p)))
 
 
-def peel_sweep_sock16(p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=None, want_lost=False):
-    """scldpc_peel_sweep_device_sock16: peel_sweep from the 2-byte VN -> CN table and the CN -> socket table (cn_sockets(p,
-    d_adj16) or a second-generation sampler's) with 4 bits of LDS per CN — the same dict, columns 0, 1, 2, 7 of `out` and the
-    `lost` bits bit for bit; column 5 counts this kernel's rounds, column 6 its re-scans.  No workspace, no fallback: an
-    ensemble it does not take raises."""
+def _peel_sweep_tables(entry, p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start, lost_lo, lost_hi, want_lost):
+    """The one body of peel_sweep_sock16 / peel_sweep_sock16_wide."""
     _require_gpu()
     T = d_adj16.shape[0]
     assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous() and tuple(d_adj16.shape[1:]) == (p.n, p.dv)
@@ -620,11 +617,35 @@ def peel_sweep_sock16(p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start=0, 
     dev = d_adj16.device
     out = torch.empty((T, 8), dtype=torch.int32, device=dev)
     lost = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_lost else None
-    check(lib().scldpc_peel_sweep_device_sock16(C.byref(p), T, d_adj16.data_ptr(), d_cn_sock.data_ptr(), d_chan.data_ptr(),
-                                                int(total_size), int(sweep_start), int(lost_lo),
-                                                int(total_size if lost_hi is None else lost_hi), out.data_ptr(),
-                                                lost.data_ptr() if lost is not None else None, _stream_ptr(dev)))
+    check(getattr(lib(), entry)(C.byref(p), T, d_adj16.data_ptr(), d_cn_sock.data_ptr(), d_chan.data_ptr(),
+                                 int(total_size), int(sweep_start), int(lost_lo),
+                                 int(total_size if lost_hi is None else lost_hi), out.data_ptr(),
+                                 lost.data_ptr() if lost is not None else None, _stream_ptr(dev)))
     return {"out": out, "lost": lost}
+
+
+def peel_sweep_sock16(p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=None, want_lost=False):
+    """scldpc_peel_sweep_device_sock16: peel_sweep from the 2-byte VN -> CN table and the CN -> socket table (cn_sockets(p,
+    d_adj16) or a second-generation sampler's) with 4 bits of LDS per CN — the same dict, columns 0, 1, 2, 7 of `out` and the
+    `lost` bits bit for bit; column 5 counts this kernel's rounds, column 6 its re-scans.  No workspace, no fallback: an
+    ensemble it does not take raises."""
+    return _peel_sweep_tables("scldpc_peel_sweep_device_sock16", p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start, lost_lo,
+                              lost_hi, want_lost)
+
+
+def peel_sweep_wide_supported(p):
+    """The pairs (3,6), (4,8), (5,10) with 16-bit sockets whose 4-bit state leaves two queues of 1024 32-bit entries in one
+    CU's LDS, any number of CNs per trial: peel_sweep_sock16_wide takes the ensemble (scldpc_peel_sweep_wide_supported,
+    judged at sweep_start = 0).  Needs no device."""
+    return bool(lib().scldpc_peel_sweep_wide_supported(C.byref(p)))
+
+
+def peel_sweep_sock16_wide(p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=None, want_lost=False):
+    """scldpc_peel_sweep_device_sock16_wide: peel_sweep_sock16 with 32-bit queue entries and one 1024-thread workgroup per CU,
+    for trials of more than 65536 CNs (and any smaller one) — the same arguments, the same dict.  No workspace, no fallback:
+    an ensemble it does not take raises."""
+    return _peel_sweep_tables("scldpc_peel_sweep_device_sock16_wide", p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start,
+                              lost_lo, lost_hi, want_lost)
 
 
 def peel_pick(p, d_adj, d_chan, total_size, num_steps, mt_state=None, seed=0, trial0=0, want_r1=True, moments=None):

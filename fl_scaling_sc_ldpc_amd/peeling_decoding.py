@@ -176,18 +176,55 @@ class _Geometry:
 # is measured: the flip is a change of its own.
 SWEEP_SMALL_BY_DEFAULT = False
 
+# The same for the wide form of that decoder (engine.peel_sweep_sock16_wide: 32-bit queue entries, one trial per CU, more than
+# 65 536 CNs per trial), which sweep="auto" consults only where SWEEP_SMALL_BY_DEFAULT's rule has declined: True only if every
+# repetition of the new path beats every repetition of the old one on every shape of tools/sweep_wide_speedup.py
+# (profiles/sweep_wide_speedup.json).  Kept False here whatever is measured.
+SWEEP_WIDE_BY_DEFAULT = False
+
 SWEEP_SAMPLERS = ("sample_philox_sock16", "sample_philox_deg_sock16", "sample_philox+cn_sockets")
+SWEEP_WIDE_SAMPLERS = ("sample_philox_sock16", "sample_philox_deg_sock16", "sample_philox_wide_sock16", "sample_philox+cn_sockets")
 
 
-def select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, sweep="auto"):
+def _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock16_ok):
+    """select_sweep's rule for the wide form: ("wide", one of SWEEP_WIDE_SAMPLERS) or ("first", reason)."""
+    if rng != "philox":
+        return "first", "rng=%r draws the codes on the host: the 4-bit sweep decoder reads the device samplers' tables" % (rng,)
+    if ensemble != "olmos":
+        return "first", "the %s tables hold global CN ids: the 4-bit sweep decoder reads position-local 2-byte rows" % ensemble
+    if not wide_ok:
+        return "first", ("the wide 4-bit sweep decoder takes the pairs (3,6), (4,8), (5,10) with vns_pos * dv <= 65535 (16-bit "
+                         "sockets) whose CN counts, VN bits and sweep_start bitmap leave two queues of 1024 entries in one CU's LDS "
+                         "(dv = %d, dc = %d, L = %d, M = %d: %d CNs)" % (p.dv, p.dc, p.L, p.vns_pos, p.nk))
+    if (p.dv, p.dc) == (4, 8) and sock16_ok:
+        return "wide", "sample_philox_sock16"
+    if (p.dv, p.dc) in ((3, 6), (5, 10)) and deg_sock16_ok:
+        return "wide", "sample_philox_deg_sock16"
+    if wide_sock16_ok:
+        return "wide", "sample_philox_wide_sock16"
+    return "wide", "sample_philox+cn_sockets"
+
+
+def select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, sweep="auto", wide_ok=False, wide_sock16_ok=False):
     """Which sampler and sweep decoder a simulate_sc_ldpc run takes: ("first", reason) — sample_philox / the host streams and
-    peel_sweep — or ("small", sampler) — peel_sweep_sock16 behind one of SWEEP_SAMPLERS.  A pure function of its arguments:
+    peel_sweep —, ("small", sampler) — peel_sweep_sock16 behind one of SWEEP_SAMPLERS — or ("wide", sampler) —
+    peel_sweep_sock16_wide behind one of SWEEP_WIDE_SAMPLERS.  A pure function of its arguments:
     p the _Geometry's parameters, ensemble "olmos" | "tail_biting" | "protograph", decoder_ok / sock16_ok / deg_sock16_ok the
-    answers of engine.peel_sweep_sock16_supported / sock16_supported / deg_sock16_supported, sweep the requested mode."""
-    if sweep not in ("auto", "first", "small"):
-        raise ValueError("sweep must be 'auto', 'first' or 'small'")
+    answers of engine.peel_sweep_sock16_supported / sock16_supported / deg_sock16_supported, sweep the requested mode,
+    wide_ok / wide_sock16_ok the answers of engine.peel_sweep_wide_supported / wide_sock16_supported (read by "wide", and by
+    "auto" under SWEEP_WIDE_BY_DEFAULT where the small rule has declined)."""
+    if sweep not in ("auto", "first", "small", "wide"):
+        raise ValueError("sweep must be 'auto', 'first', 'small' or 'wide'")
     if sweep == "first":
         return "first", "sweep='first'"
+    if sweep == "wide":
+        return _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock16_ok)
+    if sweep == "auto" and SWEEP_WIDE_BY_DEFAULT:
+        small = select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, "small") if SWEEP_SMALL_BY_DEFAULT else None
+        if small and small[0] == "small":
+            return small
+        wide = _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock16_ok)
+        return wide if wide[0] == "wide" or not small else small
     if sweep == "auto" and not SWEEP_SMALL_BY_DEFAULT:
         return "first", "sweep='auto' is 'first' (SWEEP_SMALL_BY_DEFAULT)"
     if rng != "philox":
@@ -205,15 +242,20 @@ def select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, sweep="
 
 
 def _sweep_choice(p, rng, ensemble, sweep):
-    """select_sweep with the library's answers; sweep='small' on a run it refuses raises."""
+    """select_sweep with the library's answers; sweep='small' / 'wide' on a run it refuses raises."""
     # the default path asks the library nothing it did not ask before
-    asked = sweep == "small" or (sweep == "auto" and SWEEP_SMALL_BY_DEFAULT)
-    answers = (E.peel_sweep_sock16_supported(p), E.sock16_supported(p), E.deg_sock16_supported(p)) if asked else (False,) * 3
-    kind, what = select_sweep(p, rng, ensemble, *answers, sweep)
-    if sweep == "small" and kind != "small":
-        raise ValueError("sweep='small': " + what)
-    if sweep != "auto" or kind == "small":
+    small = sweep == "small" or (sweep == "auto" and SWEEP_SMALL_BY_DEFAULT)
+    wide = sweep == "wide" or (sweep == "auto" and SWEEP_WIDE_BY_DEFAULT)
+    decoder_ok = E.peel_sweep_sock16_supported(p) if small else False
+    sock16_ok, deg_sock16_ok = (E.sock16_supported(p), E.deg_sock16_supported(p)) if small or wide else (False, False)
+    wide_ok, wide_sock16_ok = (E.peel_sweep_wide_supported(p), E.wide_sock16_supported(p)) if wide else (False, False)
+    kind, what = select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, sweep, wide_ok=wide_ok,
+                              wide_sock16_ok=wide_sock16_ok)
+    if sweep in ("small", "wide") and kind != sweep:
+        raise ValueError("sweep='%s': %s" % (sweep, what))
+    if sweep != "auto" or kind != "first":
         line = (what.replace("+", " + ") + " + peel_sweep_small (4-bit CN counts)" if kind == "small" else
+                what.replace("+", " + ") + " + peel_sweep_wide (4-bit CN counts, 32-bit queues)" if kind == "wide" else
                 "%s + peel_sweep (16- or 32-bit CN words): %s" % ("sampler (first generation)" if rng == "philox" else
                                                                   "host streams", what))
         print("[scldpc] kernels: " + line, file=sys.stderr, flush=True)
@@ -226,6 +268,8 @@ def _sample_small(sampler, p, seed, trial0, ntrials, e, doped, device):
         return E.sample_philox_sock16(p, seed, trial0, ntrials, e, doped, device=device)
     if sampler == "sample_philox_deg_sock16":
         return E.sample_philox_deg_sock16(p, seed, trial0, ntrials, e, doped, device=device)
+    if sampler == "sample_philox_wide_sock16":
+        return E.sample_philox_wide_sock16(p, seed, trial0, ntrials, e, doped, device=device)
     d_adj, d_ch = E.sample_philox(p, seed, trial0, ntrials, e, doped, device=device, adj16=True)
     return d_adj, E.cn_sockets(p, d_adj), d_ch
 
@@ -237,7 +281,8 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
     per-trial result rows (32 B each) are all-gathered and every rank runs the same ordered accumulation, so the stop
     rule (max_fuckups, PD:698) cuts at the same trial and every rank returns the same tuple as a single rank would.
     sweep: "first" = peel_sweep, "small" = the 4-bit sweep decoder and the sampler select_sweep names (ValueError where it
-    does not apply), "auto" = what SWEEP_SMALL_BY_DEFAULT says; the same 13-tuple either way."""
+    does not apply), "wide" = its wide form for more than 65 536 CNs per trial (the same), "auto" = what SWEEP_SMALL_BY_DEFAULT
+    and then SWEEP_WIDE_BY_DEFAULT say; the same 13-tuple either way."""
     _check_flags(is_protograph, is_tail_biting)
     device = _device(device)
     dist, rank, world = _dist()
@@ -274,7 +319,7 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
             if soft and is_protograph:
                 raise NameError("name 'position' is not defined")   # the reference's own failure for soft doping (PD:228)
             doped = [] if soft else _doped_positions(doping_points)
-            if kind == "small":
+            if kind in ("small", "wide"):
                 d_adj, d_cn, d_ch = _sample_small(small_sampler, p, seed, done + lo, mine, e, doped, device)
             else:
                 d_adj, d_ch = E.sample_philox(p, seed, done + lo, mine, e, doped, device=device, adj16=(ens == "olmos"),
@@ -286,6 +331,8 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
             raise ValueError("rng must be 'numpy' or 'philox'")
         if kind == "small":
             d_out = E.peel_sweep_sock16(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
+        elif kind == "wide":
+            d_out = E.peel_sweep_sock16_wide(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
         else:
             d_out = E.peel_sweep(p, d_adj, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
         if world > 1:
@@ -521,14 +568,14 @@ def _safe_eval(text):
 def _cli_options(args, kw):
     """The reference's command lines are positional only.  This mirror also takes, anywhere among them,
     `--rng philox|numpy`, `--seed S`, `--batch B`, `--device D` — the keyword arguments of the simulators (throughput mode:
-    device sampling, trials sharded over the ranks of a torch.distributed.run job) — and `--sweep first|small|auto`, which
+    device sampling, trials sharded over the ranks of a torch.distributed.run job) — and `--sweep first|small|wide|auto`, which
     only ber_sim (simulate_sc_ldpc) takes."""
     kw, pos, it = dict(kw), [], iter(args)
     for x in it:
         if isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device", "--sweep"):
             v = next(it)
-            if x == "--sweep" and v not in ("first", "small", "auto"):
-                raise SystemExit("--sweep takes first, small or auto (got %r)" % (v,))
+            if x == "--sweep" and v not in ("first", "small", "wide", "auto"):
+                raise SystemExit("--sweep takes first, small, wide or auto (got %r)" % (v,))
             kw[x[2:]] = v if x in ("--rng", "--device", "--sweep") else int(v)
         else:
             pos.append(x)

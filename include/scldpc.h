@@ -431,13 +431,27 @@ int scldpc_peel_sweep_device_adj16(const scldpc_code_params *p, int32_t ntrials,
  * scldpc_sample_philox_device_sock16 / _deg_sock16 / scldpc_cn_sockets_device; no workspace.  d_out columns 0, 1, 2, 7 and
  * d_lost_bits equal scldpc_peel_sweep_device_adj16's bit for bit; [5] counts this kernel's barrier rounds, [6] its scans after
  * the first (0 unless a queue overflowed).  total_size in [0, nk], any sweep_start >= 0.  Checks in a fixed order: parameters,
- * CN ranges (SCLDPC_ERR_BAD_ARG), shape (SCLDPC_ERR_TOO_LARGE, also for ntrials == 0), buffers.  There is no form for more
- * than 65536 CNs, for the CN -> VN table, or for tail-biting / protograph tables (global CN ids). */
+ * CN ranges (SCLDPC_ERR_BAD_ARG), shape (SCLDPC_ERR_TOO_LARGE, also for ntrials == 0), buffers.  More than 65536 CNs per trial
+ * take the _wide form below; there is no form for the CN -> VN table or for tail-biting / protograph tables (global CN ids). */
 int scldpc_peel_sweep_sock16_supported(const scldpc_code_params *p);
 int scldpc_peel_sweep_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                     const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t total_size,
                                     int32_t sweep_start, int32_t lost_lo, int32_t lost_hi, int32_t *d_out,
                                     uint32_t *d_lost_bits, void *stream);
+
+/* The wide form of the same kernel: 32-bit queue entries and one 1024-thread workgroup per CU (one trial per CU), for trials of
+ * any number of CNs whose 4-bit state fits one CU's LDS.  The shape rule (scldpc_peel_sweep_wide_supported, judged at
+ * sweep_start = 0; a launch judges its own): the pairs (3,6), (4,8), (5,10); vns_pos * dv <= 65535; cns_pos <= 65536; an exact
+ * multiply-high division for vns_pos and cns_pos; and, of 160 KiB - 512 B, the count words (nk / 8), the VN words (n / 32), the
+ * frozen bytes (min(sweep_start, total_size) / 8), L position flags and 16 scalars, each region rounded up to 16 bytes, leave
+ * at least 1024 32-bit entries for each of two queues.  (4,8), L = 50, M = 5000 (132 500 CNs) is taken, (4,8), L = 90, M = 5000
+ * (172.5 KB of state) is not.  No lower bound: small shapes run through it too.  Parameters, outputs, order of the checks and
+ * error texts as scldpc_peel_sweep_device_sock16 (the texts start with this entry's name; SCLDPC_ERR_TOO_LARGE names the limit). */
+int scldpc_peel_sweep_wide_supported(const scldpc_code_params *p);
+int scldpc_peel_sweep_device_sock16_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                         const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t total_size,
+                                         int32_t sweep_start, int32_t lost_lo, int32_t lost_hi, int32_t *d_out,
+                                         uint32_t *d_lost_bits, void *stream);
 
 /* One trial of simulate_peeling_decoder_ldpc's loop body (PD:750-785): random-pick peeling with the
  * degree-1-CN trajectory.  num_steps = int(M*num_positions*(e+0.1)) (PD:721).
