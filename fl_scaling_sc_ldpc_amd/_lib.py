@@ -58,6 +58,7 @@ EXPORTS = (
     "scldpc_sample_philox_wide_sock16_supported", "scldpc_sample_philox_device_wide_sock16",
     "scldpc_peel_sweep_sock16_supported", "scldpc_peel_sweep_device_sock16",
     "scldpc_peel_sweep_wide_supported", "scldpc_peel_sweep_device_sock16_wide",
+    "scldpc_peel_pick_deg_supported", "scldpc_peel_pick_deg_workspace_bytes", "scldpc_peel_pick_device_adj16_deg",
 )
 
 
@@ -168,6 +169,10 @@ def lib():
     L.scldpc_peel_sweep_device_sock16_wide.argtypes = L.scldpc_peel_sweep_device_sock16.argtypes
     L.scldpc_peel_pick_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, u64, u64, vp, vp, vp, vp, u64, vp]
     L.scldpc_peel_pick_device_adj16.argtypes = L.scldpc_peel_pick_device.argtypes
+    L.scldpc_peel_pick_deg_supported.argtypes = [pp, i32]
+    L.scldpc_peel_pick_deg_workspace_bytes.argtypes = [pp, i32, i32]
+    L.scldpc_peel_pick_deg_workspace_bytes.restype = i64
+    L.scldpc_peel_pick_device_adj16_deg.argtypes = [pp, i32, vp, vp, i32, i32, u64, u64, vp, vp, vp, u64, vp]
     L.scldpc_r1_moments_device.argtypes = [i32, i32, vp, vp, vp]
     L.scldpc_swc_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_swc_bp_device_adj16.argtypes = L.scldpc_swc_bp_device.argtypes

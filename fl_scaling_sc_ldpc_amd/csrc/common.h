@@ -47,6 +47,9 @@ int allow_max_lds(const void *kernel);
 // cn_build.hip: the CN words [T][nk] of the dv = 4 chain with 2-byte rows built through an LDS ring; false = not applicable
 bool cn_build_launch(const scldpc_code_params *p, int ntrials, const uint16_t *d_vn_adj16, const uint32_t *d_chan_bits,
                      uint32_t *d_words, bool deg, void *stream);
+// the same build for dv = 3, 4, 5 (peel_pick.hip's _deg entry alone): 0, or the error of its LDS attribute or launch
+int cn_build_launch_deg(const scldpc_code_params *p, int ntrials, const uint16_t *d_vn_adj16, const uint32_t *d_chan_bits,
+                        uint32_t *d_words, void *stream);
 
 // full_bp_small.hip: which limit keeps this ensemble from the narrow socket-table forms of the 4-bit decoders' _deg entry
 // points (the pairs (3,6), (4,8), (5,10); 16-bit sockets; at most 65536 CNs per trial); nullptr: none.  peel_sweep_small.hip

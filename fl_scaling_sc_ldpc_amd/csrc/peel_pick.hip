@@ -16,6 +16,7 @@
 #include "common.h"
 #include "kernel_util.h"
 #include "philox.h"
+#include "table_rows.h"
 
 #ifndef SCLDPC_PICK_SGPRS
 #define SCLDPC_PICK_SGPRS 80
@@ -258,7 +259,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SCLDPC_PICK_
 // 512.  For the layout of BASELINE config 3: CN words and degree-1 bitmap in the
 // workspace, 2-byte rows, dv = 4, Philox draws, at most 262 144 pickable CNs (one bitmap word per lane and block).  The draws,
 // the ascending-order selection and the trajectory are those of peel_pick_kernel, value for value (tests/test_gpu_pd.py).
-template <int TPW>
+// DV = 4 is that layout: a VN row is one aligned 64-bit word.  DV = 3, 5 (scldpc_peel_pick_device_adj16_deg): a row is 6 or 10
+// bytes, so the build reads it as DV 2-byte units and a pick reads one unit on each of the DV lanes that update its CNs
+// (tests/test_gpu_pick_deg.py).
+template <int TPW, int DV>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SCLDPC_PICK_SGPRS))) void peel_pick_multi_kernel(const Args a)
 {
     constexpr int LPT = 64 / TPW, Q = 64 / LPT;                           // lanes per trial; rank-select blocks (and block words) per lane
@@ -274,6 +278,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SCLDPC_PICK_
     uint32_t *cn = a.ws + tix * a.ncn;
     unsigned long long *d1 = a.ws_d1 + tix * a.nd1;
     const unsigned long long *rows = reinterpret_cast<const unsigned long long *>(a.vn_adj) + tix * n;     // 4 x uint16 per VN
+    const uint16_t *rows16 = reinterpret_cast<const uint16_t *>(a.vn_adj) + tix * n * DV;                  // DV != 4
     const uint32_t *chan = a.chan + tix * a.nw;
     auto pos_of = [&](int j) { return (int)__umulhi((uint32_t)j, a.magic_v); };
     auto ldw = [&](int c) { return __hip_atomic_load(&cn[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
@@ -303,11 +308,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SCLDPC_PICK_
     if (valid && !a.prebuilt) {
         for (int j = sl; j < n; j += LPT) {
             if ((chan[j >> 5] >> (j & 31)) & 1u) {
-                const unsigned long long r = rows[j];
                 const int base = pos_of(j) * a.cns_pos;
+                if constexpr (DV == 4) {
+                    const unsigned long long r = rows[j];
 #pragma unroll
-                for (int i = 0; i < 4; i++)
-                    atomicAdd(&cn[base + i * a.cns_pos + (int)((r >> (16 * i)) & 0xFFFFull)], kCntOne + (uint32_t)j);
+                    for (int i = 0; i < 4; i++)
+                        atomicAdd(&cn[base + i * a.cns_pos + (int)((r >> (16 * i)) & 0xFFFFull)], kCntOne + (uint32_t)j);
+                } else {
+                    const Row<DV> r = load_row<DV>(rows16, j);
+#pragma unroll
+                    for (int i = 0; i < DV; i++) atomicAdd(&cn[base + i * a.cns_pos + (int)r[i]], kCntOne + (uint32_t)j);
+                }
             }
         }
     }
@@ -391,12 +402,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(SCLDPC_PICK_
         }
         m = (int)from((uint32_t)m, W0s);
         if (!alive || (unsigned)m >= (unsigned)ts) m = 0;                  // (m < ts whenever the counts and the bitmap agree)
-        // ---- remove its single VN from its four CNs (PD:769-777) ---------------------------------------------------------------
+        // ---- remove its single VN from its DV CNs (PD:769-777) -----------------------------------------------------------------
         const int j = (int)(ldw(m) & kSumMask);
-        const unsigned long long row = rows[alive ? j : 0];
+        unsigned long long row = 0ull;
+        if constexpr (DV == 4) row = rows[alive ? j : 0];
         bool plus = false, minus = false;
-        if (alive && sl < 4) {
-            const int c = (pos_of(j) + sl) * a.cns_pos + (int)((row >> (16 * sl)) & 0xFFFFull);
+        if (alive && sl < DV) {
+            int local;
+            if constexpr (DV == 4) local = (int)((row >> (16 * sl)) & 0xFFFFull);
+            else                   local = (int)rows16[(size_t)j * DV + sl];                 // (alive: m holds one VN, j < n)
+            const int c = (pos_of(j) + sl) * a.cns_pos + local;
             const uint32_t nc = (atomicSub(&cn[c], kCntOne + (uint32_t)j) >> kCntShift) - 1u;
             if (c < ts) {
                 minus = nc == 0u;                                         // was 1
@@ -502,7 +517,7 @@ static int launch_peel_pick(const scldpc_code_params *p, int32_t ntrials, const 
         bool pre = true;
         if (const char *v = getenv("SCLDPC_DEBUG_PICK_PREBUILD")) pre = atoi(v) != 0;                      // A/B, tests
         a.prebuilt = pre && scldpc::cn_build_launch(p, ntrials, static_cast<const uint16_t *>(d_vn_adj), d_chan_bits, a.ws, false, stream) ? 1 : 0;
-        kern = tpw == 2 ? peel_pick_multi_kernel<2> : peel_pick_multi_kernel<4>;
+        kern = tpw == 2 ? peel_pick_multi_kernel<2, 4> : peel_pick_multi_kernel<4, 4>;
         hipLaunchKernelGGL(kern, dim3((ntrials + tpw - 1) / tpw), dim3(kBlock), (size_t)tpw * (64 + 256) * 4, static_cast<hipStream_t>(stream), a);
         SCLDPC_HIP_CHECK(hipGetLastError());
         return SCLDPC_OK;
@@ -543,4 +558,99 @@ int64_t scldpc_peel_pick_workspace_query(const scldpc_code_params *p, int32_t nt
     const int rc = launch_peel_pick(p, ntrials, nullptr, true, nullptr, total_size, 0, rng_mt ? &dummy : nullptr, 0, 0,
                                     nullptr, nullptr, nullptr, scldpc::Scratch{nullptr, 0, &need}, nullptr);
     return rc ? (int64_t)rc : (int64_t)need;
+}
+
+// ---- the pairs (3,6), (4,8), (5,10): ring build + several trials per wave, an entry of its own -------------------------------
+namespace {
+
+constexpr const char *kDegEntry = "scldpc_peel_pick_device_adj16_deg";
+
+// The shape rule of scldpc_peel_pick_deg_supported, in the documented order; 0, or the error with the limit that refuses.
+int pick_deg_rule(const scldpc_code_params *p, int32_t total_size, uint32_t *magic_v)
+{
+    if (int rc = scldpc::check_params(p)) return rc;
+    if (!((p->dv == 3 && p->dc == 6) || (p->dv == 4 && p->dc == 8) || (p->dv == 5 && p->dc == 10)))
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: the pairs (3,6), (4,8), (5,10) only: no instance for dv = %d, dc = %d",
+                                 kDegEntry, p->dv, p->dc);
+    if (p->cns_pos > 65536)
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: 2-byte rows: cns_pos = %d exceeds 65536", kDegEntry, p->cns_pos);
+    const int64_t nk = (int64_t)(p->L + p->dv - 1) * p->cns_pos, n = (int64_t)p->L * p->vns_pos;
+    if (total_size < 0 || (int64_t)total_size > nk)
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: total_size = %d outside [0,%lld]", kDegEntry, total_size, (long long)nk);
+    const int nd1 = (total_size + 63) / 64 + 1;
+    if (nd1 > 4096)
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: the degree-1 bitmap takes %d words, at most 4096 (262080 pickable CNs)",
+                                 kDegEntry, nd1);
+    if ((int64_t)p->dc * n >= (1ll << kDegShift))
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: needs dc * n < 2^24 (dc = %d, n = %lld)", kDegEntry, p->dc, (long long)n);
+    uint32_t magic = 0;
+    if (!scldpc::magic_of(p->vns_pos, n, &magic))
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: reciprocal division by vns_pos = %d inexact", kDegEntry, p->vns_pos);
+    const int64_t ring = (int64_t)p->dv * 4 * p->cns_pos;
+    if (ring > (int64_t)scldpc::kMaxLdsBytes)
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: LDS: the ring of %d CN positions takes %lld B, at most %d",
+                                 kDegEntry, p->dv, (long long)ring, scldpc::kMaxLdsBytes);
+    if (magic_v) *magic_v = magic;
+    return SCLDPC_OK;
+}
+
+template <int TPW>
+void (*pick_multi_of(int dv))(const Args)
+{
+    return dv == 3 ? peel_pick_multi_kernel<TPW, 3> : dv == 4 ? peel_pick_multi_kernel<TPW, 4> : peel_pick_multi_kernel<TPW, 5>;
+}
+
+}  // namespace
+
+extern "C" int scldpc_peel_pick_deg_supported(const scldpc_code_params *p, int32_t total_size)
+{
+    return pick_deg_rule(p, total_size, nullptr) == SCLDPC_OK ? 1 : 0;
+}
+
+extern "C" int64_t scldpc_peel_pick_deg_workspace_bytes(const scldpc_code_params *p, int32_t ntrials, int32_t total_size)
+{
+    if (int rc = pick_deg_rule(p, total_size, nullptr)) return rc;
+    if (ntrials < 0) return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_peel_pick_deg_workspace_bytes: negative ntrials");
+    const int64_t cn_bytes = (((int64_t)ntrials * scldpc::nk_of(p) * 4) + 255) & ~(int64_t)255;
+    return cn_bytes + (int64_t)ntrials * ((total_size + 63) / 64 + 1) * 8;
+}
+
+extern "C" int scldpc_peel_pick_device_adj16_deg(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                                 const uint32_t *d_chan_bits, int32_t total_size, int32_t num_steps,
+                                                 uint64_t seed, uint64_t trial0, int32_t *d_r1, int32_t *d_out,
+                                                 void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    Args a{};
+    if (int rc = pick_deg_rule(p, total_size, &a.magic_v)) return rc;
+    if (ntrials < 0 || num_steps < 0)
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: negative ntrials or num_steps", kDegEntry);
+    if (ntrials == 0) return SCLDPC_OK;
+    if (!d_vn_adj16 || !d_chan_bits || !d_out)
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer", kDegEntry);
+    const int64_t need = scldpc_peel_pick_deg_workspace_bytes(p, ntrials, total_size);
+    if (!d_workspace || (int64_t)workspace_bytes < need)
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: needs %lld bytes of device workspace (scldpc_peel_pick_deg_workspace_bytes), "
+                                 "the caller passed %llu", kDegEntry, (long long)need, (unsigned long long)(d_workspace ? workspace_bytes : 0));
+    if (reinterpret_cast<uintptr_t>(d_workspace) & 255u)
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: the workspace must be 256-byte aligned", kDegEntry);
+    const int n = scldpc::n_of(p), ncn = scldpc::nk_of(p);
+    a.dv = p->dv; a.vns_pos = p->vns_pos; a.cns_pos = p->cns_pos; a.n = n; a.ncn = ncn; a.total_size = total_size;
+    a.steps = num_steps; a.nw = (n + 31) / 32; a.nd1 = (total_size + 63) / 64 + 1;
+    a.rng_mode = 1; a.ntrials = ntrials; a.bshift = 12;
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.trial0 = trial0;
+    const size_t cn_bytes = (((size_t)ntrials * ncn * sizeof(uint32_t)) + 255) & ~(size_t)255;
+    a.ws = static_cast<uint32_t *>(d_workspace);
+    a.ws_d1 = reinterpret_cast<unsigned long long *>(static_cast<char *>(d_workspace) + cn_bytes);
+    a.vn_adj = d_vn_adj16; a.chan = d_chan_bits; a.r1 = d_r1; a.out = d_out;
+    int tpw = 2;
+    if (const char *v = getenv("SCLDPC_DEBUG_PICK_TPW")) tpw = atoi(v) == 4 ? 4 : 2;                    // A/B, tests
+    bool pre = true;
+    if (const char *v = getenv("SCLDPC_DEBUG_PICK_PREBUILD")) pre = atoi(v) != 0;                       // A/B, tests
+    if (pre)                                  // an error is the caller's: the kernel's own build never stands in silently
+        if (int rc = scldpc::cn_build_launch_deg(p, ntrials, d_vn_adj16, d_chan_bits, a.ws, stream)) return rc;
+    a.prebuilt = pre ? 1 : 0;
+    void (*kern)(const Args) = tpw == 2 ? pick_multi_of<2>(p->dv) : pick_multi_of<4>(p->dv);
+    hipLaunchKernelGGL(kern, dim3((ntrials + tpw - 1) / tpw), dim3(kBlock), (size_t)tpw * (64 + 256) * 4, static_cast<hipStream_t>(stream), a);
+    SCLDPC_HIP_CHECK(hipGetLastError());
+    return SCLDPC_OK;
 }

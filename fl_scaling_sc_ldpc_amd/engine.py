@@ -668,6 +668,35 @@ def peel_pick(p, d_adj, d_chan, total_size, num_steps, mt_state=None, seed=0, tr
     return {"out": out, "r1": r1, "moments": moments}
 
 
+def peel_pick_deg_supported(p, total_size):
+    """The pairs (3,6), (4,8), (5,10) with 2-byte rows, at most 4096 words of degree-1 bitmap and a ring of dv CN positions
+    within the LDS: peel_pick_deg takes the ensemble at this total_size (scldpc_peel_pick_deg_supported; on False
+    lib().scldpc_last_error() names the limit).  Needs no device."""
+    return bool(lib().scldpc_peel_pick_deg_supported(C.byref(p), int(total_size)))
+
+
+def peel_pick_deg(p, d_adj16, d_chan, total_size, num_steps, seed=0, trial0=0, want_r1=True):
+    """scldpc_peel_pick_device_adj16_deg: peel_pick with Philox draws from the 2-byte rows of the pairs (3,6), (4,8), (5,10),
+    the CN words built through an LDS ring and two trials stepped per wave — `out` and `r1` value for value peel_pick's.
+    No fallback: a shape it does not take raises."""
+    _require_gpu()
+    T = d_adj16.shape[0]
+    assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous() and tuple(d_adj16.shape[1:]) == (p.n, p.dv)
+    assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous() and tuple(d_chan.shape) == (T, p.nw)
+    dev = d_adj16.device
+    out = torch.empty((T, 4), dtype=torch.int32, device=dev)
+    r1 = torch.empty((T, num_steps + 1), dtype=torch.int32, device=dev) if want_r1 else None
+    nbytes = lib().scldpc_peel_pick_deg_workspace_bytes(C.byref(p), T, int(total_size))
+    if nbytes < 0:
+        check(int(nbytes))
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    check(lib().scldpc_peel_pick_device_adj16_deg(C.byref(p), T, d_adj16.data_ptr(), d_chan.data_ptr(), int(total_size),
+                                                  int(num_steps), int(seed), int(trial0),
+                                                  r1.data_ptr() if r1 is not None else None, out.data_ptr(), ws.data_ptr(),
+                                                  int(nbytes), _stream_ptr(dev)))
+    return {"out": out, "r1": r1}
+
+
 def r1_moments(d_r1, moments=None):
     """(cnt, Σr1, Σr1²) per step over a batch of trajectories, accumulated into int64 [3, steps+1]."""
     T, ncols = d_r1.shape

@@ -368,9 +368,56 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
             total_blocks_failed_exp / total_blocks_generated)
 
 
+# Whether simulate_peeling_decoder_ldpc(pick="auto") takes engine.peel_pick_deg (the CN words through cn_build.hip's LDS ring,
+# two trials per wave in peel_pick_multi_kernel, for the pairs (3,6), (4,8), (5,10)) where select_pick allows it, instead of
+# engine.peel_pick: True only if every repetition of the new path beats every repetition of the old one on every shape of
+# tools/pick_deg_speedup.py, with equal outputs (profiles/pick_deg_speedup.json).  Kept False here whatever is
+# measured: the flip is a change of its own.
+PICK_DEG_BY_DEFAULT = False
+
+
+def select_pick(p, total_size, rng, ensemble, moments_from, deg_ok, pick="auto"):
+    """Which random-pick decoder a simulate_peeling_decoder_ldpc run takes: ("first", reason) — engine.peel_pick — or
+    ("multi", "cn_build ring + peel_pick_multi") — engine.peel_pick_deg.  A pure function of its arguments: ensemble is
+    "olmos" or "protograph", moments_from the resolved source of the moments ("rows" where none are wanted), deg_ok the
+    answer of engine.peel_pick_deg_supported(p, total_size), pick the requested mode."""
+    if pick not in ("auto", "first", "multi"):
+        raise ValueError("pick must be 'auto', 'first' or 'multi'")
+    if pick == "first":
+        return "first", "pick='first'"
+    if pick == "auto" and not PICK_DEG_BY_DEFAULT:
+        return "first", "pick='auto' is 'first' (PICK_DEG_BY_DEFAULT)"
+    if rng != "philox":
+        return "first", "rng=%r replays the MT19937 stream, which is sequential: the multi-trial pick kernel draws from Philox" % (rng,)
+    if ensemble == "protograph":
+        return "first", "the protograph tables hold global CN ids in 4-byte rows: the multi-trial pick kernel reads position-local 2-byte rows"
+    if moments_from == "kernel":
+        return "first", "moments_from='kernel': the multi-trial pick kernel has no in-chain moments (use 'rows')"
+    if not deg_ok:
+        return "first", ("the multi-trial pick kernel takes the pairs (3,6), (4,8), (5,10) with cns_pos <= 65536, at most 4096 "
+                         "words of degree-1 bitmap and a ring of dv CN positions within the LDS (dv = %d, dc = %d, L = %d, M = %d, "
+                         "total_size = %d)" % (p.dv, p.dc, p.L, p.vns_pos, total_size))
+    return "multi", "cn_build ring + peel_pick_multi"
+
+
+def _pick_choice(p, total_size, rng, ensemble, moments_from, pick):
+    """select_pick with the library's answer; pick='multi' on a run it refuses raises."""
+    # the default path asks the library nothing it did not ask before
+    ask = pick == "multi" or (pick == "auto" and PICK_DEG_BY_DEFAULT)
+    deg_ok = E.peel_pick_deg_supported(p, total_size) if ask else False
+    kind, what = select_pick(p, total_size, rng, ensemble, moments_from, deg_ok, pick)
+    if pick == "multi" and kind != "multi":
+        raise ValueError("pick='multi': %s" % what)
+    if pick != "auto" or kind != "first":
+        sampler = "sampler (first generation)" if rng == "philox" else "host streams"
+        line = ("%s + %s" % (sampler, what) if kind == "multi" else "%s + peel_pick: %s" % (sampler, what))
+        print("[scldpc] kernels: " + line, file=sys.stderr, flush=True)
+    return kind
+
+
 def simulate_peeling_decoder_ldpc(e, l_deg, r_deg, L, M, is_terminated, is_protograph, num_repeats=None,
                                   doping_points=[], rng="numpy", seed=0, batch=None, device=None,
-                                  want_moments=False, moments_from="auto"):
+                                  want_moments=False, moments_from="auto", pick="auto"):
     """Random-pick peeling with the degree-1-CN trajectory (PD:705-789): returns (None, r1, plrs) with
     r1 int64 [num_repeats, num_pd_steps+1] and plrs float64 [num_repeats].  want_moments=True (philox mode) returns
     (None, moments int64 [3, num_pd_steps+1], plrs) instead of the full trajectories; moments_from: "rows" (the batch's
@@ -378,7 +425,9 @@ def simulate_peeling_decoder_ldpc(e, l_deg, r_deg, L, M, is_terminated, is_proto
     row buffer) or "auto" (rows where they fit 24 GB).
     rng="philox" under torch.distributed: rank r runs a contiguous share of the trials (global trial indices, so the
     draws do not depend on the sharding); one all-reduce sums the moment vectors (24 B per step) and fills in plrs —
-    and the r1 rows when they are asked for — so every rank returns what a single rank would."""
+    and the r1 rows when they are asked for — so every rank returns what a single rank would.
+    pick: "first" = engine.peel_pick, "multi" = engine.peel_pick_deg (ValueError where select_pick refuses; with want_moments
+    it resolves moments_from="auto" to "rows"), "auto" = what PICK_DEG_BY_DEFAULT says; the same arrays either way."""
     if not num_repeats:
         num_repeats = 100
     device = _device(device)
@@ -394,6 +443,9 @@ def simulate_peeling_decoder_ldpc(e, l_deg, r_deg, L, M, is_terminated, is_proto
     nd = len(doping_points)
     p = E.CodeParams(l_deg, r_deg, L, cpp, M)
     total_generated = (L - nd) * M                                         # PD:747
+    kind = _pick_choice(p, total_size, rng, "protograph" if is_protograph else "olmos", moments_from if want_moments else "rows", pick)
+    if kind == "multi" and want_moments and moments_from == "auto":
+        moments_from = "rows"
     plrs = np.zeros(num_repeats)
     if rng == "numpy":
         r1 = np.zeros((num_repeats, num_pd_steps + 1), dtype="int")
@@ -437,8 +489,11 @@ def simulate_peeling_decoder_ldpc(e, l_deg, r_deg, L, M, is_terminated, is_proto
         rows_first = want_moments and (moments_from == "rows" or
                                        (moments_from == "auto" and
                                         4 * (num_pd_steps + 1) * nb <= min(24e9, 0.25 * _free_bytes(device))))
-        res = E.peel_pick(p, d_adj, d_ch, total_size, num_pd_steps, mt_state=None, seed=seed, trial0=done,
-                          want_r1=not want_moments or rows_first, moments=None if rows_first else moments)
+        if kind == "multi":
+            res = E.peel_pick_deg(p, d_adj, d_ch, total_size, num_pd_steps, seed=seed, trial0=done, want_r1=True)
+        else:
+            res = E.peel_pick(p, d_adj, d_ch, total_size, num_pd_steps, mt_state=None, seed=seed, trial0=done,
+                              want_r1=not want_moments or rows_first, moments=None if rows_first else moments)
         if rows_first:
             E.r1_moments(res["r1"], moments)
             res["r1"] = None
@@ -568,15 +623,18 @@ def _safe_eval(text):
 def _cli_options(args, kw):
     """The reference's command lines are positional only.  This mirror also takes, anywhere among them,
     `--rng philox|numpy`, `--seed S`, `--batch B`, `--device D` — the keyword arguments of the simulators (throughput mode:
-    device sampling, trials sharded over the ranks of a torch.distributed.run job) — and `--sweep first|small|wide|auto`, which
-    only ber_sim (simulate_sc_ldpc) takes."""
+    device sampling, trials sharded over the ranks of a torch.distributed.run job) — `--sweep first|small|wide|auto`, which
+    only ber_sim (simulate_sc_ldpc) takes, and `--pick first|multi|auto`, which only simulate_variance
+    (simulate_peeling_decoder_ldpc) takes."""
     kw, pos, it = dict(kw), [], iter(args)
     for x in it:
-        if isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device", "--sweep"):
+        if isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device", "--sweep", "--pick"):
             v = next(it)
             if x == "--sweep" and v not in ("first", "small", "wide", "auto"):
                 raise SystemExit("--sweep takes first, small, wide or auto (got %r)" % (v,))
-            kw[x[2:]] = v if x in ("--rng", "--device", "--sweep") else int(v)
+            if x == "--pick" and v not in ("first", "multi", "auto"):
+                raise SystemExit("--pick takes first, multi or auto (got %r)" % (v,))
+            kw[x[2:]] = v if x in ("--rng", "--device", "--sweep", "--pick") else int(v)
         else:
             pos.append(x)
     return pos, kw
@@ -596,6 +654,9 @@ def _join_job(kw):
 def main_simulate_sc_ldpc(argv=None, **kw):
     """ber_sim.py: OUT l r L M "es" T|N U|P B|N TB|NTB num_repeats max_fuckups "doping" (PD:1327-1356)."""
     a, kw = _cli_options(sys.argv if argv is None else [None] + list(argv), kw)
+    if "pick" in kw:
+        raise SystemExit("--pick chooses the random-pick decoder of simulate_variance (simulate_peeling_decoder_ldpc): ber_sim "
+                         "runs the sweep decoder and takes no such option")
     joined = _join_job(kw)
     try:
         return _main_simulate_sc_ldpc(a, kw)

@@ -474,6 +474,26 @@ int scldpc_peel_pick_device_adj16(const scldpc_code_params *p, int32_t ntrials,
                                   uint32_t *d_mt_state, uint64_t seed, uint64_t trial0,
                                   int32_t *d_r1, int64_t *d_moments, int32_t *d_out, void *d_workspace, uint64_t workspace_bytes, void *stream);
 
+/* The same trial for the pairs (3,6), (4,8), (5,10) from 2-byte rows, Philox draws only (no MT19937 state, no in-kernel moments):
+ * the CN words of every trial are built through a ring of dv CN positions in LDS and two trials are stepped per wave (four with
+ * SCLDPC_DEBUG_PICK_TPW=4; SCLDPC_DEBUG_PICK_PREBUILD=0 has the pick kernel build its own CN words) — what
+ * scldpc_peel_pick_device_adj16 does at dv = 4 beyond the LDS budget, and value for value the d_r1 and d_out it writes for every
+ * shape both take.  The shape rule (scldpc_peel_pick_deg_supported; pure, needs no device; on 0 scldpc_last_error() names the
+ * limit), checked in this order: valid parameters; the pairs (3,6), (4,8), (5,10); cns_pos <= 65536; 0 <= total_size <= nk;
+ * ceil(total_size / 64) + 1 <= 4096 bitmap words; dc * n < 2^24; an exact multiply-high division by vns_pos; dv * 4 * cns_pos
+ * <= 160 KiB (the ring).  No lower bound: small shapes run through it too, with CN words and bitmap always in the workspace.
+ * scldpc_peel_pick_deg_workspace_bytes: ntrials * nk * 4 rounded up to 256, plus ntrials * (ceil(total_size / 64) + 1) * 8
+ * (negative: the error code of a refused shape).  The entry checks the shape first (SCLDPC_ERR_TOO_LARGE with the rule's
+ * text, even for an empty batch), then negative counts, then — ntrials == 0 is SCLDPC_OK here — null buffers and a short or not
+ * 256-byte-aligned workspace (SCLDPC_ERR_BAD_ARG).  A failure of the ring build (its LDS attribute or its launch) is returned
+ * as SCLDPC_ERR_HIP: no other build stands in.  d_r1 optional; d_out as scldpc_peel_pick_device. */
+int scldpc_peel_pick_deg_supported(const scldpc_code_params *p, int32_t total_size);
+int64_t scldpc_peel_pick_deg_workspace_bytes(const scldpc_code_params *p, int32_t ntrials, int32_t total_size);
+int scldpc_peel_pick_device_adj16_deg(const scldpc_code_params *p, int32_t ntrials,
+                                      const uint16_t *d_vn_adj16, const uint32_t *d_chan_bits,
+                                      int32_t total_size, int32_t num_steps, uint64_t seed, uint64_t trial0,
+                                      int32_t *d_r1, int32_t *d_out, void *d_workspace, uint64_t workspace_bytes, void *stream);
+
 /* Integer moments of a batch of trajectories, the device half of main_simulate_variance (PD:1264-1294) /
  * calc_nu_chunk (fl_scaling/est_scaling_params.py:90-94,131-138): d_moments int64 [3][ncols], accumulated in
  * place: [0][s] += #{r1[t][s] != 0}, [1][s] += Σ_t r1[t][s], [2][s] += Σ_t r1[t][s]². */
