@@ -31,6 +31,18 @@ def _stream_ptr(device):
 WS_SAMPLE, WS_FULL_BP, WS_SW_BP, WS_PEEL_SWEEP, WS_PEEL_PICK = range(5)      # SCLDPC_WS_*
 
 
+def _uninit(shape, dtype, device):
+    """Every kernel output and workspace of this module is allocated here, uninitialised: the kernels define every element the
+    header's "Buffers" paragraph lists and rely on no earlier content.  (The one seam the buffer-contract tests replace.)"""
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _zeroed(shape, dtype, device):
+    """The trajectory rows of the full_bp* wrappers: the kernels write rows [0, min(iterations, rows_cap)) of a trial and leave
+    the rest alone; every wrapper hands the rest back as zeros."""
+    return _uninit(shape, dtype, device).zero_()
+
+
 def _workspace(op, p, ntrials, device, arg0=0, arg1=0):
     """(device pointer, bytes) of a caller-owned workspace for one call, or (None, 0) when the ensemble needs none.
     A fresh torch buffer per call: the caching allocator hands memory back only to the stream that used it, so calls
@@ -40,7 +52,7 @@ def _workspace(op, p, ntrials, device, arg0=0, arg1=0):
         check(int(nbytes))
     if nbytes == 0:
         return None, 0, None
-    buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    buf = _uninit(int(nbytes), dtype=torch.uint8, device=device)
     return buf.data_ptr(), int(nbytes), buf
 
 
@@ -122,8 +134,8 @@ def sample_philox(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0", out=
     ensemble: "olmos" (generate_code / sc_ldpc.gen_slots), "tail_biting" or "protograph" (global CN ids)."""
     _require_gpu()
     if out is None:
-        d_adj = torch.empty((ntrials, p.n, p.dv), dtype=torch.int16 if adj16 else torch.int32, device=device)
-        d_ch = torch.empty((ntrials, p.nw), dtype=torch.int32, device=device)
+        d_adj = _uninit((ntrials, p.n, p.dv), dtype=torch.int16 if adj16 else torch.int32, device=device)
+        d_ch = _uninit((ntrials, p.nw), dtype=torch.int32, device=device)
     else:
         d_adj, d_ch = out
     darr, dptr = _lib.doped_array(doped)
@@ -178,9 +190,9 @@ def _sample_philox_tables(fn, p, seed, trial0, ntrials, eps, doped, device, out,
     second-generation sampler."""
     _require_gpu()
     if out is None:
-        d_adj = torch.empty((ntrials, p.n, p.dv), dtype=torch.int16, device=device)
-        d_cn = torch.empty((ntrials, p.nk, p.dc), dtype=torch.int16, device=device) if want_cn else None
-        d_ch = torch.empty((ntrials, p.nw), dtype=torch.int32, device=device)
+        d_adj = _uninit((ntrials, p.n, p.dv), dtype=torch.int16, device=device)
+        d_cn = _uninit((ntrials, p.nk, p.dc), dtype=torch.int16, device=device) if want_cn else None
+        d_ch = _uninit((ntrials, p.nw), dtype=torch.int32, device=device)
     else:
         d_adj, d_cn, d_ch = out
     darr, dptr = _lib.doped_array(doped)
@@ -259,9 +271,9 @@ def sample_philox_sock(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0",
     the sampler's own launch, for every ensemble sample_philox takes with 16-bit sockets."""
     _require_gpu()
     if out is None:
-        d_adj = torch.empty((ntrials, p.n, p.dv), dtype=torch.int16, device=device)
-        d_cn = torch.empty((ntrials, p.nk, p.dc), dtype=torch.int16, device=device)
-        d_ch = torch.empty((ntrials, p.nw), dtype=torch.int32, device=device)
+        d_adj = _uninit((ntrials, p.n, p.dv), dtype=torch.int16, device=device)
+        d_cn = _uninit((ntrials, p.nk, p.dc), dtype=torch.int16, device=device)
+        d_ch = _uninit((ntrials, p.nw), dtype=torch.int32, device=device)
     else:
         d_adj, d_cn, d_ch = out
     darr, dptr = _lib.doped_array(doped)
@@ -315,10 +327,10 @@ def global_to_adj16(p, adj):
 # ------------------------------------------------------------------------------------------------
 # decoding
 # ------------------------------------------------------------------------------------------------
-def _full_bp(p, d_adj, d_cn, d_chan, call, counters=None, want_erased=False, rows_cap=0, new_rows=torch.empty, ncaps=0):
+def _full_bp(p, d_adj, d_cn, d_chan, call, counters=None, want_erased=False, rows_cap=0, new_rows=None, ncaps=0):
     """The one body of the full_bp* wrappers.  Checks the tensors against p — d_cn None: the first-generation decoders, which
     take the 4-byte VN -> CN table too; else the 2-byte tables of the 4-bit decoders — allocates counters [T,8] ([ncaps,T,8]),
-    rows [T,rows_cap,3] (by new_rows) and erased [T,nw] where asked, and calls
+    rows [T,rows_cap,3] (by new_rows; None: _uninit, looked up at call time) and erased [T,nw] where asked, and calls
     call(head, counters, rows, erased, stream) with head = (p, T, the tables, the channel) and every tensor as its pointer."""
     _require_gpu()
     T = d_adj.shape[0]
@@ -330,10 +342,10 @@ def _full_bp(p, d_adj, d_cn, d_chan, call, counters=None, want_erased=False, row
     dev = d_adj.device
     shape = (ncaps, T, NCOUNTERS) if ncaps else (T, NCOUNTERS)
     if counters is None:
-        counters = torch.empty(shape, dtype=torch.int32, device=dev)
+        counters = _uninit(shape, dtype=torch.int32, device=dev)
     assert not ncaps or (counters.is_contiguous() and counters.dtype == torch.int32 and tuple(counters.shape) == shape)
-    rows = new_rows((T, rows_cap, 3), dtype=torch.int32, device=dev) if rows_cap > 0 else None
-    erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
+    rows = (new_rows or _uninit)((T, rows_cap, 3), dtype=torch.int32, device=dev) if rows_cap > 0 else None
+    erased = _uninit((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
     head = (C.byref(p), T, d_adj.data_ptr()) + ((d_cn.data_ptr(),) if d_cn is not None else ()) + (d_chan.data_ptr(),)
     check(call(head, counters.data_ptr(), rows.data_ptr() if rows is not None else None,
                erased.data_ptr() if erased is not None else None, _stream_ptr(dev)))
@@ -342,13 +354,14 @@ def _full_bp(p, d_adj, d_cn, d_chan, call, counters=None, want_erased=False, row
 
 def full_bp(p, d_adj, d_chan, max_it=0, is_term=True, rows_cap=0, want_erased=False, counters=None):
     """decodeBP for a batch resident on the device.  Returns dict of device tensors:
-    counters int32 [T,8] (+ rows int32 [T,rows_cap,3], erased int32 [T,nw] when asked)."""
+    counters int32 [T,8] (+ rows int32 [T,rows_cap,3], erased int32 [T,nw] when asked).  Rows beyond a trial's iteration count
+    (counters[t, 5]) are zeros, here and in every full_bp* wrapper that takes rows_cap."""
     fn = lib().scldpc_full_bp_device_adj16 if _is_adj16(d_adj) else lib().scldpc_full_bp_device
 
     def call(head, cnt, rows, erased, stream):
         ws, wsb, _keep = _workspace(WS_FULL_BP, p, head[1], d_adj.device, 1 if rows is not None else 0)
         return fn(*head, int(max_it), 1 if is_term else 0, cnt, rows, int(rows_cap), erased, ws, wsb, stream)
-    return _full_bp(p, d_adj, None, d_chan, call, counters, want_erased, rows_cap, torch.zeros)
+    return _full_bp(p, d_adj, None, d_chan, call, counters, want_erased, rows_cap, _zeroed)
 
 
 def full_bp_fixpoint(p, d_adj, d_chan, is_term=True, want_erased=False, counters=None):
@@ -392,7 +405,8 @@ def full_bp_cn16(p, d_adj16, d_cn16, d_chan, max_it=0, is_term=True, want_erased
         fn = L.scldpc_full_bp_traj_device_sock16 if sockets else L.scldpc_full_bp_traj_device_cn16
     else:
         fn = L.scldpc_full_bp_device_sock16 if sockets else L.scldpc_full_bp_device_cn16
-    return _full_bp(p, d_adj16, d_cn16, d_chan, _level_call(fn, max_it, is_term, rows_cap), counters, want_erased, rows_cap)
+    return _full_bp(p, d_adj16, d_cn16, d_chan, _level_call(fn, max_it, is_term, rows_cap), counters, want_erased, rows_cap,
+                    _zeroed)                        # zeros, as full_bp's
 
 
 def full_bp_wide_supported(p):
@@ -407,7 +421,7 @@ def full_bp_wide(p, d_adj16, d_cn_sock, d_chan, max_it=0, is_term=True, rows_cap
     d_cn_sock: cn_sockets(p, d_adj16) or sample_philox_sock16's table."""
     fn = lib().scldpc_full_bp_traj_device_wide if rows_cap > 0 else lib().scldpc_full_bp_device_wide
     return _full_bp(p, d_adj16, d_cn_sock, d_chan, _level_call(fn, max_it, is_term, rows_cap), counters, want_erased, rows_cap,
-                    torch.zeros)                        # zeros, as full_bp's
+                    _zeroed)                        # zeros, as full_bp's
 
 
 def full_bp_deg_supported(p, wide=False):
@@ -423,7 +437,7 @@ def full_bp_deg(p, d_adj16, d_cn_sock, d_chan, max_it=0, is_term=True, rows_cap=
     cn_sockets(p, d_adj16); the same dict as full_bp_cn16 / full_bp_wide."""
     name = "scldpc_full_bp_%sdevice_deg%s" % ("traj_" if rows_cap > 0 else "", "_wide" if wide else "")
     return _full_bp(p, d_adj16, d_cn_sock, d_chan, _level_call(getattr(lib(), name), max_it, is_term, rows_cap), counters,
-                    want_erased, rows_cap, torch.zeros)                 # zeros, as full_bp's
+                    want_erased, rows_cap, _zeroed)                 # zeros, as full_bp's
 
 
 def full_bp_fixpoint_deg(p, d_adj16, d_cn_sock, d_chan, is_term=True, want_erased=False, counters=None):
@@ -478,7 +492,7 @@ def cn_sockets(p, d_adj16, out=None):
     T = d_adj16.shape[0]
     assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous()
     if out is None:
-        out = torch.empty((T, p.nk, p.dc), dtype=torch.int16, device=d_adj16.device)
+        out = _uninit((T, p.nk, p.dc), dtype=torch.int16, device=d_adj16.device)
     check(lib().scldpc_cn_sockets_device(C.byref(p), T, d_adj16.data_ptr(), out.data_ptr(), _stream_ptr(d_adj16.device)))
     return out
 
@@ -510,8 +524,8 @@ def sw_bp(p, d_adj, d_chan, W, max_it, init_it=0, want_erased=False, counters=No
     assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
     dev = d_adj.device
     if counters is None:
-        counters = torch.empty((T, NCOUNTERS), dtype=torch.int32, device=dev)
-    erased = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
+        counters = _uninit((T, NCOUNTERS), dtype=torch.int32, device=dev)
+    erased = _uninit((T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
     head = (C.byref(p), T, d_adj.data_ptr())
     tail = (counters.data_ptr(), erased.data_ptr() if erased is not None else None)
     if use_ring and classical:
@@ -591,8 +605,8 @@ def peel_sweep(p, d_adj, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=N
     assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
     assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous()
     dev = d_adj.device
-    out = torch.empty((T, 8), dtype=torch.int32, device=dev)
-    lost = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_lost else None
+    out = _uninit((T, 8), dtype=torch.int32, device=dev)
+    lost = _uninit((T, p.nw), dtype=torch.int32, device=dev) if want_lost else None
     fn = lib().scldpc_peel_sweep_device_adj16 if _is_adj16(d_adj) else lib().scldpc_peel_sweep_device
     ws, wsb, _keep = _workspace(WS_PEEL_SWEEP, p, T, dev, 1 if _is_adj16(d_adj) else 0)
     check(fn(C.byref(p), T, d_adj.data_ptr(), d_chan.data_ptr(), int(total_size), int(sweep_start), int(lost_lo),
@@ -615,8 +629,8 @@ def _peel_sweep_tables(entry, p, d_adj16, d_cn_sock, d_chan, total_size, sweep_s
     assert d_cn_sock.is_cuda and d_cn_sock.dtype == torch.int16 and d_cn_sock.is_contiguous() and tuple(d_cn_sock.shape) == (T, p.nk, p.dc)
     assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous() and tuple(d_chan.shape) == (T, p.nw)
     dev = d_adj16.device
-    out = torch.empty((T, 8), dtype=torch.int32, device=dev)
-    lost = torch.empty((T, p.nw), dtype=torch.int32, device=dev) if want_lost else None
+    out = _uninit((T, 8), dtype=torch.int32, device=dev)
+    lost = _uninit((T, p.nw), dtype=torch.int32, device=dev) if want_lost else None
     check(getattr(lib(), entry)(C.byref(p), T, d_adj16.data_ptr(), d_cn_sock.data_ptr(), d_chan.data_ptr(),
                                  int(total_size), int(sweep_start), int(lost_lo),
                                  int(total_size if lost_hi is None else lost_hi), out.data_ptr(),
@@ -655,8 +669,8 @@ def peel_pick(p, d_adj, d_chan, total_size, num_steps, mt_state=None, seed=0, tr
     T = d_adj.shape[0]
     assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
     dev = d_adj.device
-    out = torch.empty((T, 4), dtype=torch.int32, device=dev)
-    r1 = torch.empty((T, num_steps + 1), dtype=torch.int32, device=dev) if want_r1 else None
+    out = _uninit((T, 4), dtype=torch.int32, device=dev)
+    r1 = _uninit((T, num_steps + 1), dtype=torch.int32, device=dev) if want_r1 else None
     if mt_state is not None:
         assert mt_state.is_cuda and mt_state.dtype == torch.int32 and tuple(mt_state.shape) == (T, 625)
     fn = lib().scldpc_peel_pick_device_adj16 if _is_adj16(d_adj) else lib().scldpc_peel_pick_device
@@ -684,12 +698,12 @@ def peel_pick_deg(p, d_adj16, d_chan, total_size, num_steps, seed=0, trial0=0, w
     assert d_adj16.is_cuda and d_adj16.dtype == torch.int16 and d_adj16.is_contiguous() and tuple(d_adj16.shape[1:]) == (p.n, p.dv)
     assert d_chan.is_cuda and d_chan.dtype == torch.int32 and d_chan.is_contiguous() and tuple(d_chan.shape) == (T, p.nw)
     dev = d_adj16.device
-    out = torch.empty((T, 4), dtype=torch.int32, device=dev)
-    r1 = torch.empty((T, num_steps + 1), dtype=torch.int32, device=dev) if want_r1 else None
+    out = _uninit((T, 4), dtype=torch.int32, device=dev)
+    r1 = _uninit((T, num_steps + 1), dtype=torch.int32, device=dev) if want_r1 else None
     nbytes = lib().scldpc_peel_pick_deg_workspace_bytes(C.byref(p), T, int(total_size))
     if nbytes < 0:
         check(int(nbytes))
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    ws = _uninit(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
     check(lib().scldpc_peel_pick_device_adj16_deg(C.byref(p), T, d_adj16.data_ptr(), d_chan.data_ptr(), int(total_size),
                                                   int(num_steps), int(seed), int(trial0),
                                                   r1.data_ptr() if r1 is not None else None, out.data_ptr(), ws.data_ptr(),
@@ -735,7 +749,7 @@ class Streams:
 
     def run(self, npos, trace=False):
         """Decode npos further positions on every stream; returns (counters int64 [n,10], trace int32 [n,npos,10] | None)."""
-        tr = torch.empty((self.n, npos, 10), dtype=torch.int32, device=self.state.device) if trace else None
+        tr = _uninit((self.n, npos, 10), dtype=torch.int32, device=self.state.device) if trace else None
         darr, dptr = _lib.doped_array(self.doped)
         check(lib().scldpc_stream_run_device(C.byref(self.p), self.n, int(self.seed), int(self.stream0), float(self.eps),
                                              int(self.W), darr.size, dptr, int(npos), self.state.data_ptr(),
@@ -801,7 +815,7 @@ class GlibcStreamRun:
         d_inter = torch.zeros((1, ng + dv - 1, self.S), dtype=torch.int16, device=self.device)
         d_inter[0, (0 if first else dv - 1):] = torch.from_numpy(inter.view(np.int16)).to(self.device)
         d_chan = torch.from_numpy(np.ascontiguousarray(chan).view(np.int32)).to(self.device).reshape(1, ng, self.wpp)
-        tr = torch.empty((1, npos, 10), dtype=torch.int32, device=self.device)
+        tr = _uninit((1, npos, 10), dtype=torch.int32, device=self.device)
         darr, dptr = _lib.doped_array(self.doped)
         check(lib().scldpc_stream_run_device_inputs_at(C.byref(p), 1, self.W, darr.size, dptr, int(npos),
                                                        self.st.state.data_ptr(), self.st.counters.data_ptr(), tr.data_ptr(),
@@ -840,7 +854,7 @@ class InputStreams(Streams):
         self.done = 0
 
     def run(self, npos, trace=False):
-        tr = torch.empty((self.n, npos, 10), dtype=torch.int32, device=self.state.device) if trace else None
+        tr = _uninit((self.n, npos, 10), dtype=torch.int32, device=self.state.device) if trace else None
         darr, dptr = _lib.doped_array(self.doped)
         check(lib().scldpc_stream_run_device_inputs(C.byref(self.p), self.n, int(self.W), darr.size, dptr, int(npos),
                                                     self.state.data_ptr(), self.counters.data_ptr(),

@@ -22,6 +22,17 @@
  * workspace_bytes) with at least scldpc_workspace_bytes(op, ...) bytes, 256-byte aligned, not shared with a call that
  * may run at the same time.  The query returns 0 when the ensemble needs none (NULL / 0 may then be passed).
  *
+ * Buffers: an OUTPUT (d_counters, d_out, d_rows, d_r1, d_erased_bits, d_lost_bits, d_trace, the tables and channel a sampler
+ * writes) needs no initialisation: a call writes every element listed here as defined, whatever the buffer held, and nothing
+ * outside [ntrials] trials.  Defined are: every element of d_counters, d_out (slots without a meaning are 0), d_trace and a
+ * sampler's outputs; every word of d_erased_bits / d_lost_bits, the padding bits of the last word (bits n .. 32 nw - 1) being 0;
+ * d_r1[t][0 .. num_steps]; d_rows[t][0 .. min(d_counters[t][SCLDPC_C_ITERATIONS], rows_cap) - 1] — rows beyond a trial's
+ * iteration count are NOT written and keep what the buffer held.  The buffers a call accumulates into or carries on are the
+ * caller's to initialise: d_run, d_moments (zero before the first call), d_state and the streaming d_counters (zero-filled
+ * before a stream's first call), d_mt_state (a generator state) and the channel scldpc_clear_channel_range_device edits.  A
+ * WORKSPACE needs no initialisation and is not preserved: a call relies on nothing in it and leaves it undefined.  INPUTS
+ * (const pointers) are never written; padding bits of a channel's last word are ignored, whatever they hold.
+ *
  * Data layout (one "trial" = one sampled code + one channel realisation = one reference "frame"):
  *   vn_adj   int32 [ntrials][n][dv]       CN index of edge i of VN j   (VNdegree[j][1+i], BPF:87)
  *   chan     uint32[ntrials][nw]          bit (j&31) of word j>>5 = LLRsChannel[j] (1 = erased, BPF:91);
