@@ -195,7 +195,7 @@ SAMPLER2_DEG_BY_DEFAULT = False
 SAMPLER2_WIDE_BY_DEFAULT = False
 
 
-# The path of a Simulator, decided once in Simulator._select:
+# The path of a Simulator, decided once in select_path:
 #   adj_dtype    VN -> CN table: torch.int16 (position-local ids) or torch.int32 (the reference's VNdegree)
 #   sampler      what fills a batch: "glibc" (host replay), "first" (first-generation sampler), "first_sock" (the same with the
 #                CN -> socket table from its own launch), "cn16" / "sock16" (second generation, with the CN -> VN / CN -> socket
@@ -203,7 +203,7 @@ SAMPLER2_WIDE_BY_DEFAULT = False
 #                (second generation beyond 8192 sockets per position, with the CN -> socket table)
 #   cn_table     the CN table kept next to the VN -> CN one: None, "vn" or "sock"
 #   cn_pass      that table comes from the cn_sockets pass (the sampler does not emit it)
-#   decoder      "sw_ring" / "sw_chain" (E.sw_bp; "sw_ring" with cn_pass: the _deg entry points, pairs (3,6) and (5,10)),
+#   decoder      "sw_ring" / "sw_chain" (E.sw_bp; "sw_ring" of the pairs (3,6) and (5,10): the _deg entry points),
 #                "swc_ring" / "swc_chain" (E.sw_bp(classical=True): the classical window of decoder="swc"), or the full-BP call
 #                that walks the iterations: "level16", "wide", "full_bp",
 #                "deg16" / "degwide" (the 4-bit level decoder of the pairs (3,6) and (5,10), 16- / 32-bit queue entries)
@@ -216,6 +216,254 @@ def _cn16_table(p):
     """The CN table from which the 16-bit forms of the 4-bit decoder take this ensemble with device sampling: "vn", "sock"
     (n >= 65535) or None (they do not)."""
     return "vn" if E.cn16_supported(p) else "sock" if E.full_bp_sock16_supported(p) else None
+
+
+# What select_path decides from.  Config: the ensemble's numbers, the run's arguments (caps: whether caps are given) and the
+# seven switches as booleans, None resolved against the *_BY_DEFAULT (ring: the one of the decoder's ring); wide_off / deg_off:
+# the switch was given as False, which vetoes its family's caps form where None does not.  Capabilities: what the library's
+# *_supported rules answer for this ensemble and window (cn16_table: _cn16_table).
+Config = collections.namedtuple(
+    "Config", "dv dc L vns_pos cns_pos W decoder rng schedule max_it rows_cap caps num_doped "
+              "wide deg ring fused_caps sampled_table sampler2 sampler2_wide wide_off deg_off")
+Capabilities = collections.namedtuple(
+    "Capabilities", "cn16_table full_bp_wide full_bp_deg full_bp_deg_wide sw_ring sw_ring_deg swc_ring "
+                    "sock16 deg_sock16 wide_sock16 first_sock")
+# select_path's answer: the path, why each sampler switch left it alone (None: it did not), the ValueError of caps or None
+Selection = collections.namedtuple("Selection", "path sampler2_deg_reason sampler2_wide_reason sampled_table_reason caps_error")
+CAPS_ERROR = ("caps: the fused decode takes Philox sampling, no doping and an ensemble of the level-synchronous 4-bit decoder "
+              "(caps_sequential_reason)")
+
+
+def _config(p, W=0, decoder="full", rng="philox", schedule="flooding", max_it=0, rows_cap=0, caps=False, num_doped=0,
+            wide=None, deg=None, ring=None, fused_caps=None, sampled_table=None, sampler2=None, sampler2_wide=None):
+    """The Config of a Simulator's arguments; the *_BY_DEFAULT are read here, at call time."""
+    def on(want, default):
+        return default if want is None else bool(want)
+    return Config(p.dv, p.dc, p.L, p.vns_pos, p.cns_pos, W, decoder, rng, schedule, max_it, rows_cap, bool(caps), num_doped,
+                  on(wide, WIDE_BY_DEFAULT), on(deg, DEG_BY_DEFAULT),
+                  on(ring, CLASSICAL_RING_BY_DEFAULT if decoder == "swc" else RING_DEG_BY_DEFAULT),
+                  on(fused_caps, CAPS_FORMS_BY_DEFAULT), on(sampled_table, SAMPLED_TABLE_BY_DEFAULT),
+                  on(sampler2, SAMPLER2_DEG_BY_DEFAULT), on(sampler2_wide, SAMPLER2_WIDE_BY_DEFAULT), wide is False, deg is False)
+
+
+def _capabilities(p, W=0):
+    """The Capabilities of ensemble p and window W: the one place that asks the library (host functions, no device)."""
+    return Capabilities(_cn16_table(p), E.full_bp_wide_supported(p), E.full_bp_deg_supported(p),
+                        E.full_bp_deg_supported(p, wide=True), E.sw_ring_supported(p, W), E.sw_ring_deg_supported(p, W),
+                        E.swc_ring_supported(p, W), E.sock16_supported(p), E.deg_sock16_supported(p), E.wide_sock16_supported(p),
+                        E.sample_philox_sock_supported(p))
+
+
+# -- the rules: pure functions of a Config c and the Capabilities k, each the one statement of its limit and of its text --------
+def _ring_rule(c, k):
+    """ring_deg_reason (c.decoder "sw": the ring of the pairs (3,6) and (5,10)) and classical_ring_reason ("swc")."""
+    classical = c.decoder == "swc"
+    if not classical and (c.dv, c.dc) == (4, 8):
+        return "dv = 4, dc = 8 has a ring path of its own, chosen without this switch"
+    if not c.ring:
+        return "switched off"
+    if c.rng != "philox":
+        return "--rng %s samples the 4-byte VN -> CN table on the host: the ring kernel reads the 2-byte tables" % c.rng
+    if c.cns_pos > 65536:
+        return "more than 65536 CNs per position: no 2-byte VN -> CN table"
+    if not (k.swc_ring if classical else k.sw_ring_deg):
+        return ("the %sring kernel takes the pairs (3,6), (4,8) and (5,10) with W >= 1, vns_pos * dv <= 65535, L + dv - 1 <= 65535 "
+                "and a window state that fits the LDS (dv = %d, dc = %d, L = %d, N = %d, W = %d)"
+                % ("classical " if classical else "", c.dv, c.dc, c.L, c.vns_pos, c.W))
+    return None
+
+
+def _caps_rule(c, k):
+    """(form, None): the one decode whose checkpoints give every cap's file — "level16", or beyond the (4,8) forms of at most
+    65536 CNs (the fused_caps switch) "wide" / "deg16" / "degwide" — or (None, why the caps run one after another).  A caps
+    form takes exactly the shapes of its family's level form, so the library's *_supported rules decide."""
+    if c.rng != "philox":
+        return None, "--rng %s: each cap's run replays srandom(seed) from the start and stops drawing at its own frame" % c.rng
+    if c.num_doped > 0:
+        return None, "NUM_DOPED > 0: the first doped position is MAX_IT (BPF:2083-2091), so every cap is a different experiment"
+    if c.schedule != "flooding":
+        return None, "--schedule %s has no iteration caps" % c.schedule
+    if k.cn16_table is not None:
+        return "level16", None
+    if not c.fused_caps:
+        if k.full_bp_wide:
+            return None, "more than 65536 CNs per trial: the wide form of the level-synchronous 4-bit decoder has no cap checkpoints"
+        return None, "the level-synchronous 4-bit decoder takes dv = 4, dc = 8 and at most 65536 CNs per trial"
+    if (c.dv, c.dc) == (4, 8):
+        if c.wide_off:
+            return None, "--wide off: more than 65536 CNs per trial take the wide form of the level-synchronous 4-bit decoder"
+        if not k.full_bp_wide:
+            return None, ("the wide form of the level-synchronous 4-bit decoder takes a state that leaves 1024 queue entries per "
+                          "queue in one CU's LDS, and vns_pos * dv <= 65535 (L = %d, N = %d)" % (c.L, c.vns_pos))
+        return "wide", None
+    if (c.dv, c.dc) not in ((3, 6), (5, 10)):
+        return None, "the level-synchronous 4-bit decoder takes the pairs (3,6), (4,8) and (5,10) (dv = %d, dc = %d)" % (c.dv, c.dc)
+    if c.deg_off:
+        return None, "--deg off: dv = %d, dc = %d takes the _deg forms of the level-synchronous 4-bit decoder" % (c.dv, c.dc)
+    if c.cns_pos > 65536:
+        return None, "more than 65536 CNs per position: no 2-byte VN -> CN table"
+    if k.full_bp_deg:
+        return "deg16", None
+    if k.full_bp_deg_wide:
+        return "degwide", None
+    return None, ("the _deg forms of the level-synchronous 4-bit decoder take at most 65536 CNs per trial, or a state that leaves "
+                  "1024 queue entries per queue in one CU's LDS, and vns_pos * dv <= 65535 (dv = %d, dc = %d, L = %d, N = %d)"
+                  % (c.dv, c.dc, c.L, c.vns_pos))
+
+
+def _sampler2_deg_rule(c, k, path):
+    """sampler2_deg_reason on the records."""
+    if not c.sampler2:
+        return "switched off"
+    if c.rng != "philox":
+        return "--rng %s samples the code on the host" % c.rng
+    if (c.dv, c.dc) == (4, 8):
+        return "dv = 4, dc = 8 has a second-generation sampler of its own, chosen without this switch"
+    if (c.dv, c.dc) not in ((3, 6), (5, 10)):
+        return "the second-generation sampler takes the pairs (3,6), (4,8) and (5,10) (dv = %d, dc = %d)" % (c.dv, c.dc)
+    # what runs the cn_sockets pass after the first-generation sampler, or a ring decoder on a table of sockets
+    if not (path.sampler == "first" and path.adj_dtype == torch.int16
+            and (path.cn_pass or (path.decoder in ("sw_ring", "swc_ring") and path.cn_table == "sock"))):
+        return "the decoder of this configuration (%s) reads no CN -> socket table" % path.decoder
+    if not k.deg_sock16:
+        return ("the second-generation sampler of the pairs (3,6) and (5,10) takes at most 8192 sockets per position "
+                "(dv = %d, dc = %d, N = %d: %d sockets)" % (c.dv, c.dc, c.vns_pos, c.cns_pos * c.dc))
+    return None
+
+
+def _sampler2_wide_rule(c, k, path):
+    """sampler2_wide_reason on the records."""
+    if not c.sampler2_wide:
+        return "switched off"
+    if c.rng != "philox":
+        return "--rng %s samples the code on the host" % c.rng
+    if path.sampler in ("cn16", "sock16", "deg_sock16"):
+        return ("the second-generation sampler of at most 8192 sockets per position takes this ensemble and writes the CN table "
+                "with the code already")
+    if not k.wide_sock16:
+        return ("the wide second-generation sampler takes the pairs (3,6), (4,8) and (5,10) with more than 8192 and at most 20480 "
+                "sockets per position (dv = %d, dc = %d, N = %d: %d sockets)" % (c.dv, c.dc, c.vns_pos, c.cns_pos * c.dc))
+    # what runs the cn_sockets pass after the first-generation sampler, a ring decoder on a table of sockets, and the (4,8) ring
+    # whose table E.sw_bp builds per call
+    if not (path.sampler == "first" and path.adj_dtype == torch.int16
+            and (path.cn_pass or (path.decoder in ("sw_ring", "swc_ring") and path.cn_table == "sock")
+                 or (path.decoder == "sw_ring" and path.cn_table is None))):
+        return "the decoder of this configuration (%s) reads no CN -> socket table" % path.decoder
+    return None
+
+
+def _sampled_table_rule(c, k, path):
+    """sampled_table_reason on the records."""
+    if not c.sampled_table:
+        return "switched off"
+    if c.rng != "philox":
+        return "--rng %s samples the code on the host" % c.rng
+    if path.sampler in ("cn16", "sock16", "deg_sock16", "wide_sock16"):
+        return "the second-generation sampler takes this ensemble and writes the CN table with the code already"
+    # what runs the cn_sockets pass after the first-generation sampler, and the (4,8) ring whose table E.sw_bp builds per call
+    if not (path.sampler == "first" and path.adj_dtype == torch.int16
+            and (path.cn_pass or (path.decoder == "sw_ring" and path.cn_table is None))):
+        return "the decoder of this configuration (%s) reads no CN -> socket table" % path.decoder
+    if not k.first_sock:
+        return ("the first-generation sampler writes the table for vns_pos * dv <= 65535, cns_pos <= 65536 and, beyond 8192 "
+                "sockets per position, dc <= 255 and cns_pos <= 32768 (dv = %d, dc = %d, L = %d, N = %d)"
+                % (c.dv, c.dc, c.L, c.vns_pos))
+    return None
+
+
+def select_path(c, k):
+    """The path of configuration c where the library answers k: a Selection.  A function of its two arguments — it asks no
+    library rule, reads no *_BY_DEFAULT and touches no device.  One rule per decoder family, asked in order, the first that
+    takes the configuration decides; then the three sampler switches, each judged on the path the one before it left."""
+    philox = c.rng == "philox"
+    first = "first" if philox else "glibc"
+    # compact 2-byte position-local ids for device-sampled codes; the reference's int32 VNdegree for host replays
+    adj = torch.int16 if (philox and c.cns_pos <= 65536) else torch.int32
+    full16 = c.decoder == "full" and adj == torch.int16
+    # the one place that knows an unlimited fixpoint run: no iteration cap to honour, no iteration statistics.  Without rows it
+    # takes a fixpoint kernel (decided per call in decode_batch: a call that wants rows walks the iterations); no_walk: no call
+    # of this run wants rows
+    unlimited_fix = c.schedule == "fixpoint" and (c.max_it <= 0 or c.max_it >= 1000000)
+    no_walk = unlimited_fix and c.rows_cap == 0
+
+    def on_sockets(decoder, fix=None, sampled=False):
+        # a decoder that reads the CN -> socket table: sampled with the code where the (4,8) second-generation sampler takes the
+        # ensemble (sampled=True), else the first-generation sampler writes the 2-byte VN -> CN table for every dv and the
+        # cn_sockets pass the table of sockets
+        if sampled and k.sock16:
+            return Path(adj, "sock16", "sock", False, decoder, fix)
+        return Path(adj, first, "sock", True, decoder, fix)
+
+    def no_table(decoder, fix=None):
+        return Path(adj, first, None, False, decoder, fix)
+
+    def sw():
+        # square windows: the ring kernel keeps the window's state in LDS and reads a CN -> socket table — sampled with the
+        # code, else built by E.sw_bp per call ((4,8)) or by the cn_sockets pass (the _deg entry points of the other pairs)
+        if c.decoder != "sw":
+            return None
+        ring = adj == torch.int16 and k.sw_ring
+        if ring and k.sock16:
+            return Path(adj, "sock16", "sock", False, "sw_ring", None)
+        if _ring_rule(c, k) is None:
+            return on_sockets("sw_ring")
+        return no_table("sw_ring" if ring else "sw_chain")
+
+    def swc():
+        # classical windows: the ring kernel of all three pairs; everything else keeps the whole-chain kernel
+        if c.decoder != "swc":
+            return None
+        return on_sockets("swc_ring", sampled=True) if _ring_rule(c, k) is None else no_table("swc_chain")
+
+    def level16():
+        # full BP on the BASELINE ensemble family: the second-generation pair (sampler_v2 + the 4-bits-per-CN decoder) on the
+        # CN -> VN table (n >= 65535: the CN -> socket table).  Unlimited, no iteration statistics: its fixpoint form; else the
+        # same decoder walked one flooding iteration per round — iteration caps, counts and rows
+        table = k.cn16_table if (philox and c.decoder == "full") else None
+        if table is None:
+            return None
+        sampler = "cn16" if table == "vn" else "sock16"
+        if no_walk:                                     # (a call that wants rows all the same gets full_bp's iterations)
+            return Path(adj, sampler, table, False, "full_bp", "fixpoint16")
+        return Path(adj, sampler, table, False, "level16", None)
+
+    def caps_forms():
+        # cap checkpoints beyond level16 (opt-in): the path a single-cap run of the family takes
+        form = _caps_rule(c, k)[0] if (c.caps and full16 and c.rows_cap == 0) else None
+        return on_sockets(form, sampled=form == "wide") if form is not None else None
+
+    def deg_forms():
+        # the 4-bit decoder of the pairs (3,6) and (5,10); doped positions come with the channel.  Unlimited, no rows: the narrow
+        # fixpoint form — there is no wide fixpoint kernel, so such a run of a wide shape keeps the first-generation path
+        if not (c.deg and (c.dv, c.dc) != (4, 8) and full16 and not c.caps):
+            return None
+        form = "deg16" if k.full_bp_deg else "degwide" if (k.full_bp_deg_wide and not no_walk) else None
+        fix = ("fixpoint_deg" if form == "deg16" else "fixpoint") if unlimited_fix else None
+        return on_sockets(form, fix) if form is not None else None
+
+    def wide():
+        # more than 65536 CNs per trial (bp_traj's default N = 5000; L = 100, N = 2000): the wide form of the level decoder.  An
+        # unlimited fixpoint run keeps full_bp_fixpoint (there is no wide fixpoint kernel)
+        if not (c.wide and full16 and not no_walk and not c.caps and k.full_bp_wide):
+            return None
+        return on_sockets("wide", "fixpoint" if unlimited_fix else None, sampled=True)
+
+    def first_generation():
+        return no_table("full_bp", "fixpoint" if unlimited_fix else None)
+
+    path = sw() or swc() or level16() or caps_forms() or deg_forms() or wide() or first_generation()
+    # code and CN -> socket table from one launch instead of the first-generation sampler and the cn_sockets pass (opt-in): the
+    # second-generation sampler of the pairs (3,6) and (5,10); behind it the wide one, whose shapes the first does not take;
+    # last the first-generation sampler's own table, which then finds no first-generation sampler where either took the path
+    reasons = []
+    for rule, sampler in ((_sampler2_deg_rule, "deg_sock16"), (_sampler2_wide_rule, "wide_sock16"),
+                          (_sampled_table_rule, "first_sock")):
+        reasons.append(rule(c, k, path))
+        if reasons[-1] is None:
+            path = path._replace(sampler=sampler, cn_table="sock", cn_pass=False)
+    # caps need a decode with checkpoints (the wide and _deg forms are reached with caps through caps_forms only)
+    fused = path.decoder in ("level16", "wide", "deg16", "degwide") and c.rows_cap == 0 and c.num_doped == 0
+    return Selection(path, *reasons, CAPS_ERROR if (c.caps and not fused) else None)
 
 
 class Simulator:
@@ -274,126 +522,26 @@ class Simulator:
     def _select(self):
         """Decides the path of this configuration, once (no device work): self.path, which _alloc, fill_batch, decode_batch,
         decode_batch_caps and kernel_choice read.  Returns the dtype of the VN -> CN table."""
-        p, philox = self.p, self.rng == "philox"
-        first = "first" if philox else "glibc"
-        # compact 2-byte position-local ids for device-sampled codes; the reference's int32 VNdegree for host replays
-        adj_dtype = torch.int16 if (philox and p.cns_pos <= 65536) else torch.int32
-        # the one place that knows an unlimited fixpoint run: no iteration cap to honour, no iteration statistics.  Without
-        # rows it takes a fixpoint kernel (decided per call in decode_batch: a call that wants rows walks the iterations)
-        unlimited_fix = self.schedule == "fixpoint" and (self.max_it <= 0 or self.max_it >= 1000000)
-        table = _cn16_table(p) if (philox and self.decoder == "full") else None
-        if self.decoder == "sw":
-            # square-window decoding with the window's state in LDS reads a CN -> socket table: sampled with the code where the
-            # second-generation sampler takes the ensemble (else E.sw_bp builds it in a pass of its own)
-            ring = adj_dtype == torch.int16 and E.sw_ring_supported(p, self.W)
-            if ring and E.sock16_supported(p):
-                self.path = Path(adj_dtype, "sock16", "sock", False, "sw_ring", None)
-            elif ring_deg_reason(p, self.W, self.rng, self.want_ring) is None:
-                # another degree pair the ring kernel has an instance for: the first-generation sampler writes the 2-byte VN -> CN
-                # table for every dv, the cn_sockets pass the CN -> socket table into the preallocated d_cn
-                self.path = Path(adj_dtype, first, "sock", True, "sw_ring", None)
-            else:
-                self.path = Path(adj_dtype, first, None, False, "sw_ring" if ring else "sw_chain", None)
-        elif self.decoder == "swc":
-            # classical window: the ring kernel reads the CN -> socket table, sampled with the code where the second-generation
-            # sampler takes the ensemble, else from the cn_sockets pass; everything else keeps the whole-chain kernel
-            if classical_ring_reason(p, self.W, self.rng, self.want_ring) is not None:
-                self.path = Path(adj_dtype, first, None, False, "swc_chain", None)
-            elif E.sock16_supported(p):
-                self.path = Path(adj_dtype, "sock16", "sock", False, "swc_ring", None)
-            else:
-                self.path = Path(adj_dtype, first, "sock", True, "swc_ring", None)
-        elif table is not None:
-            # full BP on the BASELINE ensemble family: the second-generation pair (sampler_v2 + the 4-bits-per-CN decoder) needs
-            # the CN -> VN table (n >= 65535: the CN -> socket table) next to the VN -> CN one.  Unlimited, no iteration
-            # statistics: its fixpoint form; else the same decoder walked one flooding iteration per round — iteration caps
-            # (the published ..._500it_... tables), counts and rows
-            sampler = "cn16" if table == "vn" else "sock16"
-            if unlimited_fix and self.rows_cap == 0:       # (a call that wants rows all the same gets full_bp's iterations)
-                self.path = Path(adj_dtype, sampler, table, False, "full_bp", "fixpoint16")
-            else:
-                self.path = Path(adj_dtype, sampler, table, False, "level16", None)
-        elif self._caps_form(adj_dtype) is not None:
-            # cap checkpoints beyond the (4,8) forms of at most 65536 CNs (opt-in): the path a single-cap run of the family takes —
-            # the wide form on the CN -> socket table, sampled with the code where the second-generation sampler takes the
-            # ensemble; for the other pairs the first-generation sampler and the cn_sockets pass
-            form = self._caps_form(adj_dtype)
-            if form == "wide":
-                sampled = E.sock16_supported(p)
-                self.path = Path(adj_dtype, "sock16" if sampled else first, "sock", not sampled, "wide", None)
-            else:
-                self.path = Path(adj_dtype, first, "sock", True, form, None)
-        elif self._deg_form(adj_dtype, unlimited_fix) is not None:
-            # another degree pair the 4-bit decoder has instances for: the first-generation sampler writes the 2-byte VN -> CN
-            # table for every dv, the cn_sockets pass the CN -> socket table; doped positions come with the channel.  Unlimited,
-            # no rows: the narrow fixpoint form (a wide shape keeps full_bp_fixpoint: _deg_form)
-            form = self._deg_form(adj_dtype, unlimited_fix)
-            fix = ("fixpoint_deg" if form == "deg16" else "fixpoint") if unlimited_fix else None
-            self.path = Path(adj_dtype, first, "sock", True, form, fix)
-        else:
-            # more than 65536 CNs per trial (bp_traj's default N = 5000; L = 100, N = 2000): the wide form of the level decoder,
-            # on the CN -> socket table — from the second-generation sampler where it takes the ensemble, else from the
-            # cn_sockets pass.  An unlimited fixpoint run keeps full_bp_fixpoint (there is no wide fixpoint kernel).
-            use = WIDE_BY_DEFAULT if self.want_wide is None else bool(self.want_wide)
-            fix = "fixpoint" if unlimited_fix else None
-            if (use and philox and self.decoder == "full" and adj_dtype == torch.int16 and not (unlimited_fix and self.rows_cap == 0)
-                    and self.caps is None and E.full_bp_wide_supported(p)):
-                sampled = E.sock16_supported(p)
-                self.path = Path(adj_dtype, "sock16" if sampled else first, "sock", not sampled, "wide", fix)
-            else:
-                self.path = Path(adj_dtype, first, None, False, "full_bp", fix)
-        path = self.path
-        self.ring_deg = path.decoder == "sw_ring" and path.cn_pass       # (the _deg entry points: decided where the table's pass is)
-        # the pairs (3,6) and (5,10): code and CN -> socket table from their second-generation sampler instead of the
-        # first-generation sampler and the cn_sockets pass (opt-in; decided before the next switch, which then finds no
-        # first-generation sampler to take the table from)
-        self.sampler2_deg_reason = sampler2_deg_reason(p, self.rng, path, self.want_sampler2)
-        if self.sampler2_deg_reason is None:
-            path = self.path = path._replace(sampler="deg_sock16", cn_table="sock", cn_pass=False)
-        # beyond 8192 sockets per position: code and CN -> socket table from the wide second-generation sampler (opt-in; decided
-        # behind sampler2, whose shapes it does not take, and before the next switch, as sampler2 is)
-        self.sampler2_wide_reason = sampler2_wide_reason(p, self.rng, path, self.want_sampler2_wide)
-        if self.sampler2_wide_reason is None:
-            path = self.path = path._replace(sampler="wide_sock16", cn_table="sock", cn_pass=False)
-        # the table of a path that runs the cn_sockets pass after the first-generation sampler, or leaves it to E.sw_bp, from the
-        # sampler's own launch instead (opt-in)
-        self.sampled_table_reason = sampled_table_reason(p, self.rng, path, self.want_sampled_table)
-        if self.sampled_table_reason is None:
-            path = self.path = path._replace(sampler="first_sock", cn_table="sock", cn_pass=False)
-        # the path as the flags it used to be kept in
-        self.gen2, self.lvl2, self.wide = path.fix_decoder == "fixpoint16", path.decoder == "level16", path.decoder == "wide"
-        self.sock = (self.gen2 or self.lvl2) and path.cn_table == "sock"
-        self.ring2 = path.decoder == "sw_ring" and path.cn_table == "sock"
-        self.wide_sock = self.wide and not path.cn_pass
-        self.deg = path.decoder in ("deg16", "degwide")
-        fused_form = self.caps is not None and path.decoder in ("wide", "deg16", "degwide")      # reached through _caps_form only
-        if self.caps is not None and not ((self.lvl2 or fused_form) and self.rows_cap == 0 and not self.doped):
-            raise ValueError("caps: the fused decode takes Philox sampling, no doping and an ensemble of the "
-                             "level-synchronous 4-bit decoder (caps_sequential_reason)")
-        return adj_dtype
+        config = _config(self.p, self.W, self.decoder, self.rng, self.schedule, self.max_it, self.rows_cap, self.caps is not None,
+                         len(self.doped), self.want_wide, self.want_deg, self.want_ring, self.want_fused_caps,
+                         self.want_sampled_table, self.want_sampler2, self.want_sampler2_wide)
+        self.path, self.sampler2_deg_reason, self.sampler2_wide_reason, self.sampled_table_reason, caps_error = \
+            select_path(config, _capabilities(self.p, self.W))
+        if caps_error is not None:
+            raise ValueError(caps_error)
+        return self.path.adj_dtype
 
-    def _caps_form(self, adj_dtype):
-        """"wide" / "deg16" / "degwide" where this configuration takes the cap checkpoints of those forms, else None."""
-        if self.caps is None or self.decoder != "full" or adj_dtype != torch.int16 or self.rows_cap != 0:
-            return None
-        if caps_sequential_reason(self.p, self.rng, len(self.doped), self.schedule, self.want_fused_caps, self.want_wide,
-                                  self.want_deg) is not None:
-            return None
-        return _caps_form(self.p, self.want_wide, self.want_deg)[0]
-
-    def _deg_form(self, adj_dtype, unlimited_fix):
-        """"deg16" / "degwide" where the _deg forms of the 4-bit decoder apply to this configuration, else None."""
-        p = self.p
-        use = DEG_BY_DEFAULT if self.want_deg is None else bool(self.want_deg)
-        if not (use and (p.dv, p.dc) != (4, 8) and self.rng == "philox" and self.decoder == "full" and adj_dtype == torch.int16
-                and self.caps is None):
-            return None
-        if E.full_bp_deg_supported(p):
-            return "deg16"
-        # no wide fixpoint kernel: an unlimited fixpoint run without rows keeps the first-generation path, as on the wide path
-        if not (unlimited_fix and self.rows_cap == 0) and E.full_bp_deg_supported(p, wide=True):
-            return "degwide"
-        return None
+    # the path as the flags it used to be kept in
+    gen2 = property(lambda self: self.path.fix_decoder == "fixpoint16")
+    lvl2 = property(lambda self: self.path.decoder == "level16")
+    wide = property(lambda self: self.path.decoder == "wide")
+    sock = property(lambda self: (self.gen2 or self.lvl2) and self.path.cn_table == "sock")
+    ring2 = property(lambda self: self.path.decoder == "sw_ring" and self.path.cn_table == "sock")
+    wide_sock = property(lambda self: self.wide and not self.path.cn_pass)
+    deg = property(lambda self: self.path.decoder in ("deg16", "degwide"))
+    # the _deg entry points of the ring window decoder: every ring of another pair than (4,8), whose own ring E.sw_ring_supported
+    # keeps to itself (the cn_sockets pass that marks them in select_path is gone where a sampler switch took the table)
+    ring_deg = property(lambda self: self.path.decoder == "sw_ring" and (self.p.dv, self.p.dc) != (4, 8))
 
     def _alloc(self):
         p, batch = self.p, self.batch
@@ -410,59 +558,47 @@ class Simulator:
 
     def kernel_choice(self):
         """Which device kernels this configuration runs."""
-        path = self.path
-        samp2 = "sampler_v2 (dv = %d, dc = %d, CN->socket table)" % (self.p.dv, self.p.dc)
-        samp2w = "sampler_v2 wide (dv = %d, dc = %d, CN->socket table)" % (self.p.dv, self.p.dc)
-        if path.decoder == "sw_ring" and path.sampler == "deg_sock16":
-            return samp2 + " + sw_ring (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc)
-        if path.decoder == "sw_ring" and path.sampler == "wide_sock16":
-            return samp2w + (" + sw_ring (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc) if self.ring_deg else
-                             " + sw_ring (window state in LDS)")
-        if path.decoder == "sw_ring" and path.sampler == "first_sock":
-            return ("sampler (first generation, CN->socket table) + sw_ring (window state in LDS"
-                    + (", dv = %d, dc = %d)" % (self.p.dv, self.p.dc) if self.ring_deg else ")"))
-        if path.decoder == "sw_ring" and path.cn_pass:
-            return ("sampler (first generation) + cn_sockets pass + sw_ring (window state in LDS, dv = %d, dc = %d)"
-                    % (self.p.dv, self.p.dc))
+        return self._sampler_label() + " + " + self._decoder_label()
+
+    def _sampler_label(self):
+        path, pair = self.path, "dv = %d, dc = %d" % (self.p.dv, self.p.dc)
+        sampler = path.sampler
+        if path.decoder in ("sw_ring", "sw_chain"):
+            # decoder="sw" names the host replay and the (4,8) second-generation sampler as it always has (pinned)
+            sampler = {"glibc": "first", "sock16": "sock16 under sw"}.get(sampler, sampler)
+        label = {"glibc": "glibc replay on the host", "first": "sampler (first generation)",
+                 "first_sock": "sampler (first generation, CN->socket table)", "cn16": "sampler_v3 (CN->VN table)",
+                 "sock16": "sampler_v3 (CN->socket table)", "sock16 under sw": "sampler_v2 (CN->socket table)",
+                 "deg_sock16": "sampler_v2 (%s, CN->socket table)" % pair,
+                 "wide_sock16": "sampler_v2 wide (%s, CN->socket table)" % pair}[sampler]
+        return label + (" + cn_sockets pass" if path.cn_pass else "")
+
+    def _decoder_label(self):
+        path, pair = self.path, "dv = %d, dc = %d" % (self.p.dv, self.p.dc)
+        if path.decoder == "sw_ring" and path.cn_table is None:
+            return "sw_ring + cn_sockets pass"                          # (the (4,8) ring whose table E.sw_bp builds; pinned)
         if path.decoder == "sw_ring":
-            return ("sampler_v2 (CN->socket table) + sw_ring (window state in LDS)" if path.cn_table is not None else
-                    "sampler (first generation) + sw_ring + cn_sockets pass")
+            return "sw_ring (window state in LDS" + (", " + pair if self.ring_deg else "") + ")"
         if path.decoder == "sw_chain":
-            return "sampler (first generation) + sw_bp (whole chain)"
-        samp = {"glibc": "glibc replay on the host", "first": "sampler (first generation)",
-                "first_sock": "sampler (first generation, CN->socket table)", "cn16": "sampler_v3 (CN->VN table)",
-                "sock16": "sampler_v3 (CN->socket table)", "deg_sock16": samp2,
-                "wide_sock16": samp2w}[path.sampler] + (" + cn_sockets pass" if path.cn_pass else "")
+            return "sw_bp (whole chain)"
         if path.decoder == "swc_ring":
-            return samp + " + sw_ring classical window (window state in LDS, dv = %d, dc = %d)" % (self.p.dv, self.p.dc)
+            return "sw_ring classical window (window state in LDS, %s)" % pair
         if path.decoder == "swc_chain":
-            return samp + " + sw_bp classical window (whole chain)"
+            return "sw_bp classical window (whole chain)"
         rows = ", trajectory rows)" if self.rows_cap else ")"
-        if path.fix_decoder == "fixpoint16":
-            return samp + " + full_bp_small fixpoint (4-bit CN counts)"
-        if path.decoder == "level16" and self.caps is not None:
-            return samp + " + full_bp_small level-synchronous with %d cap checkpoints per decode (4-bit CN counts)" % len(self.caps)
-        if path.decoder == "level16":
-            return samp + " + full_bp_small level-synchronous (4-bit CN counts" + rows
-        if path.decoder == "wide" and self.caps is not None:
-            return samp + (" + full_bp_small wide level-synchronous with %d cap checkpoints per decode (4-bit CN counts, "
-                           "32-bit queue entries)" % len(self.caps))
-        if path.decoder == "wide":
-            return samp + " + full_bp_small wide level-synchronous (4-bit CN counts, 32-bit queue entries" + rows
-        if self.deg:
-            pair = "4-bit CN counts, dv = %d, dc = %d" % (self.p.dv, self.p.dc)
-            if self.caps is not None:
-                return samp + (" + full_bp_small %slevel-synchronous with %d cap checkpoints per decode (%s%s)"
-                               % ("wide " if path.decoder == "degwide" else "", len(self.caps), pair,
-                                  ", 32-bit queue entries" if path.decoder == "degwide" else ""))
-            if path.fix_decoder == "fixpoint_deg" and not self.rows_cap:
-                return samp + " + full_bp_small fixpoint (" + pair + ")"
-            if path.decoder == "degwide":
-                return samp + " + full_bp_small wide level-synchronous (" + pair + ", 32-bit queue entries" + rows
-            return samp + " + full_bp_small level-synchronous (" + pair + rows
-        return samp + " + full_bp (16-bit CN words" + rows + \
-            ": the 4-bit decoders take dv = 4, dc = 8 with device sampling and at most 65536 CNs per trial, or (the wide " \
-            "form, unless switched off) a state that leaves 1024 queue entries in one CU's LDS"
+        if path.decoder == "full_bp" and path.fix_decoder != "fixpoint16":
+            return ("full_bp (16-bit CN words" + rows + ": the 4-bit decoders take dv = 4, dc = 8 with device sampling and at most "
+                    "65536 CNs per trial, or (the wide form, unless switched off) a state that leaves 1024 queue entries in one "
+                    "CU's LDS")
+        # the 4-bit decoder: its fixpoint form (a run none of whose calls wants rows), its cap checkpoints, or one flooding
+        # iteration per round; the _deg forms name their pair, the wide forms their queue entries
+        counts = "4-bit CN counts" + (", " + pair if self.deg else "")
+        wide, q32 = ("wide ", ", 32-bit queue entries") if path.decoder in ("wide", "degwide") else ("", "")
+        if path.fix_decoder in ("fixpoint16", "fixpoint_deg") and not self.rows_cap:
+            return "full_bp_small fixpoint (%s)" % counts
+        if self.caps is not None:
+            return "full_bp_small %slevel-synchronous with %d cap checkpoints per decode (%s%s)" % (wide, len(self.caps), counts, q32)
+        return "full_bp_small %slevel-synchronous (%s%s%s" % (wide, counts, q32, rows)
 
     def _accumulate(self, allcnt, run, stop_frame_err):
         return E.accumulate_run(allcnt, run, stop_frame_err)
@@ -524,11 +660,8 @@ class Simulator:
                             out=(self.d_adj[:nb], self.d_ch[:nb]))
             if path.cn_pass:                       # more sockets per position than the second-generation sampler takes
                 E.cn_sockets(self.p, self.d_adj[:nb], out=self.d_cn[:nb])
-        elif path.sampler == "first_sock":
-            E.sample_philox_sock(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
-                                 out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
-        else:
-            sample = {"cn16": E.sample_philox_cn16, "sock16": E.sample_philox_sock16,
+        else:                                          # the samplers that write the CN table with the code
+            sample = {"first_sock": E.sample_philox_sock, "cn16": E.sample_philox_cn16, "sock16": E.sample_philox_sock16,
                       "deg_sock16": E.sample_philox_deg_sock16, "wide_sock16": E.sample_philox_wide_sock16}[path.sampler]
             sample(self.p, self.seed, trial_key(self.index, sim, frame0), nb, eps, self.doped,
                    out=(self.d_adj[:nb], self.d_cn[:nb], self.d_ch[:nb]))
@@ -658,146 +791,42 @@ def sampled_table_reason(p, rng, path, want=True):
     """Why a configuration whose path (before this switch) is `path` does not take the CN -> socket table from the
     first-generation sampler's own launch, or None where it does.  want: the Simulator's sampled_table argument (None:
     SAMPLED_TABLE_BY_DEFAULT)."""
-    if not (SAMPLED_TABLE_BY_DEFAULT if want is None else bool(want)):
-        return "switched off"
-    if rng != "philox":
-        return "--rng %s samples the code on the host" % rng
-    if path.sampler in ("cn16", "sock16", "deg_sock16", "wide_sock16"):
-        return "the second-generation sampler takes this ensemble and writes the CN table with the code already"
-    # what runs the cn_sockets pass after the first-generation sampler, and the (4,8) ring whose table E.sw_bp builds per call
-    if not (path.sampler == "first" and path.adj_dtype == torch.int16
-            and (path.cn_pass or (path.decoder == "sw_ring" and path.cn_table is None))):
-        return "the decoder of this configuration (%s) reads no CN -> socket table" % path.decoder
-    if not E.sample_philox_sock_supported(p):
-        return ("the first-generation sampler writes the table for vns_pos * dv <= 65535, cns_pos <= 65536 and, beyond 8192 "
-                "sockets per position, dc <= 255 and cns_pos <= 32768 (dv = %d, dc = %d, L = %d, N = %d)"
-                % (p.dv, p.dc, p.L, p.vns_pos))
-    return None
+    return _sampled_table_rule(_config(p, rng=rng, sampled_table=want), _capabilities(p), path)
 
 
 def sampler2_deg_reason(p, rng, path, want=True):
     """Why a configuration whose path (before this switch) is `path` does not take the second-generation sampler of the pairs
     (3,6) and (5,10), or None where it does.  want: the Simulator's sampler2 argument (None: SAMPLER2_DEG_BY_DEFAULT)."""
-    if not (SAMPLER2_DEG_BY_DEFAULT if want is None else bool(want)):
-        return "switched off"
-    if rng != "philox":
-        return "--rng %s samples the code on the host" % rng
-    if (p.dv, p.dc) == (4, 8):
-        return "dv = 4, dc = 8 has a second-generation sampler of its own, chosen without this switch"
-    if (p.dv, p.dc) not in ((3, 6), (5, 10)):
-        return "the second-generation sampler takes the pairs (3,6), (4,8) and (5,10) (dv = %d, dc = %d)" % (p.dv, p.dc)
-    # what runs the cn_sockets pass after the first-generation sampler, or a ring decoder on a table of sockets
-    if not (path.sampler == "first" and path.adj_dtype == torch.int16
-            and (path.cn_pass or (path.decoder in ("sw_ring", "swc_ring") and path.cn_table == "sock"))):
-        return "the decoder of this configuration (%s) reads no CN -> socket table" % path.decoder
-    if not E.deg_sock16_supported(p):
-        return ("the second-generation sampler of the pairs (3,6) and (5,10) takes at most 8192 sockets per position "
-                "(dv = %d, dc = %d, N = %d: %d sockets)" % (p.dv, p.dc, p.vns_pos, p.cns_pos * p.dc))
-    return None
+    return _sampler2_deg_rule(_config(p, rng=rng, sampler2=want), _capabilities(p), path)
 
 
 def sampler2_wide_reason(p, rng, path, want=True):
     """Why a configuration whose path (before this switch) is `path` does not take the wide second-generation sampler (more than
     8192 sockets per position), or None where it does.  want: the Simulator's sampler2_wide argument (None:
     SAMPLER2_WIDE_BY_DEFAULT)."""
-    if not (SAMPLER2_WIDE_BY_DEFAULT if want is None else bool(want)):
-        return "switched off"
-    if rng != "philox":
-        return "--rng %s samples the code on the host" % rng
-    if path.sampler in ("cn16", "sock16", "deg_sock16"):
-        return ("the second-generation sampler of at most 8192 sockets per position takes this ensemble and writes the CN table "
-                "with the code already")
-    if not E.wide_sock16_supported(p):
-        return ("the wide second-generation sampler takes the pairs (3,6), (4,8) and (5,10) with more than 8192 and at most 20480 "
-                "sockets per position (dv = %d, dc = %d, N = %d: %d sockets)" % (p.dv, p.dc, p.vns_pos, p.cns_pos * p.dc))
-    # what runs the cn_sockets pass after the first-generation sampler, a ring decoder on a table of sockets, and the (4,8) ring
-    # whose table E.sw_bp builds per call
-    if not (path.sampler == "first" and path.adj_dtype == torch.int16
-            and (path.cn_pass or (path.decoder in ("sw_ring", "swc_ring") and path.cn_table == "sock")
-                 or (path.decoder == "sw_ring" and path.cn_table is None))):
-        return "the decoder of this configuration (%s) reads no CN -> socket table" % path.decoder
-    return None
+    return _sampler2_wide_rule(_config(p, rng=rng, sampler2_wide=want), _capabilities(p), path)
 
 
 def ring_deg_reason(p, W, rng, want=True):
     """Why decoder="sw" does not take the ring window decoder of the pairs (3,6) and (5,10) — sampler (first generation) +
     cn_sockets pass + sw_ring through the _deg entry points — on this configuration, or None where it does.  want: the
     Simulator's ring argument (None: RING_DEG_BY_DEFAULT)."""
-    if (p.dv, p.dc) == (4, 8):
-        return "dv = 4, dc = 8 has a ring path of its own, chosen without this switch"
-    if not (RING_DEG_BY_DEFAULT if want is None else bool(want)):
-        return "switched off"
-    if rng != "philox":
-        return "--rng %s samples the 4-byte VN -> CN table on the host: the ring kernel reads the 2-byte tables" % rng
-    if p.cns_pos > 65536:
-        return "more than 65536 CNs per position: no 2-byte VN -> CN table"
-    if not E.sw_ring_deg_supported(p, W):
-        return ("the ring kernel takes the pairs (3,6), (4,8) and (5,10) with W >= 1, vns_pos * dv <= 65535, L + dv - 1 <= 65535 "
-                "and a window state that fits the LDS (dv = %d, dc = %d, L = %d, N = %d, W = %d)" % (p.dv, p.dc, p.L, p.vns_pos, W))
-    return None
+    return _ring_rule(_config(p, W, "sw", rng, ring=want), _capabilities(p, W))
 
 
 def classical_ring_reason(p, W, rng, want=True):
     """Why decoder="swc" does not take the classical ring window decoder on this configuration, or None where it does.
     want: the Simulator's ring argument (None: CLASSICAL_RING_BY_DEFAULT)."""
-    if not (CLASSICAL_RING_BY_DEFAULT if want is None else bool(want)):
-        return "switched off"
-    if rng != "philox":
-        return "--rng %s samples the 4-byte VN -> CN table on the host: the ring kernel reads the 2-byte tables" % rng
-    if p.cns_pos > 65536:
-        return "more than 65536 CNs per position: no 2-byte VN -> CN table"
-    if not E.swc_ring_supported(p, W):
-        return ("the classical ring kernel takes the pairs (3,6), (4,8) and (5,10) with W >= 1, vns_pos * dv <= 65535, "
-                "L + dv - 1 <= 65535 and a window state that fits the LDS (dv = %d, dc = %d, L = %d, N = %d, W = %d)"
-                % (p.dv, p.dc, p.L, p.vns_pos, W))
-    return None
-
-
-def _caps_form(p, wide=None, deg=None):
-    """The cap-checkpoint form beyond the (4,8) forms of at most 65536 CNs that takes ensemble p — ("wide" | "deg16" |
-    "degwide", None) — or (None, the limit that keeps it off).  wide, deg: the Simulator's arguments; False vetoes the family.
-    A caps form takes exactly the shapes of its family's level form, so the library's *_supported rules decide."""
-    if (p.dv, p.dc) == (4, 8):
-        if wide is False:
-            return None, "--wide off: more than 65536 CNs per trial take the wide form of the level-synchronous 4-bit decoder"
-        if not E.full_bp_wide_supported(p):
-            return None, ("the wide form of the level-synchronous 4-bit decoder takes a state that leaves 1024 queue entries per "
-                          "queue in one CU's LDS, and vns_pos * dv <= 65535 (L = %d, N = %d)" % (p.L, p.vns_pos))
-        return "wide", None
-    if (p.dv, p.dc) not in ((3, 6), (5, 10)):
-        return None, "the level-synchronous 4-bit decoder takes the pairs (3,6), (4,8) and (5,10) (dv = %d, dc = %d)" % (p.dv, p.dc)
-    if deg is False:
-        return None, "--deg off: dv = %d, dc = %d takes the _deg forms of the level-synchronous 4-bit decoder" % (p.dv, p.dc)
-    if p.cns_pos > 65536:
-        return None, "more than 65536 CNs per position: no 2-byte VN -> CN table"
-    if E.full_bp_deg_supported(p):
-        return "deg16", None
-    if E.full_bp_deg_supported(p, wide=True):
-        return "degwide", None
-    return None, ("the _deg forms of the level-synchronous 4-bit decoder take at most 65536 CNs per trial, or a state that leaves "
-                  "1024 queue entries per queue in one CU's LDS, and vns_pos * dv <= 65535 (dv = %d, dc = %d, L = %d, N = %d)"
-                  % (p.dv, p.dc, p.L, p.vns_pos))
+    return _ring_rule(_config(p, W, "swc", rng, ring=want), _capabilities(p, W))
 
 
 def caps_sequential_reason(p, rng, num_doped, schedule, fused=None, wide=None, deg=None):
     """Why `bp_lim_iter --caps` runs its caps one after another instead of from one decode, or None.  The fused decode is
     used only where each cap's file is exactly the single-cap file and the level-synchronous 4-bit decoder takes the ensemble.
     fused, wide, deg: the Simulator's fused_caps, wide and deg (None: CAPS_FORMS_BY_DEFAULT; no veto) — with the fused path on,
-    the wide form and the pairs (3,6) and (5,10) fuse as well (_caps_form)."""
-    if rng != "philox":
-        return "--rng %s: each cap's run replays srandom(seed) from the start and stops drawing at its own frame" % rng
-    if num_doped > 0:
-        return "NUM_DOPED > 0: the first doped position is MAX_IT (BPF:2083-2091), so every cap is a different experiment"
-    if schedule != "flooding":
-        return "--schedule %s has no iteration caps" % schedule
-    if _cn16_table(p) is None:
-        if CAPS_FORMS_BY_DEFAULT if fused is None else bool(fused):
-            return _caps_form(p, wide, deg)[1]
-        if E.full_bp_wide_supported(p):
-            return ("more than 65536 CNs per trial: the wide form of the level-synchronous 4-bit decoder has no cap "
-                    "checkpoints")
-        return "the level-synchronous 4-bit decoder takes dv = 4, dc = 8 and at most 65536 CNs per trial"
-    return None
+    the wide form and the pairs (3,6) and (5,10) fuse as well (_caps_rule)."""
+    config = _config(p, rng=rng, schedule=schedule, caps=True, num_doped=num_doped, wide=wide, deg=deg, fused_caps=fused)
+    return _caps_rule(config, _capabilities(p))[1]
 
 
 def _caps_list(text):
@@ -819,8 +848,7 @@ def _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, sh
     writes — from one decode per batch with a checkpoint at every cap where that is exact, else one run per cap."""
     dist, rank, world = _dist()
     file_its = sorted(set(opts.caps) | {max_it})                  # the MAX_IT of each file
-    switch = {"auto": None, "on": True, "off": False}
-    fused, wide, deg = (switch[getattr(opts, name, "auto")] for name in ("caps_fused", "wide", "deg"))
+    fused, wide, deg = (_switch(opts, name) for name in ("caps_fused", "wide", "deg"))
     reason = caps_sequential_reason(p, opts.rng, num_doped, getattr(opts, "schedule", "flooding"), fused, wide, deg)
     verbose = rank == 0 and not opts.quiet
     if reason is not None and fused:
@@ -849,12 +877,9 @@ def _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, sh
     sim_obj = Simulator(p, decoder="full", W=W, max_it=caps[-1], is_term=True, doped=doped, batch=opts.batch, rng=opts.rng,
                         seed=opts.seed, schedule="flooding", shard_frames=shard == "frames",
                         device=getattr(opts, "device", None), index=index, verbose=verbose, caps=caps, wide=wide, deg=deg,
-                        fused_caps=fused, sampled_table=switch[getattr(opts, "sampled_table", "auto")],
-                        sampler2=switch[getattr(opts, "sampler2", "auto")],
-                        sampler2_wide=switch[getattr(opts, "sampler2_wide", "auto")])
-    _check_sampler2(opts, sim_obj)
-    _check_sampler2_wide(opts, sim_obj)
-    _check_sampled_table(opts, sim_obj)
+                        fused_caps=fused, sampled_table=_switch(opts, "sampled_table"), sampler2=_switch(opts, "sampler2"),
+                        sampler2_wide=_switch(opts, "sampler2_wide"))
+    _check_sampler_switches(opts, sim_obj)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     paths = {v: os.path.join(outdir, result_filename(prog, p, W, v, 0, index)) for v in file_its}
@@ -968,7 +993,7 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
         init_it = extra if extra else max_it                       # BPW:2101-2102
     elif prog == "bp_traj":
         is_term = bool(extra)
-    ring = {"auto": None, "on": True, "off": False}[getattr(opts, "ring", "auto")]
+    ring = _switch(opts, "ring")
     if prog == "bp_lim_iter":
         _check_window(opts)
         if getattr(opts, "window", "off") == "classical":
@@ -1005,15 +1030,10 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                         rows_cap=opts.rows_cap if prog == "bp_traj" else 0, schedule=getattr(opts, "schedule", "flooding"),
                         shard_frames=shard == "frames", device=getattr(opts, "device", None), index=replica,
                         verbose=rank == 0 and not opts.quiet,
-                        wide={"auto": None, "on": True, "off": False}[getattr(opts, "wide", "auto")],
-                        deg={"auto": None, "on": True, "off": False}[getattr(opts, "deg", "auto")],
-                        ring=ring if decoder in ("sw", "swc") else None,
-                        sampled_table={"auto": None, "on": True, "off": False}[getattr(opts, "sampled_table", "auto")],
-                        sampler2={"auto": None, "on": True, "off": False}[getattr(opts, "sampler2", "auto")],
-                        sampler2_wide={"auto": None, "on": True, "off": False}[getattr(opts, "sampler2_wide", "auto")])
-    _check_sampler2(opts, sim_obj)
-    _check_sampler2_wide(opts, sim_obj)
-    _check_sampled_table(opts, sim_obj)
+                        wide=_switch(opts, "wide"), deg=_switch(opts, "deg"), ring=ring if decoder in ("sw", "swc") else None,
+                        sampled_table=_switch(opts, "sampled_table"), sampler2=_switch(opts, "sampler2"),
+                        sampler2_wide=_switch(opts, "sampler2_wide"))
+    _check_sampler_switches(opts, sim_obj)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     t0 = time.time()
@@ -1084,22 +1104,18 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
     return 0
 
 
-def _check_sampled_table(opts, sim_obj):
-    """--sampled-table on where the sampler cannot write the table: exits with the reason."""
-    if getattr(opts, "sampled_table", "auto") == "on" and sim_obj.sampled_table_reason is not None:
-        raise SystemExit("--sampled-table on: " + sim_obj.sampled_table_reason)
+def _switch(opts, name):
+    """An `--x on|off|auto` option as the Simulator's argument: True, False or None (auto, or a program without the option)."""
+    return {"auto": None, "on": True, "off": False}[getattr(opts, name, "auto")]
 
 
-def _check_sampler2(opts, sim_obj):
-    """--sampler2 on where the second-generation sampler of the pairs (3,6) and (5,10) does not apply: exits with the reason."""
-    if getattr(opts, "sampler2", "auto") == "on" and sim_obj.sampler2_deg_reason is not None:
-        raise SystemExit("--sampler2 on: " + sim_obj.sampler2_deg_reason)
-
-
-def _check_sampler2_wide(opts, sim_obj):
-    """--sampler2-wide on where the wide second-generation sampler does not apply: exits with the reason."""
-    if getattr(opts, "sampler2_wide", "auto") == "on" and sim_obj.sampler2_wide_reason is not None:
-        raise SystemExit("--sampler2-wide on: " + sim_obj.sampler2_wide_reason)
+def _check_sampler_switches(opts, sim_obj):
+    """--sampler2 on, --sampler2-wide on or --sampled-table on where the Simulator did not take that sampler: exits with the
+    reason (in the order in which the Simulator judges them)."""
+    for name, reason in (("sampler2", "sampler2_deg_reason"), ("sampler2_wide", "sampler2_wide_reason"),
+                         ("sampled_table", "sampled_table_reason")):
+        if getattr(opts, name, "auto") == "on" and getattr(sim_obj, reason) is not None:
+            raise SystemExit("--%s on: %s" % (name.replace("_", "-"), getattr(sim_obj, reason)))
 
 
 def _check_window(opts):

@@ -78,6 +78,13 @@ class FakeSimulator(B.Simulator):
         return run
 
 
+class SelectOnly(B.Simulator):
+    """The Simulator's choice of kernels without its device buffers: the selection tests read path, flags and kernel_choice()."""
+
+    def _alloc(self):
+        self.d_adj = torch.empty(0, dtype=self._select())
+
+
 class FakeStreams:
     """Stand-in for engine.Streams (streaming mode): cumulative per-stream counters as a pure function of the global
     stream id and the number of positions decoded so far."""

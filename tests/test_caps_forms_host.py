@@ -9,6 +9,7 @@ import re
 import pytest
 import torch
 
+from fakes import SelectOnly
 from test_caps_host import CapsFake
 
 from fl_scaling_sc_ldpc_amd import _lib
@@ -118,13 +119,6 @@ def test_buffers_are_checked_last(entry):
 
 
 # ---- the Simulator's choice ------------------------------------------------------------------------------------------------
-class SelectOnly(B.Simulator):
-    """The Simulator's choice of kernels without its device buffers (as tests/test_deg_host.py)."""
-
-    def _alloc(self):
-        self.d_adj = torch.empty(0, dtype=self._select())
-
-
 def _sim(dv, dc, L, N, **kw):
     return SelectOnly(E.make_params(dv, dc, L, N), device="cpu", **kw)
 

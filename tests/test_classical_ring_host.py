@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from conftest import ROOT
-from fakes import FakeSimulator
+from fakes import FakeSimulator, SelectOnly
 from fl_scaling_sc_ldpc_amd import _lib
 from fl_scaling_sc_ldpc_amd import bp_decoding as B
 from fl_scaling_sc_ldpc_amd import engine as E
@@ -126,13 +126,6 @@ def test_argument_checks_come_before_any_launch(dv, dc):
         assert rc == BAD_ARG and msg == ENTRY + ": null buffer or negative ntrials", (kw, msg)
     rc, msg = call(p, max_it=-1)
     assert rc == BAD_ARG and msg == ENTRY + ": need W >= 1, max_it >= 0"
-
-
-class SelectOnly(B.Simulator):
-    """The Simulator's choice of kernels without its device buffers (as tests/test_deg_host.py)."""
-
-    def _alloc(self):
-        self.d_adj = torch.empty(0, dtype=self._select())
 
 
 def _sim(dv, dc, L=50, N=1000, W=20, **kw):

@@ -11,6 +11,7 @@ import ctypes as C
 import pytest
 import torch
 
+from fakes import SelectOnly
 from fl_scaling_sc_ldpc_amd import _lib
 from fl_scaling_sc_ldpc_amd import bp_decoding as B
 from fl_scaling_sc_ldpc_amd import engine as E
@@ -144,13 +145,6 @@ def test_the_older_entry_points_still_refuse_other_degrees():
     assert L.scldpc_full_bp_device_sock16(C.byref(p), 0, None, None, None, 0, 1, None, None, None) == TOO_LARGE
     assert b"takes dv = 4, dc = 8" in L.scldpc_last_error()
     assert L.scldpc_full_bp_sock16_supported(C.byref(p)) == 0 and L.scldpc_full_bp_wide_supported(C.byref(p)) == 0
-
-
-class SelectOnly(B.Simulator):
-    """The Simulator's choice of kernels without its device buffers (as tests/test_wide_host.py)."""
-
-    def _alloc(self):
-        self.d_adj = torch.empty(0, dtype=self._select())
 
 
 def _sim(dv, dc, L, N, **kw):

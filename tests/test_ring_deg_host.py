@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+from fakes import SelectOnly
 from fl_scaling_sc_ldpc_amd import _lib
 from fl_scaling_sc_ldpc_amd import bp_decoding as B
 from fl_scaling_sc_ldpc_amd import engine as E
@@ -112,13 +113,6 @@ def test_the_older_entry_point_still_refuses_other_degrees(dv, dc):
     for ntrials in (1, 0):
         assert L.scldpc_sw_bp_ring_device(C.byref(p), ntrials, ONE, ONE, ONE, 10, 5, 0, ONE, None, None) == TOO_LARGE
         assert b"scldpc_sw_bp_ring_device: takes dv = 4, dc = 8" in L.scldpc_last_error()
-
-
-class SelectOnly(B.Simulator):
-    """The Simulator's choice of kernels without its device buffers (as tests/test_deg_host.py)."""
-
-    def _alloc(self):
-        self.d_adj = torch.empty(0, dtype=self._select())
 
 
 def _sim(dv, dc, L=50, N=1000, W=20, **kw):

@@ -9,8 +9,8 @@ import shutil
 import sys
 
 import pytest
-import torch
 
+from fakes import SelectOnly
 from fl_scaling_sc_ldpc_amd import _lib
 from fl_scaling_sc_ldpc_amd import bp_decoding as B
 from fl_scaling_sc_ldpc_amd import engine as E
@@ -95,13 +95,6 @@ def test_argument_checks_come_before_any_launch(shape):
 
 
 # ---- the Simulator's choice ------------------------------------------------------------------------------------------------
-class SelectOnly(B.Simulator):
-    """The Simulator's choice of kernels without its device buffers (as tests/test_select_table.py)."""
-
-    def _alloc(self):
-        self.d_adj = torch.empty(0, dtype=self._select())
-
-
 def _sim(dv, dc, L, N, **kw):
     return SelectOnly(E.make_params(dv, dc, L, N), device="cpu", **kw)
 

@@ -4,8 +4,8 @@ work, and the Simulator's choice of the path (no device buffers: _alloc replaced
 import ctypes as C
 
 import pytest
-import torch
 
+from fakes import SelectOnly
 from fl_scaling_sc_ldpc_amd import bp_decoding as B
 from fl_scaling_sc_ldpc_amd import engine as E
 
@@ -75,13 +75,6 @@ def test_wide_entry_points_refuse_on_the_host_before_any_launch():
     assert traj(ok, 1, a=None) == -1
     assert traj(ok, 1, rows=None) == -1 and b"d_rows" in L.scldpc_last_error()
     assert traj(ok, 1, rows_cap=0) == -1 and b"rows_cap" in L.scldpc_last_error()
-
-
-class SelectOnly(B.Simulator):
-    """The Simulator's choice of kernels without its device buffers."""
-
-    def _alloc(self):
-        self.d_adj = torch.empty(0, dtype=self._select())
 
 
 def _sim(L, N, **kw):
