@@ -61,6 +61,13 @@ EXPORTS = (
     "scldpc_peel_pick_deg_supported", "scldpc_peel_pick_deg_workspace_bytes", "scldpc_peel_pick_device_adj16_deg",
 )
 
+# every symbol the extension header include/scldpc_ensembles.h declares (the same shared object; tests/test_sweep_ens_host.py)
+EXPORTS_ENSEMBLES = (
+    "scldpc_sample_philox_ensemble_adj16_sock_supported", "scldpc_sample_philox_ensemble_device_adj16_sock",
+    "scldpc_peel_sweep_tb_supported", "scldpc_peel_sweep_tb_wide_supported",
+    "scldpc_peel_sweep_device_sock16_tb", "scldpc_peel_sweep_device_sock16_tb_wide",
+)
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -167,6 +174,12 @@ def lib():
     L.scldpc_peel_sweep_device_sock16.argtypes = [pp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.scldpc_peel_sweep_wide_supported.argtypes = [pp]
     L.scldpc_peel_sweep_device_sock16_wide.argtypes = L.scldpc_peel_sweep_device_sock16.argtypes
+    L.scldpc_sample_philox_ensemble_adj16_sock_supported.argtypes = [pp, i32]
+    L.scldpc_sample_philox_ensemble_device_adj16_sock.argtypes = [pp, i32, u64, u64, i32, dbl, i32, vp, vp, vp, vp, vp]
+    L.scldpc_peel_sweep_tb_supported.argtypes = [pp]
+    L.scldpc_peel_sweep_tb_wide_supported.argtypes = [pp]
+    L.scldpc_peel_sweep_device_sock16_tb.argtypes = L.scldpc_peel_sweep_device_sock16.argtypes
+    L.scldpc_peel_sweep_device_sock16_tb_wide.argtypes = L.scldpc_peel_sweep_device_sock16.argtypes
     L.scldpc_peel_pick_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, u64, u64, vp, vp, vp, vp, u64, vp]
     L.scldpc_peel_pick_device_adj16.argtypes = L.scldpc_peel_pick_device.argtypes
     L.scldpc_peel_pick_deg_supported.argtypes = [pp, i32]

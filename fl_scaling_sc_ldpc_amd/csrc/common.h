@@ -51,6 +51,11 @@ bool cn_build_launch(const scldpc_code_params *p, int ntrials, const uint16_t *d
 int cn_build_launch_deg(const scldpc_code_params *p, int ntrials, const uint16_t *d_vn_adj16, const uint32_t *d_chan_bits,
                         uint32_t *d_words, void *stream);
 
+// sw_ring.hip: the CN -> socket table [T][nk][dc] from 2-byte rows (scldpc_cn_sockets_device's launch; tail_biting: the rows of a
+// ring, scldpc_sample_philox_ensemble_device_adj16_sock).  The caller has checked the parameters and the buffers.
+int cn_sockets_launch(const char *who, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                      uint16_t *d_cn_sock16, bool tail_biting, void *stream);
+
 // full_bp_small.hip: which limit keeps this ensemble from the narrow socket-table forms of the 4-bit decoders' _deg entry
 // points (the pairs (3,6), (4,8), (5,10); 16-bit sockets; at most 65536 CNs per trial); nullptr: none.  peel_sweep_small.hip
 // takes the same shapes.

@@ -38,9 +38,18 @@
 // half_cap = wcap / 2 between which its levels alternate; it takes entries v, v + 16, ... (at most 32) into the first half, so
 // the phase needs half_cap >= 32 (the narrow form asks 64 of its four waves), which every supported shape has (qcap >= 1024).
 // What a half cannot take spills behind the first 512 entries of the queue being read, as in the narrow form.
+//
+// The TAIL-BITING form (TB; scldpc_peel_sweep_device_sock16_tb / _tb_wide, include/scldpc_ensembles.h) is the same kernel on a
+// chain closed into a ring: edge i of VN position q lies in CN position (q + i) mod L, socket dv * t + i of a CN of position pc
+// belongs to VN position (pc - i) mod L, and every CN of positions 0 .. L - 1 has dc sockets.  Only the four places that turn a VN
+// position plus an edge index into a CN position or back know it — the build, the release step, the lost pass, the
+// neighbourhood — and each wraps with a compare and an add (L >= dv: one wrap at most).  The CNs of positions L .. L + dv - 2
+// exist (nk and total_size are the chain's) and count zero.  The position flagged for a component stays the VN's own, j / vns_pos:
+// edge 0 of a row lies in CN position q, which is the position peel_sweep.hip flags from the int32 rows.
 #include "common.h"
 #include "kernel_util.h"
 #include "table_rows.h"
+#include "../../include/scldpc_ensembles.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -51,6 +60,7 @@ using namespace scldpc_dev;
 
 constexpr int kBlock = 256;             // threads per trial
 constexpr int kPerCu = 7;               // workgroups per CU the LDS carve aims at (SGPRs <= 96, VGPRs <= 72)
+constexpr int kRingPerCu = 4;           // the same for the tail-biting instances (instance_of)
 constexpr int kSwitchWidth = 128;       // frontier entries below which the waves go private
 constexpr int kMinQueueWords = 128;     // a queue shorter than 256 entries is no fast path: take fewer workgroups per CU
 constexpr int kMinDebugQcap = 8;        // floor of SCLDPC_DEBUG_SWEEP_QCAP
@@ -93,7 +103,8 @@ __device__ __forceinline__ uint32_t spread8(uint32_t b)
 // DV, DC: the degree pair, fixed at compile time (the rows of both tables are unrolled; table_rows.h).
 // OCC: waves per SIMD the registers are bounded for where an instance cannot hold kPerCu (0: kPerCu).
 // WIDE: 32-bit queue entries and a 1024-thread workgroup, one per CU (the header comment).
-template <int DV, int DC, int OCC = 0, bool WIDE = false>
+// TB: the chain is a ring of L positions (the header comment); resolved at compile time, the chain's instances keep their code.
+template <int DV, int DC, int OCC = 0, bool WIDE = false, bool TB = false>
 __global__ __launch_bounds__(WIDE ? kBlockWide : kBlock, WIDE ? kBlockWide / 256 : OCC ? OCC : kPerCu) __attribute__((amdgpu_num_sgpr(96)))
 void peel_sweep_small_kernel(const SwArgs a)
 {
@@ -119,6 +130,17 @@ void peel_sweep_small_kernel(const SwArgs a)
     auto u_bit = [&](int j) { return (U[j >> 5] >> (j & 31)) & 1u; };
     auto count_of = [&](int c) { return (cnt[c >> 3] >> ((c & 7) * 4)) & 15u; };
     const uint32_t *ch = a.chan + (size_t)trial * nw;
+    // CN of edge i of a VN whose position starts at CN `base` = position * C (l: the row's position-local id); on the ring a CN
+    // position at or beyond L wraps by -L
+    auto cn_of_edge = [&](int base, int i, int l) {
+        if constexpr (TB) {
+            int c = base + i * C;
+            if (c >= a.L * C) c -= a.L * C;
+            return c + l;
+        } else {
+            return base + i * C + l;
+        }
+    };
 
     // ---- channel bits, clear the counts -------------------------------------------------------------------------
     for (int c = tid; c < a.ncw; c += BLOCK) cnt[c] = 0;
@@ -152,7 +174,7 @@ void peel_sweep_small_kernel(const SwArgs a)
                 const int base = (int)__umulhi((uint32_t)j, a.magic_v) * C;
                 int cc[DV];
 #pragma unroll
-                for (int i = 0; i < DV; i++) cc[i] = base + i * C + (int)r[u][i];
+                for (int i = 0; i < DV; i++) cc[i] = cn_of_edge(base, i, (int)r[u][i]);
 #pragma unroll
                 for (int i = 0; i < DV; i++) atomicAdd(&cnt[cc[i] >> 3], 1u << ((cc[i] & 7) * 4));
             }
@@ -172,7 +194,15 @@ void peel_sweep_small_kernel(const SwArgs a)
         for (int k = 0; k < DC; k++) { jk[k] = s[k]; none[k] = jk[k] == 0xFFFFu; }
         const int vbase = (int)__umulhi((uint32_t)c, a.magic_c) * V;     // CN position * V; socket s = DV * t + i -> global VN index
 #pragma unroll
-        for (int k = 0; k < DC; k++) jk[k] = (uint32_t)(vbase - (int)(jk[k] % DV) * V) + (jk[k] / DV);
+        for (int k = 0; k < DC; k++) {
+            if constexpr (TB) {                                          // a VN position below 0 wraps by +L (n = L * V)
+                int vb = vbase - (int)(jk[k] % DV) * V;
+                if (vb < 0) vb += n;
+                jk[k] = (uint32_t)vb + (jk[k] / DV);
+            } else {
+                jk[k] = (uint32_t)(vbase - (int)(jk[k] % DV) * V) + (jk[k] / DV);
+            }
+        }
         uint32_t wd[DC];
 #pragma unroll
         for (int k = 0; k < DC; k++) wd[k] = U[none[k] ? 0u : jk[k] >> 5];              // no VN: any word, masked below
@@ -187,7 +217,7 @@ void peel_sweep_small_kernel(const SwArgs a)
         const int base = (int)__umulhi((uint32_t)j, a.magic_v) * C;
         int cc[DV];
 #pragma unroll
-        for (int i = 0; i < DV; i++) cc[i] = base + i * C + (int)r[i];
+        for (int i = 0; i < DV; i++) cc[i] = cn_of_edge(base, i, (int)r[i]);
         uint32_t o[DV];
 #pragma unroll
         for (int i = 0; i < DV; i++) o[i] = atomicSub(&cnt[cc[i] >> 3], 1u << ((cc[i] & 7) * 4));
@@ -376,7 +406,7 @@ void peel_sweep_small_kernel(const SwArgs a)
                 bool in_range = false, all_inside = true;
 #pragma unroll
                 for (int i = 0; i < DV; i++) {
-                    cc[i] = base + i * C + (int)r[i];
+                    cc[i] = cn_of_edge(base, i, (int)r[i]);
                     in_range |= cc[i] >= a.lost_lo && cc[i] < a.lost_hi;                // PD:661-664
                     all_inside &= cc[i] < cn_lim;                                       // PD:665
                 }
@@ -397,7 +427,9 @@ void peel_sweep_small_kernel(const SwArgs a)
             int partner = -1;
 #pragma unroll
             for (int i = 0; i < DV; i++) {
-                const int c = (pos + i) * C + (int)r[i];
+                int pc = pos + i;                                        // the CN position of edge i
+                if constexpr (TB) { if (pc >= a.L) pc -= a.L; }
+                const int c = pc * C + (int)r[i];
                 const uint32_t k = count_of(c);
                 if (k >= 3u) return -2;
                 if (k == 2u) {
@@ -407,7 +439,9 @@ void peel_sweep_small_kernel(const SwArgs a)
                     for (int e = 0; e < DC; e++) {
                         const uint32_t se = s[e];
                         if (se == 0xFFFFu) continue;
-                        const int j2 = (pos + i - (int)(se % DV)) * V + (int)(se / DV);  // c lies in CN position pos + i
+                        int vp = pc - (int)(se % DV);                    // c lies in CN position pc
+                        if constexpr (TB) { if (vp < 0) vp += a.L; }
+                        const int j2 = vp * V + (int)(se / DV);
                         if (j2 != j && u_bit(j2)) other = j2;
                     }
                     if (partner >= 0 && other != partner) return -2;
@@ -484,8 +518,19 @@ using Kernel = void (*)(const SwArgs);
 // The instances with their VGPRs / SGPRs at -O3 for gfx950 (make resources), and the workgroups per CU each is
 // bounded for
 struct Instance { Kernel kern; int per_cu; };
-Instance instance_of(int dv, int dc, bool wide = false)
+Instance instance_of(int dv, int dc, bool wide = false, bool tb = false)
 {
+    if (tb) {
+        // The ring peels at all L positions at once where the chain peels in a wave: its levels are some L / dv times as wide
+        // (about 1200 CNs behind the first frontier at (4,8), L = 50, M = 1000, against the 768 entries a carve for seven
+        // workgroups leaves).  So the narrow ring instances aim the carve at kRingPerCu workgroups per CU, i.e. at longer queues:
+        // no scan after the first in 2048 trials of each full-size shape, and the decoder no slower than at seven, six or five
+        // (profiles/sweep_ens_per_cu_ab.txt).  The register bounds stay the chain's.
+        if (dv == 4 && dc == 8) return wide ? Instance{peel_sweep_small_kernel<4, 8, 0, true, true>, 1} : Instance{peel_sweep_small_kernel<4, 8, 0, false, true>, kRingPerCu};
+        if (dv == 3 && dc == 6) return wide ? Instance{peel_sweep_small_kernel<3, 6, 0, true, true>, 1} : Instance{peel_sweep_small_kernel<3, 6, 0, false, true>, kRingPerCu};
+        if (dv == 5 && dc == 10) return wide ? Instance{peel_sweep_small_kernel<5, 10, 0, true, true>, 1} : Instance{peel_sweep_small_kernel<5, 10, 6, false, true>, kRingPerCu};
+        return {nullptr, 0};
+    }
     if (wide) {
         if (dv == 4 && dc == 8) return {peel_sweep_small_kernel<4, 8, 0, true>, 1};
         if (dv == 3 && dc == 6) return {peel_sweep_small_kernel<3, 6, 0, true>, 1};
@@ -532,9 +577,12 @@ const char *wide_shape_limit(const scldpc_code_params *p, int fz_lim)
     return nullptr;
 }
 
-// The one body of the two entry points.  The checks come in one fixed order: the parameters, the CN ranges, the shape (judged
+// what the ring asks beyond the chain's shape rules: with fewer positions than edges two edges of a VN would meet in one position
+constexpr const char *kRingLimit = "tail-biting needs L >= dv";
+
+// The one body of the four entry points (tb: the tail-biting instances).  The checks come in one fixed order: the parameters, the CN ranges, the shape (judged
 // even for an empty batch), the buffers; nothing is dereferenced before all have passed.
-int sweep_launch(const char *who, bool wide, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+int sweep_launch(const char *who, bool wide, bool tb, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                  const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t total_size, int32_t sweep_start, int32_t lost_lo,
                  int32_t lost_hi, int32_t *d_out, uint32_t *d_lost_bits, void *stream)
 {
@@ -546,12 +594,14 @@ int sweep_launch(const char *who, bool wide, const scldpc_code_params *p, int32_
     const int fz_lim = std::min(sweep_start, total_size);
     if (const char *why = wide ? wide_shape_limit(p, fz_lim) : shape_limit(p, fz_lim))
         return set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s", who, why);
+    if (tb && p->L < p->dv)                                              // (part of the ring's shape rule: as the sampler's)
+        return set_error(SCLDPC_ERR_BAD_ARG, "%s: %s (got L = %d, dv = %d)", who, kRingLimit, p->L, p->dv);
     if (ntrials < 0 || (ntrials > 0 && (!d_out || !d_vn_adj16 || !d_cn_sock16 || !d_chan_bits)))
         return set_error(SCLDPC_ERR_BAD_ARG, "%s: null buffer or negative ntrials", who);
     if (ntrials == 0) return SCLDPC_OK;
 
     SwArgs a{};
-    const Instance inst = instance_of(p->dv, p->dc, wide);
+    const Instance inst = instance_of(p->dv, p->dc, wide, tb);
     int per_cu = inst.per_cu;
     // A/B only (tools/sweep_small_speedup.py): aim the carve at fewer workgroups per CU, i.e. at longer queues
     if (const char *v = getenv("SCLDPC_DEBUG_SWEEP_PER_CU")) per_cu = std::max(1, std::min(atoi(v), per_cu));
@@ -589,7 +639,7 @@ extern "C" int scldpc_peel_sweep_device_sock16(const scldpc_code_params *p, int3
                                                int32_t sweep_start, int32_t lost_lo, int32_t lost_hi, int32_t *d_out,
                                                uint32_t *d_lost_bits, void *stream)
 {
-    return sweep_launch("scldpc_peel_sweep_device_sock16", false, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, total_size,
+    return sweep_launch("scldpc_peel_sweep_device_sock16", false, false, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, total_size,
                         sweep_start, lost_lo, lost_hi, d_out, d_lost_bits, stream);
 }
 
@@ -600,6 +650,31 @@ extern "C" int scldpc_peel_sweep_device_sock16_wide(const scldpc_code_params *p,
                                                     int32_t sweep_start, int32_t lost_lo, int32_t lost_hi, int32_t *d_out,
                                                     uint32_t *d_lost_bits, void *stream)
 {
-    return sweep_launch("scldpc_peel_sweep_device_sock16_wide", true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, total_size,
+    return sweep_launch("scldpc_peel_sweep_device_sock16_wide", true, false, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, total_size,
+                        sweep_start, lost_lo, lost_hi, d_out, d_lost_bits, stream);
+}
+
+// 1 when scldpc_peel_sweep_device_sock16_tb / _tb_wide takes this ensemble as a ring (for sweep_start = 0): the chain's rule and L >= dv
+extern "C" int scldpc_peel_sweep_tb_supported(const scldpc_code_params *p) { return shape_limit(p, 0) == nullptr && p->L >= p->dv; }
+extern "C" int scldpc_peel_sweep_tb_wide_supported(const scldpc_code_params *p) { return wide_shape_limit(p, 0) == nullptr && p->L >= p->dv; }
+
+// scldpc_peel_sweep_device_sock16 on the tables of a tail-biting code (scldpc_sample_philox_ensemble_device_adj16_sock): the TB
+// instances.  Columns 0, 1, 2, 7 of d_out and d_lost_bits equal scldpc_peel_sweep_device on the int32 rows of the same code.
+extern "C" int scldpc_peel_sweep_device_sock16_tb(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                                  const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t total_size,
+                                                  int32_t sweep_start, int32_t lost_lo, int32_t lost_hi, int32_t *d_out,
+                                                  uint32_t *d_lost_bits, void *stream)
+{
+    return sweep_launch("scldpc_peel_sweep_device_sock16_tb", false, true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, total_size,
+                        sweep_start, lost_lo, lost_hi, d_out, d_lost_bits, stream);
+}
+
+// The same from the wide form
+extern "C" int scldpc_peel_sweep_device_sock16_tb_wide(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                                                       const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t total_size,
+                                                       int32_t sweep_start, int32_t lost_lo, int32_t lost_hi, int32_t *d_out,
+                                                       uint32_t *d_lost_bits, void *stream)
+{
+    return sweep_launch("scldpc_peel_sweep_device_sock16_tb_wide", true, true, p, ntrials, d_vn_adj16, d_cn_sock16, d_chan_bits, total_size,
                         sweep_start, lost_lo, lost_hi, d_out, d_lost_bits, stream);
 }

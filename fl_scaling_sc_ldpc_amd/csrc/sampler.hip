@@ -19,6 +19,7 @@
 // sampler_common.h's, shared with the second generation.
 #include "sampler_common.h"
 #include "philox.h"
+#include "../../include/scldpc_ensembles.h"
 
 namespace {
 
@@ -822,7 +823,10 @@ int launch(const scldpc_code_params *p, int ensemble, uint64_t seed, uint64_t tr
     if (ensemble != SCLDPC_ENS_OLMOS && big)
         return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: the tail-biting / protograph samplers take at most 8192 sockets "
                                  "per position (got %d)", who, a.S);
-    if (ensemble == SCLDPC_ENS_TAIL_BITING && (ADJ16 || p->L < p->dv))
+    // (2-byte rows of a ring: only with the table, for the decoder that wraps — scldpc_sample_philox_ensemble_device_adj16_sock)
+    if (ensemble == SCLDPC_ENS_TAIL_BITING && ADJ16 && table && p->L < p->dv)
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: tail-biting needs L >= dv (got L = %d, dv = %d)", who, p->L, p->dv);
+    if (ensemble == SCLDPC_ENS_TAIL_BITING && ((ADJ16 && !table) || p->L < p->dv))
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: tail-biting needs global CN ids (int32 adjacency) and L >= dv", who);
     if (ensemble == SCLDPC_ENS_PROTOGRAPH) {
         if (p->dc % p->dv != 0)
@@ -973,6 +977,48 @@ extern "C" int scldpc_sample_philox_device_adj16_sock(const scldpc_code_params *
                                  p->cns_pos, p->vns_pos);
     return launch<true>(p, SCLDPC_ENS_OLMOS, seed, trial0, ntrials, eps, ndoped, doped_positions, d_vn_adj16, d_chan_bits,
                         scldpc::Scratch{d_workspace, workspace_bytes, nullptr}, stream, who, true, d_cn_sock16);
+}
+
+// ---- tail-biting / protograph with position-local rows and the CN -> socket table -------------------------------------------
+// Which limit keeps (p, ensemble) from scldpc_sample_philox_ensemble_device_adj16_sock beyond those launch judges; nullptr: none
+static const char *ens_sock_limit(const scldpc_code_params *p)
+{
+    if ((int64_t)p->vns_pos * p->dv > 65535) return "sockets: vns_pos * dv must fit 16 bits with 0xFFFF free (at most 65535)";
+    if (p->cns_pos > 65536) return "at most 65536 CNs per position (16-bit position-local CN ids)";
+    return nullptr;
+}
+
+// the shape rule of scldpc_sample_philox_ensemble_device_adj16_sock: pure, the same for every ntrials
+static int ens_sock_shape(const char *who, const scldpc_code_params *p, int32_t ensemble)
+{
+    if (int rc = scldpc::check_params(p)) return rc;
+    if (ensemble == SCLDPC_ENS_OLMOS)
+        return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: the Olmos chain's rows are position-local already: its entry is "
+                                 "scldpc_sample_philox_device_adj16_sock", who);
+    if (const char *limit = ens_sock_limit(p))
+        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "%s: %s (got dv=%d dc=%d cns_pos=%d vns_pos=%d)", who, limit, p->dv, p->dc,
+                                 p->cns_pos, p->vns_pos);
+    uint64_t need = 0;
+    return launch<true>(p, ensemble, 0, 0, 1, 0.5, 0, nullptr, nullptr, nullptr, scldpc::Scratch{nullptr, 0, &need}, nullptr, who, true);
+}
+
+extern "C" int scldpc_sample_philox_ensemble_adj16_sock_supported(const scldpc_code_params *p, int32_t ensemble)
+{
+    return ens_sock_shape("scldpc_sample_philox_ensemble_adj16_sock_supported", p, ensemble) == SCLDPC_OK;
+}
+
+extern "C" int scldpc_sample_philox_ensemble_device_adj16_sock(const scldpc_code_params *p, int32_t ensemble, uint64_t seed,
+                                                               uint64_t trial0, int32_t ntrials, double eps, int32_t ndoped,
+                                                               const int32_t *doped_positions, uint16_t *d_vn_adj16,
+                                                               uint16_t *d_cn_sock16, uint32_t *d_chan_bits, void *stream)
+{
+    const char *who = "scldpc_sample_philox_ensemble_device_adj16_sock";
+    if (int rc = ens_sock_shape(who, p, ensemble)) return rc;
+    // rows and channel: the instances scldpc_sample_philox_ensemble_device runs, storing 2-byte position-local ids
+    if (int rc = launch<true>(p, ensemble, seed, trial0, ntrials, eps, ndoped, doped_positions, d_vn_adj16, d_chan_bits,
+                              scldpc::Scratch{nullptr, 0, nullptr}, stream, who, true, d_cn_sock16)) return rc;
+    // the table from the finished rows, behind them on the same stream (sw_ring.hip's pass, which knows the ring)
+    return scldpc::cn_sockets_launch(who, p, ntrials, d_vn_adj16, d_cn_sock16, ensemble == SCLDPC_ENS_TAIL_BITING, stream);
 }
 
 extern "C" int scldpc_sample_philox_ensemble_device(const scldpc_code_params *p, int32_t ensemble, uint64_t seed,

@@ -384,8 +384,10 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
 }
 
 // ---- CN -> socket table from the VN -> CN table: one workgroup per (trial, CN position) ------------------------------
+// wrapL = L: the rows are a tail-biting code's (scldpc_sample_philox_ensemble_device_adj16_sock) — edge i of CN position p comes
+// from VN position p - i + (p < i ? L : 0), and positions L .. L + dv - 2 hold no socket.  wrapL = 0: a chain.
 struct IArgs {
-    int dv, dc, L, V, C, n, nk;
+    int dv, dc, L, V, C, n, nk, wrapL;
     const uint16_t *vn_adj16;
     uint16_t *cn_sock16;
 };
@@ -397,13 +399,15 @@ __global__ __launch_bounds__(256) void cn_sockets_kernel(const IArgs a)
     uint16_t *stage = reinterpret_cast<uint16_t *>(lds + ((a.C + 3) & ~3));      // C * dc sockets
     const int D = a.L + a.dv - 1;
     const int trial = blockIdx.x / D, p = blockIdx.x % D, tid = threadIdx.x;
+    const bool off_ring = a.wrapL && p >= a.wrapL;                        // no VN position reaches this CN position: all 0xFFFF
     for (int i = tid; i < a.C; i += 256) fill[i] = 0;
     for (int i = tid; i < (a.C * a.dc + 1) / 2; i += 256) reinterpret_cast<uint32_t *>(stage)[i] = 0xFFFFFFFFu;
     __syncthreads();
     const uint16_t *rows = a.vn_adj16 + (size_t)trial * a.n * a.dv;
     for (int i = 0; i < a.dv; i++) {
-        const int qq = p - i;
-        if (qq < 0 || qq >= a.L) continue;
+        int qq = p - i;
+        if (qq < 0 && a.wrapL) qq += a.wrapL;
+        if (qq < 0 || qq >= a.L || off_ring) continue;
         for (int t = tid; t < a.V; t += 256) {
             const uint32_t l = rows[((size_t)qq * a.V + t) * a.dv + i];
             const uint32_t slot = atomicAdd(&fill[l], 1u);
@@ -507,26 +511,37 @@ extern "C" int scldpc_sw_bp_ring_supported(const scldpc_code_params *p, int32_t 
     return p->dv == 4 && p->dc == 8 && p->cns_pos <= 65536 && (int64_t)p->vns_pos * p->dv <= 65535 && ring_args(p, W, &a) == 0;
 }
 
+namespace scldpc {
+
+// The one launch of cn_sockets_kernel (tail_biting: the rows close the chain into a ring); the caller has checked the buffers
+int cn_sockets_launch(const char *who, const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
+                      uint16_t *d_cn_sock16, bool tail_biting, void *stream)
+{
+    if ((int64_t)p->vns_pos * p->dv > 65535 || p->cns_pos > 65536)
+        return set_error(SCLDPC_ERR_TOO_LARGE, "%s: sockets and CN ids must fit 16 bits", who);
+    if (ntrials == 0) return SCLDPC_OK;
+    IArgs a{p->dv, p->dc, p->L, p->vns_pos, p->cns_pos, n_of(p), nk_of(p), tail_biting ? p->L : 0, d_vn_adj16, d_cn_sock16};
+    const size_t lds_bytes = 4u * (size_t)((p->cns_pos + 3) & ~3) + 2u * (size_t)p->cns_pos * p->dc + 16;
+    if (lds_bytes > (size_t)kMaxLdsBytes)
+        return set_error(SCLDPC_ERR_TOO_LARGE, "%s: one CN position does not fit the LDS", who);
+    const long long blocks = (long long)ntrials * (p->L + p->dv - 1);
+    if (blocks > 0x7FFFFFFFll)
+        return set_error(SCLDPC_ERR_TOO_LARGE, "%s: too many (trial, position) pairs for one launch", who);
+    if (int rc_ = allow_max_lds(reinterpret_cast<const void *>(cn_sockets_kernel))) return rc_;
+    hipLaunchKernelGGL(cn_sockets_kernel, dim3((unsigned)blocks), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), a);
+    SCLDPC_HIP_CHECK(hipGetLastError());
+    return SCLDPC_OK;
+}
+
+}  // namespace scldpc
+
 extern "C" int scldpc_cn_sockets_device(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                         uint16_t *d_cn_sock16, void *stream)
 {
     if (int rc = scldpc::check_params(p)) return rc;
     if (ntrials < 0 || (ntrials > 0 && (!d_vn_adj16 || !d_cn_sock16)))
         return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "scldpc_cn_sockets_device: null buffer or negative ntrials");
-    if ((int64_t)p->vns_pos * p->dv > 65535 || p->cns_pos > 65536)
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_cn_sockets_device: sockets and CN ids must fit 16 bits");
-    if (ntrials == 0) return SCLDPC_OK;
-    IArgs a{p->dv, p->dc, p->L, p->vns_pos, p->cns_pos, scldpc::n_of(p), scldpc::nk_of(p), d_vn_adj16, d_cn_sock16};
-    const size_t lds_bytes = 4u * (size_t)((p->cns_pos + 3) & ~3) + 2u * (size_t)p->cns_pos * p->dc + 16;
-    if (lds_bytes > (size_t)scldpc::kMaxLdsBytes)
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_cn_sockets_device: one CN position does not fit the LDS");
-    const long long blocks = (long long)ntrials * (p->L + p->dv - 1);
-    if (blocks > 0x7FFFFFFFll)
-        return scldpc::set_error(SCLDPC_ERR_TOO_LARGE, "scldpc_cn_sockets_device: too many (trial, position) pairs for one launch");
-    if (int rc_ = scldpc::allow_max_lds(reinterpret_cast<const void *>(cn_sockets_kernel))) return rc_;
-    hipLaunchKernelGGL(cn_sockets_kernel, dim3((unsigned)blocks), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), a);
-    SCLDPC_HIP_CHECK(hipGetLastError());
-    return SCLDPC_OK;
+    return scldpc::cn_sockets_launch("scldpc_cn_sockets_device", p, ntrials, d_vn_adj16, d_cn_sock16, false, stream);
 }
 
 extern "C" int scldpc_sw_bp_ring_device(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,

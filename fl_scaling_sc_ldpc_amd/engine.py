@@ -284,6 +284,32 @@ def sample_philox_sock(p, seed, trial0, ntrials, eps, doped=(), device="cuda:0",
     return d_adj, d_cn, d_ch
 
 
+def ens_sock16_supported(p, ensemble):
+    """Whether sample_philox_ens_sock16 takes this ensemble ("tail_biting" | "protograph"; "olmos" never: its rows are
+    position-local already) — scldpc_sample_philox_ensemble_adj16_sock_supported; on False lib().scldpc_last_error() names the
+    limit.  Needs no device."""
+    return bool(lib().scldpc_sample_philox_ensemble_adj16_sock_supported(C.byref(p), ENSEMBLES[ensemble]))
+
+
+def sample_philox_ens_sock16(p, ensemble, seed, trial0, ntrials, eps, doped=(), device="cuda:0", out=None):
+    """scldpc_sample_philox_ensemble_device_adj16_sock: (vn_adj16 int16 [T,n,dv], cn_sock16 int16 [T,nk,dc], chan int32 [T,nw])
+    of the tail-biting or protograph ensemble.  chan is bit for bit sample_philox(..., ensemble=ensemble)'s, vn_adj16 holds its
+    rows as position-local ids (edge i of VN position q in CN position (q + i) mod L, protograph: q + i), cn_sock16 the sockets
+    dv * t + i of every CN (0xFFFF: none)."""
+    _require_gpu()
+    if out is None:
+        d_adj = _uninit((ntrials, p.n, p.dv), dtype=torch.int16, device=device)
+        d_cn = _uninit((ntrials, p.nk, p.dc), dtype=torch.int16, device=device)
+        d_ch = _uninit((ntrials, p.nw), dtype=torch.int32, device=device)
+    else:
+        d_adj, d_cn, d_ch = out
+    darr, dptr = _lib.doped_array(doped)
+    check(lib().scldpc_sample_philox_ensemble_device_adj16_sock(C.byref(p), ENSEMBLES[ensemble], int(seed), int(trial0), int(ntrials),
+                                                                float(eps), darr.size, dptr, d_adj.data_ptr(), d_cn.data_ptr(),
+                                                                d_ch.data_ptr(), _stream_ptr(d_adj.device)))
+    return d_adj, d_cn, d_ch
+
+
 def cn_adj_from_vn_adj(p, adj16):
     """Host: the CN -> VN table (uint16 [.., nk, dc] as int16 bit patterns: the VNs of every CN in ascending order,
     0xFFFF where a chain-end CN has fewer than dc) from the position-local VN -> CN table — for feeding host-sampled
@@ -638,12 +664,29 @@ def _peel_sweep_tables(entry, p, d_adj16, d_cn_sock, d_chan, total_size, sweep_s
     return {"out": out, "lost": lost}
 
 
-def peel_sweep_sock16(p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=None, want_lost=False):
+def _sweep_entry(ensemble, wide):
+    """The entry of peel_sweep_sock16(_wide) for the tables of `ensemble`: a tail-biting code is a ring (the _tb entries), the
+    Olmos and protograph codes are chains."""
+    if ensemble not in ENSEMBLES:
+        raise ValueError("ensemble must be one of %s" % (sorted(ENSEMBLES),))
+    return "scldpc_peel_sweep_device_sock16" + ("_tb" if ensemble == "tail_biting" else "") + ("_wide" if wide else "")
+
+
+def peel_sweep_tb_supported(p, wide=False):
+    """Whether peel_sweep_sock16(..., ensemble="tail_biting") — wide: peel_sweep_sock16_wide — takes this ensemble as a ring:
+    the chain's shape rule and L >= dv (scldpc_peel_sweep_tb_supported / _tb_wide_supported).  Needs no device."""
+    fn = lib().scldpc_peel_sweep_tb_wide_supported if wide else lib().scldpc_peel_sweep_tb_supported
+    return bool(fn(C.byref(p)))
+
+
+def peel_sweep_sock16(p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=None, want_lost=False,
+                      ensemble="olmos"):
     """scldpc_peel_sweep_device_sock16: peel_sweep from the 2-byte VN -> CN table and the CN -> socket table (cn_sockets(p,
     d_adj16) or a second-generation sampler's) with 4 bits of LDS per CN — the same dict, columns 0, 1, 2, 7 of `out` and the
     `lost` bits bit for bit; column 5 counts this kernel's rounds, column 6 its re-scans.  No workspace, no fallback: an
-    ensemble it does not take raises."""
-    return _peel_sweep_tables("scldpc_peel_sweep_device_sock16", p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start, lost_lo,
+    ensemble it does not take raises.  ensemble: whose tables these are (sample_philox_ens_sock16) — "tail_biting" runs
+    scldpc_peel_sweep_device_sock16_tb, "protograph" this entry."""
+    return _peel_sweep_tables(_sweep_entry(ensemble, False), p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start, lost_lo,
                               lost_hi, want_lost)
 
 
@@ -654,11 +697,12 @@ def peel_sweep_wide_supported(p):
     return bool(lib().scldpc_peel_sweep_wide_supported(C.byref(p)))
 
 
-def peel_sweep_sock16_wide(p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=None, want_lost=False):
+def peel_sweep_sock16_wide(p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=None, want_lost=False,
+                           ensemble="olmos"):
     """scldpc_peel_sweep_device_sock16_wide: peel_sweep_sock16 with 32-bit queue entries and one 1024-thread workgroup per CU,
     for trials of more than 65536 CNs (and any smaller one) — the same arguments, the same dict.  No workspace, no fallback:
-    an ensemble it does not take raises."""
-    return _peel_sweep_tables("scldpc_peel_sweep_device_sock16_wide", p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start,
+    an ensemble it does not take raises.  ensemble="tail_biting": scldpc_peel_sweep_device_sock16_tb_wide."""
+    return _peel_sweep_tables(_sweep_entry(ensemble, True), p, d_adj16, d_cn_sock, d_chan, total_size, sweep_start,
                               lost_lo, lost_hi, want_lost)
 
 

@@ -182,14 +182,45 @@ SWEEP_SMALL_BY_DEFAULT = False
 # (profiles/sweep_wide_speedup.json).  Kept False here whatever is measured.
 SWEEP_WIDE_BY_DEFAULT = False
 
-SWEEP_SAMPLERS = ("sample_philox_sock16", "sample_philox_deg_sock16", "sample_philox+cn_sockets")
-SWEEP_WIDE_SAMPLERS = ("sample_philox_sock16", "sample_philox_deg_sock16", "sample_philox_wide_sock16", "sample_philox+cn_sockets")
+# Whether simulate_sc_ldpc(local_tables=None) lets sweep "small" / "wide" (and "auto" where a flag above sends it there) take
+# the tail-biting and protograph ensembles: engine.sample_philox_ens_sock16 — their rows as position-local 2-byte ids with the
+# CN -> socket table — and the 4-bit sweep decoder, whose tail-biting instances close the chain into a ring, instead of
+# sample_philox(ensemble=...) + peel_sweep: True only if every repetition of the new path beats every repetition of the old one
+# on every shape of tools/sweep_ens_speedup.py, with equal outputs (profiles/sweep_ens_speedup.json).  Kept False
+# here whatever is measured: the flip is a change of its own.
+LOCAL_TABLES_BY_DEFAULT = False
+
+SWEEP_SAMPLERS = ("sample_philox_sock16", "sample_philox_deg_sock16", "sample_philox+cn_sockets", "sample_philox_ens_sock16")
+SWEEP_WIDE_SAMPLERS = ("sample_philox_sock16", "sample_philox_deg_sock16", "sample_philox_wide_sock16", "sample_philox+cn_sockets",
+                       "sample_philox_ens_sock16")
+
+_SMALL_SHAPES = ("the 4-bit sweep decoder takes the pairs (3,6), (4,8), (5,10) with vns_pos * dv <= 65535 and at most "
+                 "65536 CNs per trial")
+_WIDE_SHAPES = ("the wide 4-bit sweep decoder takes the pairs (3,6), (4,8), (5,10) with vns_pos * dv <= 65535 (16-bit "
+                "sockets) whose CN counts, VN bits and sweep_start bitmap leave two queues of 1024 entries in one CU's LDS")
 
 
-def _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock16_ok):
+def _select_local(p, ensemble, form, chain_ok, ens_sock16_ok, tb_ok):
+    """select_sweep's rule for the tail-biting and protograph ensembles under local_tables: (form, "sample_philox_ens_sock16")
+    where the decoder of that form takes the shape — protograph: the chain's instances (chain_ok), tail-biting: the ring's
+    (tb_ok) — and the sampler takes the ensemble (ens_sock16_ok); else ("first", the limit that refused)."""
+    shape = "(dv = %d, dc = %d, L = %d, M = %d: %d CNs)" % (p.dv, p.dc, p.L, p.vns_pos, p.nk)
+    if not (tb_ok if ensemble == "tail_biting" else chain_ok):
+        return "first", "%s%s %s" % (_WIDE_SHAPES if form == "wide" else _SMALL_SHAPES,
+                                     ", tail-biting with L >= dv" if ensemble == "tail_biting" else "", shape)
+    if not ens_sock16_ok:
+        return "first", ("sample_philox_ens_sock16 takes at most 8192 sockets per position with vns_pos * dv <= 65535, tail-biting "
+                         "with L >= dv and protograph with dv | dc " + shape)
+    return form, "sample_philox_ens_sock16"
+
+
+def _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock16_ok, local_tables=False, ens_sock16_ok=False,
+                 tb_ok=False):
     """select_sweep's rule for the wide form: ("wide", one of SWEEP_WIDE_SAMPLERS) or ("first", reason)."""
     if rng != "philox":
         return "first", "rng=%r draws the codes on the host: the 4-bit sweep decoder reads the device samplers' tables" % (rng,)
+    if ensemble != "olmos" and local_tables:
+        return _select_local(p, ensemble, "wide", wide_ok, ens_sock16_ok, tb_ok)
     if ensemble != "olmos":
         return "first", "the %s tables hold global CN ids: the 4-bit sweep decoder reads position-local 2-byte rows" % ensemble
     if not wide_ok:
@@ -205,30 +236,38 @@ def _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock1
     return "wide", "sample_philox+cn_sockets"
 
 
-def select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, sweep="auto", wide_ok=False, wide_sock16_ok=False):
+def select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, sweep="auto", wide_ok=False, wide_sock16_ok=False,
+                 local_tables=False, ens_sock16_ok=False, tb_ok=False):
     """Which sampler and sweep decoder a simulate_sc_ldpc run takes: ("first", reason) — sample_philox / the host streams and
     peel_sweep —, ("small", sampler) — peel_sweep_sock16 behind one of SWEEP_SAMPLERS — or ("wide", sampler) —
     peel_sweep_sock16_wide behind one of SWEEP_WIDE_SAMPLERS.  A pure function of its arguments:
     p the _Geometry's parameters, ensemble "olmos" | "tail_biting" | "protograph", decoder_ok / sock16_ok / deg_sock16_ok the
     answers of engine.peel_sweep_sock16_supported / sock16_supported / deg_sock16_supported, sweep the requested mode,
     wide_ok / wide_sock16_ok the answers of engine.peel_sweep_wide_supported / wide_sock16_supported (read by "wide", and by
-    "auto" under SWEEP_WIDE_BY_DEFAULT where the small rule has declined)."""
+    "auto" under SWEEP_WIDE_BY_DEFAULT where the small rule has declined).
+    local_tables: the tail-biting and protograph ensembles may take "small" / "wide" behind "sample_philox_ens_sock16"
+    (_select_local) instead of being refused for their global CN ids; ens_sock16_ok is engine.ens_sock16_supported's answer and
+    tb_ok engine.peel_sweep_tb_supported's for the requested form (read for tail-biting, where decoder_ok / wide_ok are read
+    for protograph).  With local_tables false every answer and text is what it was without these three."""
+    local = dict(local_tables=local_tables, ens_sock16_ok=ens_sock16_ok, tb_ok=tb_ok)
     if sweep not in ("auto", "first", "small", "wide"):
         raise ValueError("sweep must be 'auto', 'first', 'small' or 'wide'")
     if sweep == "first":
         return "first", "sweep='first'"
     if sweep == "wide":
-        return _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock16_ok)
+        return _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock16_ok, **local)
     if sweep == "auto" and SWEEP_WIDE_BY_DEFAULT:
-        small = select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, "small") if SWEEP_SMALL_BY_DEFAULT else None
+        small = select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, "small", **local) if SWEEP_SMALL_BY_DEFAULT else None
         if small and small[0] == "small":
             return small
-        wide = _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock16_ok)
+        wide = _select_wide(p, rng, ensemble, sock16_ok, deg_sock16_ok, wide_ok, wide_sock16_ok, **local)
         return wide if wide[0] == "wide" or not small else small
     if sweep == "auto" and not SWEEP_SMALL_BY_DEFAULT:
         return "first", "sweep='auto' is 'first' (SWEEP_SMALL_BY_DEFAULT)"
     if rng != "philox":
         return "first", "rng=%r draws the codes on the host: the 4-bit sweep decoder reads the device samplers' tables" % (rng,)
+    if ensemble != "olmos" and local_tables:
+        return _select_local(p, ensemble, "small", decoder_ok, ens_sock16_ok, tb_ok)
     if ensemble != "olmos":
         return "first", "the %s tables hold global CN ids: the 4-bit sweep decoder reads position-local 2-byte rows" % ensemble
     if not decoder_ok:
@@ -241,29 +280,47 @@ def select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, sweep="
     return "small", "sample_philox+cn_sockets"
 
 
-def _sweep_choice(p, rng, ensemble, sweep):
-    """select_sweep with the library's answers; sweep='small' / 'wide' on a run it refuses raises."""
+def _sweep_choice(p, rng, ensemble, sweep, local_tables=None):
+    """select_sweep with the library's answers; sweep='small' / 'wide' on a run it refuses raises, and so does
+    local_tables=True on a run that does not take the position-local tables of a tail-biting or protograph ensemble."""
+    if sweep not in ("auto", "first", "small", "wide"):
+        raise ValueError("sweep must be 'auto', 'first', 'small' or 'wide'")
+    asked = local_tables is True                                         # None: what LOCAL_TABLES_BY_DEFAULT says, never an error
+    local = LOCAL_TABLES_BY_DEFAULT if local_tables is None else bool(local_tables)
+    if asked and ensemble == "olmos":
+        raise ValueError("local_tables=True: the Olmos chain's tables are position-local already (the switch is for the "
+                         "tail-biting and protograph ensembles)")
     # the default path asks the library nothing it did not ask before
     small = sweep == "small" or (sweep == "auto" and SWEEP_SMALL_BY_DEFAULT)
     wide = sweep == "wide" or (sweep == "auto" and SWEEP_WIDE_BY_DEFAULT)
     decoder_ok = E.peel_sweep_sock16_supported(p) if small else False
     sock16_ok, deg_sock16_ok = (E.sock16_supported(p), E.deg_sock16_supported(p)) if small or wide else (False, False)
     wide_ok, wide_sock16_ok = (E.peel_sweep_wide_supported(p), E.wide_sock16_supported(p)) if wide else (False, False)
+    ens_ok = tb_ok = False
+    if local and ensemble != "olmos" and rng == "philox" and (small or wide):
+        ens_ok = E.ens_sock16_supported(p, ensemble)
+        # (sweep="auto" under both flags: the narrow ring's answer also stands for the wide one, which takes every shape it takes)
+        tb_ok = E.peel_sweep_tb_supported(p, wide=wide and not small) if ensemble == "tail_biting" else False
     kind, what = select_sweep(p, rng, ensemble, decoder_ok, sock16_ok, deg_sock16_ok, sweep, wide_ok=wide_ok,
-                              wide_sock16_ok=wide_sock16_ok)
+                              wide_sock16_ok=wide_sock16_ok, local_tables=local, ens_sock16_ok=ens_ok, tb_ok=tb_ok)
+    if asked and kind == "first":
+        raise ValueError("local_tables=True: %s" % what)
     if sweep in ("small", "wide") and kind != sweep:
         raise ValueError("sweep='%s': %s" % (sweep, what))
     if sweep != "auto" or kind != "first":
-        line = (what.replace("+", " + ") + " + peel_sweep_small (4-bit CN counts)" if kind == "small" else
-                what.replace("+", " + ") + " + peel_sweep_wide (4-bit CN counts, 32-bit queues)" if kind == "wide" else
+        ring = ", tail-biting" if ensemble == "tail_biting" else ""
+        line = (what.replace("+", " + ") + " + peel_sweep_small (4-bit CN counts%s)" % ring if kind == "small" else
+                what.replace("+", " + ") + " + peel_sweep_wide (4-bit CN counts, 32-bit queues%s)" % ring if kind == "wide" else
                 "%s + peel_sweep (16- or 32-bit CN words): %s" % ("sampler (first generation)" if rng == "philox" else
                                                                   "host streams", what))
         print("[scldpc] kernels: " + line, file=sys.stderr, flush=True)
     return kind, what
 
 
-def _sample_small(sampler, p, seed, trial0, ntrials, e, doped, device):
+def _sample_small(sampler, p, seed, trial0, ntrials, e, doped, device, ensemble="olmos"):
     """(vn_adj16, cn_sock16, chan) from the sampler select_sweep named."""
+    if sampler == "sample_philox_ens_sock16":
+        return E.sample_philox_ens_sock16(p, ensemble, seed, trial0, ntrials, e, doped, device=device)
     if sampler == "sample_philox_sock16":
         return E.sample_philox_sock16(p, seed, trial0, ntrials, e, doped, device=device)
     if sampler == "sample_philox_deg_sock16":
@@ -275,14 +332,19 @@ def _sample_small(sampler, p, seed, trial0, ntrials, e, doped, device):
 
 
 def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats=int(1e5),
-                     max_fuckups=2000, doping_points=[], rng="numpy", seed=0, batch=None, device=None, sweep="auto"):
+                     max_fuckups=2000, doping_points=[], rng="numpy", seed=0, batch=None, device=None, sweep="auto",
+                     local_tables=None):
     """Error-rate Monte-Carlo of the sweep peeling decoder (PD:591-701); returns the reference's 13-tuple.
     rng="philox" under torch.distributed: every round of world*batch trials is split evenly over the ranks, the
     per-trial result rows (32 B each) are all-gathered and every rank runs the same ordered accumulation, so the stop
     rule (max_fuckups, PD:698) cuts at the same trial and every rank returns the same tuple as a single rank would.
     sweep: "first" = peel_sweep, "small" = the 4-bit sweep decoder and the sampler select_sweep names (ValueError where it
     does not apply), "wide" = its wide form for more than 65 536 CNs per trial (the same), "auto" = what SWEEP_SMALL_BY_DEFAULT
-    and then SWEEP_WIDE_BY_DEFAULT say; the same 13-tuple either way."""
+    and then SWEEP_WIDE_BY_DEFAULT say; the same 13-tuple either way.
+    local_tables: True = a tail-biting or protograph run takes sweep "small" / "wide" on position-local tables
+    (sample_philox_ens_sock16; ValueError("local_tables=True: ...") for the Olmos chain, whose tables are position-local
+    already, for a sweep that resolves to "first", for rng="numpy" and for a shape the sampler or the decoder refuses), False =
+    never, None = what LOCAL_TABLES_BY_DEFAULT says."""
     _check_flags(is_protograph, is_tail_biting)
     device = _device(device)
     dist, rank, world = _dist()
@@ -291,7 +353,9 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
     g = _Geometry(l, r, L, M, is_terminated, is_bounded, doping_points)
     p = g.params
     ens = "protograph" if is_protograph else "tail_biting" if is_tail_biting else "olmos"
-    kind, small_sampler = _sweep_choice(p, rng, ens, sweep)
+    kind, small_sampler = _sweep_choice(p, rng, ens, sweep, local_tables)
+    # whose tables the decoder reads: passed on only where it is not the Olmos chain's (sample_philox_ens_sock16)
+    ens_kw = {"ensemble": ens} if small_sampler == "sample_philox_ens_sock16" and kind != "first" else {}
     if batch is None:
         batch = 64 if rng == "numpy" else 2048
     # The reference's per-trial bookkeeping and its stop rule (PD:668-699) run on the device, in trial order
@@ -320,7 +384,7 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
                 raise NameError("name 'position' is not defined")   # the reference's own failure for soft doping (PD:228)
             doped = [] if soft else _doped_positions(doping_points)
             if kind in ("small", "wide"):
-                d_adj, d_cn, d_ch = _sample_small(small_sampler, p, seed, done + lo, mine, e, doped, device)
+                d_adj, d_cn, d_ch = _sample_small(small_sampler, p, seed, done + lo, mine, e, doped, device, ens)
             else:
                 d_adj, d_ch = E.sample_philox(p, seed, done + lo, mine, e, doped, device=device, adj16=(ens == "olmos"),
                                               ensemble=ens)
@@ -330,9 +394,9 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
         else:
             raise ValueError("rng must be 'numpy' or 'philox'")
         if kind == "small":
-            d_out = E.peel_sweep_sock16(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
+            d_out = E.peel_sweep_sock16(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi, **ens_kw)["out"]
         elif kind == "wide":
-            d_out = E.peel_sweep_sock16_wide(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
+            d_out = E.peel_sweep_sock16_wide(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi, **ens_kw)["out"]
         else:
             d_out = E.peel_sweep(p, d_adj, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
         if world > 1:
@@ -623,12 +687,17 @@ def _safe_eval(text):
 def _cli_options(args, kw):
     """The reference's command lines are positional only.  This mirror also takes, anywhere among them,
     `--rng philox|numpy`, `--seed S`, `--batch B`, `--device D` — the keyword arguments of the simulators (throughput mode:
-    device sampling, trials sharded over the ranks of a torch.distributed.run job) — `--sweep first|small|wide|auto`, which
-    only ber_sim (simulate_sc_ldpc) takes, and `--pick first|multi|auto`, which only simulate_variance
-    (simulate_peeling_decoder_ldpc) takes."""
+    device sampling, trials sharded over the ranks of a torch.distributed.run job) — `--sweep first|small|wide|auto` and
+    `--local-tables on|off|auto` (local_tables=True | False | None), which only ber_sim (simulate_sc_ldpc) takes, and
+    `--pick first|multi|auto`, which only simulate_variance (simulate_peeling_decoder_ldpc) takes."""
     kw, pos, it = dict(kw), [], iter(args)
     for x in it:
-        if isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device", "--sweep", "--pick"):
+        if isinstance(x, str) and x == "--local-tables":
+            v = next(it)
+            if v not in ("on", "off", "auto"):
+                raise SystemExit("--local-tables takes on, off or auto (got %r)" % (v,))
+            kw["local_tables"] = {"on": True, "off": False, "auto": None}[v]
+        elif isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device", "--sweep", "--pick"):
             v = next(it)
             if x == "--sweep" and v not in ("first", "small", "wide", "auto"):
                 raise SystemExit("--sweep takes first, small, wide or auto (got %r)" % (v,))
@@ -714,6 +783,9 @@ def main_simulate_variance(argv=None, **kw):
     if "sweep" in kw:
         raise SystemExit("--sweep chooses the sweep decoder of ber_sim (simulate_sc_ldpc): simulate_variance runs the "
                          "random-pick decoder and takes no such option")
+    if "local_tables" in kw:
+        raise SystemExit("--local-tables chooses the tables of ber_sim's sweep decoder (simulate_sc_ldpc): simulate_variance runs "
+                         "the random-pick decoder and takes no such option")
     joined = _join_job(kw)
     try:
         return _main_simulate_variance(a, kw)

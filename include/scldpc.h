@@ -443,7 +443,8 @@ int scldpc_peel_sweep_device_adj16(const scldpc_code_params *p, int32_t ntrials,
  * d_lost_bits equal scldpc_peel_sweep_device_adj16's bit for bit; [5] counts this kernel's barrier rounds, [6] its scans after
  * the first (0 unless a queue overflowed).  total_size in [0, nk], any sweep_start >= 0.  Checks in a fixed order: parameters,
  * CN ranges (SCLDPC_ERR_BAD_ARG), shape (SCLDPC_ERR_TOO_LARGE, also for ntrials == 0), buffers.  More than 65536 CNs per trial
- * take the _wide form below; there is no form for the CN -> VN table or for tail-biting / protograph tables (global CN ids). */
+ * take the _wide form below; there is no form for the CN -> VN table.  Tail-biting and protograph codes have position-local tables
+ * and the ring form of this decoder in the extension header scldpc_ensembles.h. */
 int scldpc_peel_sweep_sock16_supported(const scldpc_code_params *p);
 int scldpc_peel_sweep_device_sock16(const scldpc_code_params *p, int32_t ntrials, const uint16_t *d_vn_adj16,
                                     const uint16_t *d_cn_sock16, const uint32_t *d_chan_bits, int32_t total_size,
