@@ -68,6 +68,9 @@ EXPORTS_ENSEMBLES = (
     "scldpc_peel_sweep_device_sock16_tb", "scldpc_peel_sweep_device_sock16_tb_wide",
 )
 
+# every symbol the extension header include/scldpc_uncoupled.h declares (the same shared object; tests/test_uncoupled_host.py)
+EXPORTS_UNCOUPLED = ("scldpc_sample_philox_uncoupled_supported", "scldpc_sample_philox_uncoupled_device")
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -180,6 +183,8 @@ def lib():
     L.scldpc_peel_sweep_tb_wide_supported.argtypes = [pp]
     L.scldpc_peel_sweep_device_sock16_tb.argtypes = L.scldpc_peel_sweep_device_sock16.argtypes
     L.scldpc_peel_sweep_device_sock16_tb_wide.argtypes = L.scldpc_peel_sweep_device_sock16.argtypes
+    L.scldpc_sample_philox_uncoupled_supported.argtypes = [pp]
+    L.scldpc_sample_philox_uncoupled_device.argtypes = [pp, u64, u64, i32, dbl, i32, vp, vp, vp, vp]
     L.scldpc_peel_pick_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, u64, u64, vp, vp, vp, vp, u64, vp]
     L.scldpc_peel_pick_device_adj16.argtypes = L.scldpc_peel_pick_device.argtypes
     L.scldpc_peel_pick_deg_supported.argtypes = [pp, i32]

@@ -24,6 +24,7 @@ protograph-based chain (flag P, sc_ldpc_protograph.py) and the uncoupled (l,r) e
 indices mod L there (PD:204-205), which is not an ensemble.
 """
 import ast
+import math
 import os
 import pickle
 import random
@@ -578,12 +579,94 @@ def simulate_peeling_decoder_ldpc(e, l_deg, r_deg, L, M, is_terminated, is_proto
     return None, (moments.cpu().numpy() if want_moments else r1_all), plrs
 
 
-def simulate_peeling_decoder_ldpc_uncoupled(e, l_deg, r_deg, M, num_repeats=None, device=None):
+# simulate_peeling_decoder_ldpc_uncoupled(rng="philox"): the default batch keeps the expected attempts of one sampler launch,
+# batch * exp((l-1)(r-1)/2), below this — about a second of scldpc_sample_philox_uncoupled_device at (4,8), M = 1000.
+# Measured on MI355X (tools/uncoupled_speedup.py, profiles/uncoupled_speedup.json, taken with 1 << 24 here and --hard-trials 512):
+# 13.1 M attempts/s at (4,8), M = 1000 in launches of 512 trials (1.54 s; 37 561 attempts per trial) — such a launch waits for
+# its unluckiest trial, some 250 000 attempts at about 6 us each for a workgroup alone, so a smaller batch shortens it only
+# logarithmically — and 51.0 M attempts/s at (3,6), M = 1000 in launches of 8192 trials (23.5 ms; 149.4 attempts per trial),
+# which this cap leaves at the budget rule's 8192.  (4,8): batch 357.
+UNCOUPLED_ATTEMPTS_PER_LAUNCH = 13_000_000
+UNCOUPLED_MAX_ATTEMPTS = 1 << 24                # scldpc_sample_philox_uncoupled_device's range
+
+
+def _uncoupled_philox(e, l_deg, r_deg, M, num_repeats, device, seed, batch, want_moments, max_attempts):
+    """The rng="philox" body of simulate_peeling_decoder_ldpc_uncoupled."""
+    device = _device(device)
+    dist, rank, world = _dist()
+    cpp = l_deg * M // r_deg
+    num_pd_steps = int(M * (e + 0.1))                                      # PD:804
+    p = E.CodeParams(l_deg, r_deg, 1, cpp, M)
+    expected = math.exp((l_deg - 1) * (r_deg - 1) / 2.0)                    # attempts per accepted graph, about
+    if batch is None:
+        # the sibling's budget (~8192 trials in flight, ~16 GB of device buffers: tables + CN words + picks' scratch ~ 3 x the
+        # int32 adjacency, r1 rows 4 B per step), capped by the attempts one sampler launch may be expected to take
+        per_trial = 3 * M * l_deg * 4 + 4 * (num_pd_steps + 1)
+        free = _free_bytes(device)
+        batch = max(64, min(8192, int(min(16e9 + (24e9 if want_moments else 0), 0.6 * free) // per_trial)))
+        batch = max(1, min(batch, int(UNCOUPLED_ATTEMPTS_PER_LAUNCH / expected)))
+    plrs = np.zeros(num_repeats)
+    erased = np.zeros(num_repeats, dtype=np.int64)
+    r1_all = None if want_moments else np.zeros((num_repeats, num_pd_steps + 1), dtype="int")
+    moments = torch.zeros((3, num_pd_steps + 1), dtype=torch.int64, device=device) if want_moments else None
+    offs = _split(num_repeats, world)
+    for done in range(offs[rank], offs[rank + 1], batch):
+        nb = min(batch, offs[rank + 1] - done)
+        d_adj, d_ch, d_att = E.sample_philox_uncoupled(p, seed, done, nb, e, max_attempts, device=device)
+        att = d_att.cpu().numpy()                                           # the one read of the batch's attempts
+        if (att <= 0).any():
+            k = int(np.flatnonzero(att <= 0)[0])
+            if att[k] < 0:
+                raise RuntimeError("uncoupled sampler: trial %d: sixteen keys met in one bucket of the ranking (status %d)"
+                                   % (done + k, int(att[k])))
+            raise RuntimeError("uncoupled sampler: trial %d found no simple graph within max_attempts = %d; the expected number "
+                               "of attempts of the pair (%d,%d) is about exp((l-1)(r-1)/2) = %.3g"
+                               % (done + k, max_attempts, l_deg, r_deg, expected))
+        res = E.peel_pick(p, d_adj, d_ch, cpp, num_pd_steps, mt_state=None, seed=seed, trial0=done, want_r1=True)
+        if want_moments:
+            E.r1_moments(res["r1"], moments)
+        else:
+            r1_all[done:done + nb] = res["r1"].cpu().numpy()
+        o = res["out"].cpu().numpy()
+        erased[done:done + nb] = o[:, 0]
+        plrs[done:done + nb] = (o[:, 0] - o[:, 1]) / M                      # PD:823-826, 866
+    if world > 1:                                           # shares are disjoint: a sum puts them together
+        t_plr, t_er = torch.from_numpy(plrs).to(device), torch.from_numpy(erased).to(device)
+        dist.all_reduce(t_plr)
+        dist.all_reduce(t_er)
+        plrs, erased = t_plr.cpu().numpy(), t_er.cpu().numpy()
+        if want_moments:
+            dist.all_reduce(moments)
+        else:
+            t_r1 = torch.from_numpy(r1_all).to(device)
+            dist.all_reduce(t_r1)
+            r1_all = t_r1.cpu().numpy()
+    return None, (moments.cpu().numpy() if want_moments else r1_all), plrs, [int(x) for x in erased]
+
+
+def simulate_peeling_decoder_ldpc_uncoupled(e, l_deg, r_deg, M, num_repeats=None, device=None, rng="numpy", seed=0, batch=None,
+                                            want_moments=False, max_attempts=1 << 20):
     """Random-pick peeling on the uncoupled (l,r) ensemble (PD:793-869): returns (None, r1, plrs, num_vns_lst).
-    Graphs and channels come from the global numpy stream (ldpc.gen_slots with its repeat rejection, PD:134-135), the
-    picks from the global `random` stream; both are left where the reference leaves them."""
+    rng="numpy": graphs and channels come from the global numpy stream (ldpc.gen_slots with its repeat rejection, PD:134-135),
+    the picks from the global `random` stream; both are left where the reference leaves them.  One trial per launch.
+    rng="philox": the same law in throughput mode — engine.sample_philox_uncoupled redraws every trial's graph on the device
+    until it is simple (at most max_attempts candidates; a trial that finds none raises RuntimeError), engine.peel_pick
+    decodes `batch` trials per launch with Philox picks keyed (seed, trial); results do not depend on batch or on the number of
+    ranks.  want_moments=True returns the int64 [3, steps+1] moments (cnt, Σr1, Σr1²) in place of the r1 rows.  Under
+    torch.distributed rank r runs a contiguous share of the trials (global trial indices) and one all-reduce puts plrs, the
+    erased counts and the moments or rows together, so every rank returns what a single rank would."""
+    if rng not in ("numpy", "philox"):
+        raise ValueError("rng must be 'numpy' or 'philox'")
+    if not 1 <= max_attempts <= UNCOUPLED_MAX_ATTEMPTS:
+        raise ValueError("max_attempts must be in [1, 2^24] (got %r)" % (max_attempts,))
+    if rng == "philox" and (l_deg * M) % r_deg:
+        raise ValueError("rng='philox': l_deg * M must be divisible by r_deg (l_deg=%d, r_deg=%d, M=%d)" % (l_deg, r_deg, M))
     if not num_repeats:
         num_repeats = 100
+    if rng == "philox":
+        return _uncoupled_philox(e, l_deg, r_deg, M, num_repeats, device, seed, batch, want_moments, max_attempts)
+    if _dist()[2] > 1:
+        raise ValueError("rng='numpy' replays the reference's one sequential stream: single rank only")
     device = _device(device)
     cpp = int(l_deg / r_deg * M)
     num_pd_steps = int(M * (e + 0.1))                                      # PD:804
