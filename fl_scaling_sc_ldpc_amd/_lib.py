@@ -71,6 +71,10 @@ EXPORTS_ENSEMBLES = (
 # every symbol the extension header include/scldpc_uncoupled.h declares (the same shared object; tests/test_uncoupled_host.py)
 EXPORTS_UNCOUPLED = ("scldpc_sample_philox_uncoupled_supported", "scldpc_sample_philox_uncoupled_device")
 
+# every symbol the extension header include/scldpc_uncoupled_wide.h declares (the same shared object;
+# tests/test_uncoupled_wide_host.py)
+EXPORTS_UNCOUPLED_WIDE = ("scldpc_sample_philox_uncoupled_wide_supported", "scldpc_sample_philox_uncoupled_wide_device")
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -185,6 +189,8 @@ def lib():
     L.scldpc_peel_sweep_device_sock16_tb_wide.argtypes = L.scldpc_peel_sweep_device_sock16.argtypes
     L.scldpc_sample_philox_uncoupled_supported.argtypes = [pp]
     L.scldpc_sample_philox_uncoupled_device.argtypes = [pp, u64, u64, i32, dbl, i32, vp, vp, vp, vp]
+    L.scldpc_sample_philox_uncoupled_wide_supported.argtypes = [pp]
+    L.scldpc_sample_philox_uncoupled_wide_device.argtypes = L.scldpc_sample_philox_uncoupled_device.argtypes
     L.scldpc_peel_pick_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, u64, u64, vp, vp, vp, vp, u64, vp]
     L.scldpc_peel_pick_device_adj16.argtypes = L.scldpc_peel_pick_device.argtypes
     L.scldpc_peel_pick_deg_supported.argtypes = [pp, i32]

@@ -335,6 +335,30 @@ def sample_philox_uncoupled(p, seed, trial0, ntrials, eps, max_attempts, device=
     return d_adj, d_ch, d_att
 
 
+def uncoupled_wide_supported(p):
+    """Whether sample_philox_uncoupled_wide takes p = CodeParams(dv, dc, 1, cns_pos, M): L = 1, dv <= 8, at most 32768 sockets
+    and dv <= cns_pos (scldpc_sample_philox_uncoupled_wide_supported; on False lib().scldpc_last_error() names the limit).
+    Needs no device."""
+    return bool(lib().scldpc_sample_philox_uncoupled_wide_supported(C.byref(p)))
+
+
+def sample_philox_uncoupled_wide(p, seed, trial0, ntrials, eps, max_attempts, device="cuda:0", out=None):
+    """scldpc_sample_philox_uncoupled_wide_device: sample_philox_uncoupled's three outputs — bit for bit where both take the
+    shape — up to 32768 sockets (include/scldpc_uncoupled_wide.h).  attempts[t]: 0 none accepted within max_attempts, negative:
+    a part of the keys outgrew its room; rows and words are zeros then, and nothing is raised here."""
+    _require_gpu()
+    if out is None:
+        d_adj = _uninit((ntrials, p.n, p.dv), dtype=torch.int32, device=device)
+        d_ch = _uninit((ntrials, p.nw), dtype=torch.int32, device=device)
+        d_att = _uninit((ntrials,), dtype=torch.int32, device=device)
+    else:
+        d_adj, d_ch, d_att = out
+    check(lib().scldpc_sample_philox_uncoupled_wide_device(C.byref(p), int(seed), int(trial0), int(ntrials), float(eps),
+                                                           int(max_attempts), d_adj.data_ptr(), d_ch.data_ptr(), d_att.data_ptr(),
+                                                           _stream_ptr(d_adj.device)))
+    return d_adj, d_ch, d_att
+
+
 def cn_adj_from_vn_adj(p, adj16):
     """Host: the CN -> VN table (uint16 [.., nk, dc] as int16 bit patterns: the VNs of every CN in ascending order,
     0xFFFF where a chain-end CN has fewer than dc) from the position-local VN -> CN table — for feeding host-sampled

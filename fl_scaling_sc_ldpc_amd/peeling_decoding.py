@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import engine as E
+from .engine import uncoupled_supported as _unc_first_ok, uncoupled_wide_supported as _unc_wide_ok     # shape rules: no device
 
 
 # ------------------------------------------------------------------------------------------------
@@ -589,6 +590,37 @@ def simulate_peeling_decoder_ldpc(e, l_deg, r_deg, L, M, is_terminated, is_proto
 UNCOUPLED_ATTEMPTS_PER_LAUNCH = 13_000_000
 UNCOUPLED_MAX_ATTEMPTS = 1 << 24                # scldpc_sample_philox_uncoupled_device's range
 
+# Beyond 8192 sockets the graphs come from engine.sample_philox_uncoupled_wide (csrc/sampler_uncoupled_wide.hip), and the budget
+# of one launch is that kernel's: about a second at its measured rate at (3,6), M = 10000, as the first sampler's 13 M attempts
+# are about a second of its 13.1 M attempts/s.  Measured on MI355X (tools/uncoupled_wide_speedup.py,
+# profiles/uncoupled_wide_speedup.json, taken with 1_000_000 here; the tool passes its batch of 8192 itself): 2.02 M attempts/s at
+# (3,6), M = 10000 in launches of 8192 trials (589 ms; 147.9 attempts per trial) — four parts of the key range per attempt — and
+# 12.3 M attempts/s at M = 5000 (98.5 ms), where one part holds every key and this budget is the more cautious.  (3,6): the
+# budget rule's 8192 stands (13 476 would be allowed); (4,8) beyond 8192 sockets: batch 55.
+UNCOUPLED_WIDE_ATTEMPTS_PER_LAUNCH = 2_000_000
+UNCOUPLED_FIRST_SOCKETS, UNCOUPLED_WIDE_SOCKETS = 8192, 32768
+
+# Whether simulate_peeling_decoder_ldpc_uncoupled(rng="philox") takes the wide sampler also where the first one takes the shape
+# (at most 8192 sockets).  The two write the same outputs there; tools/uncoupled_wide_speedup.py times them side by side
+# (profiles/uncoupled_wide_speedup.json).  Kept False here whatever is measured: the flip is a change of its own.
+UNCOUPLED_WIDE_BY_DEFAULT = False
+
+
+def select_uncoupled(p, first_ok, wide_ok, wide_by_default=False):
+    """Which rejection sampler a simulate_peeling_decoder_ldpc_uncoupled(rng="philox") run takes: "first" —
+    engine.sample_philox_uncoupled — or "wide" — engine.sample_philox_uncoupled_wide.  A pure function of its arguments: p the
+    CodeParams(l, r, 1, cns_pos, M), first_ok / wide_ok the answers of engine.uncoupled_supported / uncoupled_wide_supported,
+    wide_by_default the module's UNCOUPLED_WIDE_BY_DEFAULT.  "first" wherever the first sampler takes the shape and
+    wide_by_default is false, so such a run does what it did before there was a second one; "wide" where only the wide one
+    does, and with wide_by_default wherever it does.  ValueError, naming the limits, where neither takes the shape."""
+    if wide_ok and (wide_by_default or not first_ok):
+        return "wide"
+    if first_ok:
+        return "first"
+    raise ValueError("rng='philox': the uncoupled samplers take L = 1, dv <= 8, dv <= cns_pos and at most %d sockets "
+                     "(sample_philox_uncoupled: %d); got dv = %d, dc = %d, cns_pos = %d, M = %d: %d sockets"
+                     % (UNCOUPLED_WIDE_SOCKETS, UNCOUPLED_FIRST_SOCKETS, p.dv, p.dc, p.cns_pos, p.vns_pos, p.cns_pos * p.dc))
+
 
 def _uncoupled_philox(e, l_deg, r_deg, M, num_repeats, device, seed, batch, want_moments, max_attempts):
     """The rng="philox" body of simulate_peeling_decoder_ldpc_uncoupled."""
@@ -598,13 +630,20 @@ def _uncoupled_philox(e, l_deg, r_deg, M, num_repeats, device, seed, batch, want
     num_pd_steps = int(M * (e + 0.1))                                      # PD:804
     p = E.CodeParams(l_deg, r_deg, 1, cpp, M)
     expected = math.exp((l_deg - 1) * (r_deg - 1) / 2.0)                    # attempts per accepted graph, about
+    sockets = cpp * r_deg
+    if sockets <= UNCOUPLED_FIRST_SOCKETS and not UNCOUPLED_WIDE_BY_DEFAULT:
+        path = "first"                                                      # the first sampler judges the shape itself, as before
+    else:
+        path = select_uncoupled(p, _unc_first_ok(p), _unc_wide_ok(p), UNCOUPLED_WIDE_BY_DEFAULT)
+    sample = E.sample_philox_uncoupled_wide if path == "wide" else E.sample_philox_uncoupled
+    budget = UNCOUPLED_WIDE_ATTEMPTS_PER_LAUNCH if sockets > UNCOUPLED_FIRST_SOCKETS else UNCOUPLED_ATTEMPTS_PER_LAUNCH
     if batch is None:
         # the sibling's budget (~8192 trials in flight, ~16 GB of device buffers: tables + CN words + picks' scratch ~ 3 x the
         # int32 adjacency, r1 rows 4 B per step), capped by the attempts one sampler launch may be expected to take
         per_trial = 3 * M * l_deg * 4 + 4 * (num_pd_steps + 1)
         free = _free_bytes(device)
         batch = max(64, min(8192, int(min(16e9 + (24e9 if want_moments else 0), 0.6 * free) // per_trial)))
-        batch = max(1, min(batch, int(UNCOUPLED_ATTEMPTS_PER_LAUNCH / expected)))
+        batch = max(1, min(batch, int(budget / expected)))
     plrs = np.zeros(num_repeats)
     erased = np.zeros(num_repeats, dtype=np.int64)
     r1_all = None if want_moments else np.zeros((num_repeats, num_pd_steps + 1), dtype="int")
@@ -612,10 +651,13 @@ def _uncoupled_philox(e, l_deg, r_deg, M, num_repeats, device, seed, batch, want
     offs = _split(num_repeats, world)
     for done in range(offs[rank], offs[rank + 1], batch):
         nb = min(batch, offs[rank + 1] - done)
-        d_adj, d_ch, d_att = E.sample_philox_uncoupled(p, seed, done, nb, e, max_attempts, device=device)
+        d_adj, d_ch, d_att = sample(p, seed, done, nb, e, max_attempts, device=device)
         att = d_att.cpu().numpy()                                           # the one read of the batch's attempts
         if (att <= 0).any():
             k = int(np.flatnonzero(att <= 0)[0])
+            if att[k] < 0 and path == "wide":
+                raise RuntimeError("uncoupled sampler: trial %d: a part of the keys outgrew its room in the wide ranking "
+                                   "(status %d)" % (done + k, int(att[k])))
             if att[k] < 0:
                 raise RuntimeError("uncoupled sampler: trial %d: sixteen keys met in one bucket of the ranking (status %d)"
                                    % (done + k, int(att[k])))
