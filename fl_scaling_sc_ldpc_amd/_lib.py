@@ -75,6 +75,10 @@ EXPORTS_UNCOUPLED = ("scldpc_sample_philox_uncoupled_supported", "scldpc_sample_
 # tests/test_uncoupled_wide_host.py)
 EXPORTS_UNCOUPLED_WIDE = ("scldpc_sample_philox_uncoupled_wide_supported", "scldpc_sample_philox_uncoupled_wide_device")
 
+# every symbol the extension header include/scldpc_cov.h declares (the same shared object; tests/test_cov_host.py)
+EXPORTS_COV = ("scldpc_r1_gram_workspace_bytes", "scldpc_r1_gram_trial_splits", "scldpc_r1_gram_device")
+COV_MAX_STEPS = 4096            # SCLDPC_COV_MAX_STEPS
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -198,6 +202,11 @@ def lib():
     L.scldpc_peel_pick_deg_workspace_bytes.restype = i64
     L.scldpc_peel_pick_device_adj16_deg.argtypes = [pp, i32, vp, vp, i32, i32, u64, u64, vp, vp, vp, u64, vp]
     L.scldpc_r1_moments_device.argtypes = [i32, i32, vp, vp, vp]
+    L.scldpc_r1_gram_workspace_bytes.argtypes = [i32, i32]
+    L.scldpc_r1_gram_workspace_bytes.restype = i64
+    L.scldpc_r1_gram_trial_splits.argtypes = [i32, i32]
+    L.scldpc_r1_gram_trial_splits.restype = i32
+    L.scldpc_r1_gram_device.argtypes = [i32, i32, vp, i32, vp, vp, vp, i64, vp]
     L.scldpc_swc_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_swc_bp_device_adj16.argtypes = L.scldpc_swc_bp_device.argtypes
     L.scldpc_stream_supported.argtypes = [pp, i32]

@@ -813,6 +813,44 @@ def r1_moments(d_r1, moments=None):
     return moments
 
 
+def r1_gram_trial_splits(ntrials, k):
+    """Over how many workgroups per 64 x 64 output tile r1_gram's launch splits `ntrials` trials at `k` steps
+    (scldpc_r1_gram_trial_splits).  Needs no device."""
+    n = lib().scldpc_r1_gram_trial_splits(int(ntrials), int(k))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def r1_gram(d_r1, steps, gram=None):
+    """scldpc_r1_gram_device: with x = d_r1[:, steps] and m = (x != 0), the exact integer Gram matrices (mᵀm, xᵀm, xᵀx) over
+    the trials of the batch, accumulated into int64 [3, K, K] (zeros where `gram` is None).  d_r1: int32 [T, ncols] on the
+    device, as peel_pick and peel_pick_deg write it; steps: any integer sequence or tensor of K <= 4096 column indices.
+    A step outside [0, ncols) is never read out of bounds: the kernel clamps it and says so in its status word, which is
+    read back here (one synchronisation) and raised as ScldpcError."""
+    _require_gpu()
+    assert d_r1.is_cuda and d_r1.dtype == torch.int32 and d_r1.dim() == 2 and d_r1.is_contiguous()
+    T, ncols = d_r1.shape
+    dev = d_r1.device
+    d_steps = torch.as_tensor(steps).reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    K = int(d_steps.numel())
+    if gram is None:
+        gram = torch.zeros((3, K, K), dtype=torch.int64, device=dev)
+    assert gram.is_cuda and gram.dtype == torch.int64 and tuple(gram.shape) == (3, K, K) and gram.is_contiguous()
+    nbytes = lib().scldpc_r1_gram_workspace_bytes(T, K)
+    if nbytes < 0:
+        check(int(nbytes))
+    ws = _uninit(int(nbytes), dtype=torch.uint8, device=dev)
+    check(lib().scldpc_r1_gram_device(T, ncols, d_r1.data_ptr(), K, d_steps.data_ptr(), gram.data_ptr(), ws.data_ptr(),
+                                      int(nbytes), _stream_ptr(dev)))
+    if T > 0:
+        status = int(ws[:4].view(torch.int32).item())
+        if status:
+            raise ScldpcError("r1_gram: a step lies outside [0, %d): the kernel clamped it (status %d) and `gram` holds the "
+                              "sums of the clamped columns" % (ncols, status))
+    return gram
+
+
 # ------------------------------------------------------------------------------------------------
 # streaming mode (main_streaming, BPF:1934-2054)
 # ------------------------------------------------------------------------------------------------

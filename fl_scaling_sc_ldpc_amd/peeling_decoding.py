@@ -580,6 +580,92 @@ def simulate_peeling_decoder_ldpc(e, l_deg, r_deg, L, M, is_terminated, is_proto
     return None, (moments.cpu().numpy() if want_moments else r1_all), plrs
 
 
+COV_MAX_STEPS = 4096            # SCLDPC_COV_MAX_STEPS (include/scldpc_cov.h)
+
+
+def _cov_steps(steps, num_pd_steps):
+    """The steps of simulate_pd_covariance as int64 [K]: an int is a stride over range(0, num_pd_steps + 1, stride)."""
+    if isinstance(steps, (int, np.integer)) and not isinstance(steps, bool):
+        if steps < 1:
+            raise ValueError("steps: a stride must be at least 1 (got %d)" % steps)
+        steps = range(0, num_pd_steps + 1, int(steps))
+    if isinstance(steps, torch.Tensor):
+        steps = steps.cpu().numpy()
+    arr = np.asarray(list(steps) if isinstance(steps, range) else steps)
+    if arr.ndim != 1 or arr.size == 0 or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("steps must be a stride or a non-empty one-dimensional sequence of integers")
+    arr = arr.astype(np.int64)
+    if arr.size > COV_MAX_STEPS:
+        raise ValueError("steps: at most %d steps (got K = %d)" % (COV_MAX_STEPS, arr.size))
+    if arr[0] < 0 or arr[-1] > num_pd_steps or arr.min() < 0 or arr.max() > num_pd_steps:
+        raise ValueError("steps: a step out of range [0, %d]" % num_pd_steps)
+    if arr.size > 1 and (np.diff(arr) <= 0).any():
+        raise ValueError("steps must be strictly increasing (unsorted or repeated steps)")
+    return arr
+
+
+def simulate_pd_covariance(e, l_deg, r_deg, L, M, is_terminated, is_protograph, num_repeats, steps, doping_points=[],
+                           seed=0, batch=None, device=None, pick="auto"):
+    """The second moments of the degree-1 trajectories between K chosen peeling steps, at a size where the rows cannot be kept:
+    returns (steps int64 [K], gram int64 [3, K, K], moments int64 [3, num_pd_steps+1], plrs float64 [num_repeats]) with, for
+    x[t, i] = r1[t, steps[i]] and m = (x != 0) over all num_repeats trials, gram = (mᵀm, xᵀm, xᵀx) in exact integers
+    (engine.r1_gram; cov_from_gram reduces it).  Philox mode only: the loop of simulate_peeling_decoder_ldpc(rng="philox",
+    want_moments=True, moments_from="rows") — the same sampler, decoder selection (pick), trial keys and batch budget, so
+    moments and plrs equal that call's value for value — in which each batch's rows go through r1_moments AND r1_gram before
+    they are dropped.  gram depends neither on batch nor on the number of ranks (integer sums); under torch.distributed one
+    more all-reduce sums it.  steps: K <= 4096 strictly increasing steps in [0, num_pd_steps], or an int stride meaning
+    range(0, num_pd_steps + 1, stride).  ValueError for other steps, a soft-doping dict, and a run whose sums could leave 63
+    bits (total_size² · num_repeats >= 2⁶³: r1 never exceeds total_size)."""
+    if isinstance(doping_points, dict):
+        raise ValueError("simulate_pd_covariance takes hard doping points only (PD:747), not a soft-doping dict")
+    num_repeats = int(num_repeats)
+    if num_repeats < 1:
+        raise ValueError("num_repeats must be at least 1")
+    cpp = int(l_deg / r_deg * M)
+    num_positions = L + l_deg - 1 if is_terminated else L
+    total_size = cpp * num_positions
+    num_pd_steps = int(M * num_positions * (e + 0.1))                      # PD:721
+    steps = _cov_steps(steps, num_pd_steps)
+    if total_size * total_size * num_repeats >= 1 << 63:
+        raise ValueError("total_size^2 * num_repeats = %d^2 * %d >= 2^63: the 64-bit sums of the Gram matrices could overflow"
+                         % (total_size, num_repeats))
+    device = _device(device)
+    dist, rank, world = _dist()
+    nd = len(doping_points)
+    p = E.CodeParams(l_deg, r_deg, L, cpp, M)
+    total_generated = (L - nd) * M                                         # PD:747
+    kind = _pick_choice(p, total_size, "philox", "protograph" if is_protograph else "olmos", "rows", pick)
+    plrs = np.zeros(num_repeats)
+    if batch is None:                                                      # simulate_peeling_decoder_ldpc's budget, rows wanted
+        per_trial = 3 * L * M * l_deg * 4 + 4 * (num_pd_steps + 1)
+        batch = max(64, min(8192, int(min(16e9 + 24e9, 0.6 * _free_bytes(device)) // per_trial)))
+    offs = _split(num_repeats, world)
+    moments = torch.zeros((3, num_pd_steps + 1), dtype=torch.int64, device=device)
+    gram = torch.zeros((3, steps.size, steps.size), dtype=torch.int64, device=device)
+    d_steps = torch.from_numpy(steps.astype(np.int32)).to(device)
+    for done in range(offs[rank], offs[rank + 1], batch):
+        nb = min(batch, offs[rank + 1] - done)
+        d_adj, d_ch = E.sample_philox(p, seed, done, nb, e, list(doping_points), device=device,
+                                      adj16=not is_protograph, ensemble="protograph" if is_protograph else "olmos")
+        if kind == "multi":
+            res = E.peel_pick_deg(p, d_adj, d_ch, total_size, num_pd_steps, seed=seed, trial0=done, want_r1=True)
+        else:
+            res = E.peel_pick(p, d_adj, d_ch, total_size, num_pd_steps, mt_state=None, seed=seed, trial0=done,
+                              want_r1=True, moments=None)
+        E.r1_moments(res["r1"], moments)
+        E.r1_gram(res["r1"], d_steps, gram)
+        res["r1"] = None
+        o = res["out"].cpu().numpy()
+        plrs[done:done + nb] = (o[:, 0] - o[:, 1]) / total_generated
+    if world > 1:                                           # shares are disjoint: a sum puts them together
+        t_plr = torch.from_numpy(plrs).to(device)
+        dist.all_reduce(t_plr)
+        plrs = t_plr.cpu().numpy()
+        dist.all_reduce(moments)
+        dist.all_reduce(gram)
+    return steps, gram.cpu().numpy(), moments.cpu().numpy(), plrs
+
+
 # simulate_peeling_decoder_ldpc_uncoupled(rng="philox"): the default batch keeps the expected attempts of one sampler launch,
 # batch * exp((l-1)(r-1)/2), below this — about a second of scldpc_sample_philox_uncoupled_device at (4,8), M = 1000.
 # Measured on MI355X (tools/uncoupled_speedup.py, profiles/uncoupled_speedup.json, taken with 1 << 24 here and --hard-trials 512):
@@ -755,6 +841,39 @@ def nu_chunk_from_moments(moments, r1s_theory, M):
     return (a.astype(np.float64) - 2.0 * f * b + cnt * f * f) / (float(M) * float(M)), cnt
 
 
+def cov_from_gram(gram):
+    """(cov float64 [K, K], counts int64 [K, K]) from the integer Gram matrices of simulate_pd_covariance / engine.r1_gram:
+    over the trials in which both steps are still decoding (calc_nu_chunk's mask, carried over to pairs; counts = gram[0]),
+    cov[i][j] = g2/g0 − (g1[i][j]/g0)·(g1[j][i]/g0), nan where counts == 0.  Nothing cancels: with n = g0, a = g1[i][j],
+    b = g1[j][i], s = g2 and the integers ki ≈ a/n, kj ≈ b/n (nu_chunk_from_moments's integer-plus-fraction split, per pair),
+    s' = Σ(x_i − ki)(x_j − kj) = s − ki·b − kj·a + n·ki·kj, a' = a − n·ki and b' = b − n·kj are exact in 64-bit integers
+    (|s'| <= n·max(x)², below 2⁶³ under simulate_pd_covariance's size check), and cov = (n·s' − a'·b') / n² has an exact integer numerator — formed in
+    int64 where it fits, in Python integers where it does not — so trajectories that sit close to a constant lose no digits."""
+    g = np.asarray(gram)
+    if g.ndim != 3 or g.shape[0] != 3 or g.shape[1] != g.shape[2] or not np.issubdtype(g.dtype, np.integer):
+        raise ValueError("gram must be an integer array [3, K, K]")
+    g = g.astype(np.int64)
+    n, a, b, s = g[0], g[1], g[1].T, g[2]
+    ok = n > 0
+    n1 = np.where(ok, n, 1)
+    ki = np.rint(a / n1).astype(np.int64)
+    kj = np.rint(b / n1).astype(np.int64)
+    with np.errstate(over="ignore"):
+        # wrapping int64 arithmetic: the intermediate products may leave 64 bits, the results do not
+        s_ = s - ki * b - kj * a + n * ki * kj
+        a_ = a - n * ki
+        b_ = b - n * kj
+    nf = n1.astype(np.float64)
+    fits = np.abs(nf * s_.astype(np.float64)) + np.abs(a_.astype(np.float64) * b_.astype(np.float64)) < 2.0 ** 62
+    num = np.where(fits, n * s_ - a_ * b_, 0).astype(np.float64)
+    cov = num / (nf * nf)
+    for i, j in zip(*np.nonzero(ok & ~fits)):                              # rare: Python integers, correctly rounded division
+        nn = int(n[i, j])
+        cov[i, j] = (nn * int(s_[i, j]) - int(a_[i, j]) * int(b_[i, j])) / (nn * nn)
+    cov[~ok] = np.nan
+    return cov, n.copy()
+
+
 class _ArraysOnly(pickle.Unpickler):
     """The theory file is a pickle of numpy arrays (NB cell 20); nothing else is allowed to load."""
     _OK = {("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
@@ -814,7 +933,8 @@ def _cli_options(args, kw):
     `--rng philox|numpy`, `--seed S`, `--batch B`, `--device D` — the keyword arguments of the simulators (throughput mode:
     device sampling, trials sharded over the ranks of a torch.distributed.run job) — `--sweep first|small|wide|auto` and
     `--local-tables on|off|auto` (local_tables=True | False | None), which only ber_sim (simulate_sc_ldpc) takes, and
-    `--pick first|multi|auto`, which only simulate_variance (simulate_peeling_decoder_ldpc) takes."""
+    `--pick first|multi|auto`, which only simulate_variance (simulate_peeling_decoder_ldpc) and simulate_covariance
+    (simulate_pd_covariance) take."""
     kw, pos, it = dict(kw), [], iter(args)
     for x in it:
         if isinstance(x, str) and x == "--local-tables":
@@ -942,6 +1062,42 @@ def _main_simulate_variance(a, kw):
     return ssquares, counts
 
 
+def main_simulate_covariance(argv=None, **kw):
+    """simulate_covariance: OUT l r L M e T|N U|P num_runs STRIDE [--seed S --batch B --device D --pick first|multi|auto]:
+    simulate_pd_covariance at every STRIDE-th step; rank 0 writes pickle.dump((steps, gram, moments, plrs)), numpy arrays
+    only.  Philox mode only, sharded over the ranks of a torch.distributed.run job."""
+    a, kw = _cli_options(sys.argv if argv is None else [None] + list(argv), kw)
+    if kw.get("rng", "philox") != "philox":
+        raise SystemExit("--rng %s: simulate_covariance runs in Philox mode only (the reference's host stream is sequential; its "
+                         "rows can be fed to engine.r1_gram by hand)" % kw["rng"])
+    if "sweep" in kw:
+        raise SystemExit("--sweep chooses the sweep decoder of ber_sim (simulate_sc_ldpc): simulate_covariance runs the "
+                         "random-pick decoder and takes no such option")
+    if "local_tables" in kw:
+        raise SystemExit("--local-tables chooses the tables of ber_sim's sweep decoder (simulate_sc_ldpc): simulate_covariance "
+                         "runs the random-pick decoder and takes no such option")
+    if len(a) != 11:
+        raise SystemExit("simulate_covariance takes OUT l r L M e T|N U|P num_runs STRIDE (got %d arguments)" % (len(a) - 1))
+    joined = _join_job(dict(kw, rng="philox"))
+    try:
+        return _main_simulate_covariance(a, {k: v for k, v in kw.items() if k != "rng"})
+    finally:
+        if joined:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+
+
+def _main_simulate_covariance(a, kw):
+    fname, l, r, L, M, e = a[1], int(a[2]), int(a[3]), int(a[4]), int(a[5]), float(a[6])
+    is_terminated, is_protograph = a[7] == "T", a[8] == "P"
+    num_runs, stride = int(a[9]), int(a[10])
+    out = simulate_pd_covariance(e, l, r, L, M, is_terminated, is_protograph, num_runs, stride, **kw)
+    if _dist()[1] == 0:                                                     # every rank holds the same sums: rank 0 writes
+        with open(fname, "wb") as f:
+            pickle.dump(tuple(np.asarray(x) for x in out), f)
+    return out
+
+
 def test_sc_ldpc(l=4, r=8, L=50, M=10000, e=0.48, is_terminated=False, num_runs=100, num_runs_batch=100,
                  out_pattern="r1_sc_ldpc_{l}_{r}_{L}_{M}_{etag}_{term}_{i}.pkl", **kw):
     """`python3 peeling_decoding.py` (PD:1212-1245): batches of trajectories pickled as (r1, plrs)."""
@@ -959,5 +1115,7 @@ if __name__ == "__main__":
         main_simulate_sc_ldpc(sys.argv[2:])
     elif prog == "simulate_variance":
         main_simulate_variance(sys.argv[2:])
+    elif prog == "simulate_covariance":
+        main_simulate_covariance(sys.argv[2:])
     else:
         test_sc_ldpc()
