@@ -79,6 +79,12 @@ EXPORTS_UNCOUPLED_WIDE = ("scldpc_sample_philox_uncoupled_wide_supported", "scld
 EXPORTS_COV = ("scldpc_r1_gram_workspace_bytes", "scldpc_r1_gram_trial_splits", "scldpc_r1_gram_device")
 COV_MAX_STEPS = 4096            # SCLDPC_COV_MAX_STEPS
 
+# every symbol the extension header include/scldpc_ss.h declares (the same shared object; tests/test_ss_host.py)
+EXPORTS_SS = ("scldpc_ss_spectrum_form", "scldpc_ss_spectrum_workspace_bytes", "scldpc_ss_spectrum_device")
+SS_MAX_BINS = 4096              # SCLDPC_SS_MAX_BINS
+SS_POS_SIZES = 8                # SCLDPC_SS_POS_SIZES
+SS_BAD_CN = 1                   # SCLDPC_SS_BAD_CN
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -207,6 +213,10 @@ def lib():
     L.scldpc_r1_gram_trial_splits.argtypes = [i32, i32]
     L.scldpc_r1_gram_trial_splits.restype = i32
     L.scldpc_r1_gram_device.argtypes = [i32, i32, vp, i32, vp, vp, vp, i64, vp]
+    L.scldpc_ss_spectrum_form.argtypes = [pp]
+    L.scldpc_ss_spectrum_workspace_bytes.argtypes = [pp, i32]
+    L.scldpc_ss_spectrum_workspace_bytes.restype = i64
+    L.scldpc_ss_spectrum_device.argtypes = [pp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp]
     L.scldpc_swc_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_swc_bp_device_adj16.argtypes = L.scldpc_swc_bp_device.argtypes
     L.scldpc_stream_supported.argtypes = [pp, i32]

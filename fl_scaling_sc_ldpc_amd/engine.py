@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import (CodeParams, MAX_CAPS, NCOUNTERS, NRUN, NPEELRUN, COUNTER_NAMES, RUN_NAMES, PEELRUN_NAMES, ScldpcError,  # noqa: F401
-                   check, lib)
+                   SS_MAX_BINS, SS_POS_SIZES, check, lib)
 
 
 def make_params(dv=4, dc=8, L=50, N=1000):
@@ -849,6 +849,53 @@ def r1_gram(d_r1, steps, gram=None):
             raise ScldpcError("r1_gram: a step lies outside [0, %d): the kernel clamped it (status %d) and `gram` holds the "
                               "sums of the clamped columns" % (ncols, status))
     return gram
+
+
+def ss_spectrum_form(p):
+    """Where ss_spectrum keeps its union-find state for ensemble p: 1 = in LDS, 2 = in its workspace
+    (scldpc_ss_spectrum_form; SCLDPC_DEBUG_SS_FORCE_WORKSPACE=1 sends every shape to 2).  Needs no device."""
+    form = lib().scldpc_ss_spectrum_form(C.byref(p))
+    if form < 0:
+        check(int(form))
+    return int(form)
+
+
+def ss_spectrum(p, d_adj, d_members, nbins, hist=None, pos_hist=None, want_trial=False):
+    """scldpc_ss_spectrum_device: the connected components (through every shared CN, pd_oracle.components) of the VNs whose
+    bits are set in d_members int32 [T, nw] — a sweep decoder's `lost`, full BP's `erased`, or any subset — one trial per
+    row.  d_adj: int32 [T, n, dv] global CN ids (any ensemble) or int16 [T, n, dv] position-local ids (the chains' 2-byte rows).
+    Accumulates into hist int64 [nbins] (hist[0] += trials without a member, hist[min(s, nbins - 1)] += 1 per component of s
+    VNs) and pos_hist int64 [L, 8] ([q, min(s, 8) - 1] += 1, q the position of the component's lowest-index member), zeros
+    where None; want_trial: also int32 [T, 4] = (components, largest size, members, members in components of more than 2).
+    Returns {"hist", "pos_hist", "trial"}.  A CN id outside [0, ncn) is skipped, never used as an index, and flagged in the
+    status word, which is read back here (one synchronisation) and raised as RuntimeError."""
+    _require_gpu()
+    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous() and tuple(d_adj.shape[1:]) == (p.n, p.dv)
+    T = d_adj.shape[0]
+    assert d_members.is_cuda and d_members.dtype == torch.int32 and d_members.is_contiguous() and tuple(d_members.shape) == (T, p.nw)
+    dev = d_adj.device
+    nbins = int(nbins)
+    if hist is None:
+        hist = torch.zeros((max(nbins, 0),), dtype=torch.int64, device=dev)
+    if pos_hist is None:
+        pos_hist = torch.zeros((p.L, _lib.SS_POS_SIZES), dtype=torch.int64, device=dev)
+    assert hist.is_cuda and hist.dtype == torch.int64 and tuple(hist.shape) == (nbins,) and hist.is_contiguous()
+    assert pos_hist.is_cuda and pos_hist.dtype == torch.int64 and tuple(pos_hist.shape) == (p.L, _lib.SS_POS_SIZES) and pos_hist.is_contiguous()
+    nbytes = lib().scldpc_ss_spectrum_workspace_bytes(C.byref(p), T)
+    if nbytes < 0:
+        check(int(nbytes))
+    ws = _uninit(int(nbytes), dtype=torch.uint8, device=dev)
+    trial = _uninit((T, 4), dtype=torch.int32, device=dev) if want_trial else None
+    check(lib().scldpc_ss_spectrum_device(C.byref(p), T, d_adj.data_ptr(), 1 if _is_adj16(d_adj) else 0, d_members.data_ptr(),
+                                          nbins, hist.data_ptr(), pos_hist.data_ptr(),
+                                          trial.data_ptr() if trial is not None else None, ws.data_ptr(), int(nbytes),
+                                          _stream_ptr(dev)))
+    if T > 0:
+        status = int(ws[:4].view(torch.int32).item())
+        if status & _lib.SS_BAD_CN:
+            raise RuntimeError("ss_spectrum: a CN id lies outside [0, %d): the kernel skipped that edge (status %d, SS_BAD_CN) "
+                               "and the sums hold the components without it" % (p.nk, status))
+    return {"hist": hist, "pos_hist": pos_hist, "trial": trial}
 
 
 # ------------------------------------------------------------------------------------------------

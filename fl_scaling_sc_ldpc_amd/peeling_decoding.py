@@ -347,6 +347,15 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
     (sample_philox_ens_sock16; ValueError("local_tables=True: ...") for the Olmos chain, whose tables are position-local
     already, for a sweep that resolves to "first", for rng="numpy" and for a shape the sampler or the decoder refuses), False =
     never, None = what LOCAL_TABLES_BY_DEFAULT says."""
+    return _simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats, max_fuckups,
+                             doping_points, rng, seed, batch, device, sweep, local_tables, None)[0]
+
+
+def _simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats, max_fuckups,
+                      doping_points, rng, seed, batch, device, sweep, local_tables, nbins):
+    """The one round loop of simulate_sc_ldpc and simulate_sc_ldpc_spectrum: (tuple13, hist, pos_hist).  nbins None: the
+    calls simulate_sc_ldpc has always made and (tuple13, None, None); else every decoder also writes its lost bits and
+    engine.ss_spectrum runs over exactly the trials the stop rule used."""
     _check_flags(is_protograph, is_tail_biting)
     device = _device(device)
     dist, rank, world = _dist()
@@ -358,8 +367,21 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
     kind, small_sampler = _sweep_choice(p, rng, ens, sweep, local_tables)
     # whose tables the decoder reads: passed on only where it is not the Olmos chain's (sample_philox_ens_sock16)
     ens_kw = {"ensemble": ens} if small_sampler == "sample_philox_ens_sock16" and kind != "first" else {}
+    if nbins is not None and ens == "tail_biting" and ens_kw:
+        raise ValueError(_SPECTRUM_RING)
     if batch is None:
         batch = 64 if rng == "numpy" else 2048
+    # the spectrum pass reads the lost bits: asked for only there, so that simulate_sc_ldpc's calls are what they were
+    lost_kw = {"want_lost": True} if nbins is not None else {}
+    hist = pos_hist = None
+    if nbins is not None:
+        hist = torch.zeros(nbins, dtype=torch.int64, device=device)
+        pos_hist = torch.zeros((p.L, E.SS_POS_SIZES), dtype=torch.int64, device=device)
+
+    def spectrum(d_adj, d_lost, take):
+        """The trials [0, take) of this rank's share of the round: those the stop rule used."""
+        if nbins is not None and take > 0:
+            E.ss_spectrum(p, d_adj[:take], d_lost[:take], nbins, hist, pos_hist)
     # The reference's per-trial bookkeeping and its stop rule (PD:668-699) run on the device, in trial order
     # (scldpc_accumulate_peel_device): the host reads the six totals only in rounds in which max_fuckups could trip.
     run = torch.zeros(E.NPEELRUN, dtype=torch.int64, device=device)
@@ -396,11 +418,12 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
         else:
             raise ValueError("rng must be 'numpy' or 'philox'")
         if kind == "small":
-            d_out = E.peel_sweep_sock16(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi, **ens_kw)["out"]
+            res = E.peel_sweep_sock16(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi, **lost_kw, **ens_kw)
         elif kind == "wide":
-            d_out = E.peel_sweep_sock16_wide(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi, **ens_kw)["out"]
+            res = E.peel_sweep_sock16_wide(p, d_adj, d_cn, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi, **lost_kw, **ens_kw)
         else:
-            d_out = E.peel_sweep(p, d_adj, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi)["out"]
+            res = E.peel_sweep(p, d_adj, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi, **lost_kw)
+        d_out, d_lost = res["out"], res.get("lost")
         if world > 1:
             m = max(offs[r + 1] - offs[r] for r in range(world))
             pad = torch.zeros((m, d_out.shape[1]), dtype=d_out.dtype, device=d_out.device)
@@ -412,11 +435,13 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
         fuckups_bound += nb
         if fuckups_bound < max_fuckups and states is None:
             done += nb                                      # cannot have tripped: stay asynchronous
+            spectrum(d_adj, d_lost, mine)
             continue
         tot = run.cpu().numpy()
         used = int(tot[i_tr]) - done
         fuckups_bound = int(tot[i_fu])
         done += used
+        spectrum(d_adj, d_lost, min(max(used - lo, 0), mine))
         if used < nb or tot[i_fu] >= max_fuckups:
             if states is not None:
                 np.random.set_state(states[used - 1])       # leave the stream where the reference stops drawing
@@ -428,10 +453,38 @@ def simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is
     total_generated, total_blocks_generated = done * g.generated, done * g.blocks
     o1 = done
     failures, gens = np.zeros(num_repeats), np.zeros(num_repeats)
-    return (num_fuckups / o1, num_fuckups_truncated / o1, total_failed / total_generated,
-            total_failed_expurgated / total_generated, num_fuckups_truncated, o1, total_failed_expurgated,
-            total_generated, failures, gens, total_blocks_failed_exp, total_blocks_generated,
-            total_blocks_failed_exp / total_blocks_generated)
+    tuple13 = (num_fuckups / o1, num_fuckups_truncated / o1, total_failed / total_generated,
+               total_failed_expurgated / total_generated, num_fuckups_truncated, o1, total_failed_expurgated,
+               total_generated, failures, gens, total_blocks_failed_exp, total_blocks_generated,
+               total_blocks_failed_exp / total_blocks_generated)
+    if nbins is None:
+        return tuple13, None, None
+    if world > 1:                                           # integer sums: one all-reduce, the same arrays on every rank
+        dist.all_reduce(hist)
+        dist.all_reduce(pos_hist)
+    return tuple13, hist.cpu().numpy(), pos_hist.cpu().numpy()
+
+
+_SPECTRUM_RING = ("spectrum: a tail-biting run on position-local tables (local_tables) has ring-local 2-byte rows, a table form "
+                  "engine.ss_spectrum does not read: pass local_tables=False")
+
+
+def simulate_sc_ldpc_spectrum(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats=int(1e5),
+                              max_fuckups=2000, doping_points=[], rng="numpy", seed=0, batch=None, device=None, sweep="auto",
+                              local_tables=None, nbins=256):
+    """simulate_sc_ldpc with the size spectrum of the stopping sets it leaves behind (extract_stopping_sets, PD:1077-1095, on
+    the device: engine.ss_spectrum on every round's lost bits).  Returns (tuple13, hist, pos_hist) as numpy arrays: tuple13 is
+    value for value simulate_sc_ldpc's for the same arguments; hist int64 [nbins] counts, over exactly the o1 = tuple13[5]
+    trials of the tuple, hist[0] = trials that lost nothing and hist[min(s, nbins - 1)] = stopping sets of s VNs; pos_hist int64
+    [L', 8] counts them by the position of their lowest-index VN (L' the widened L of the run) and min(s, 8) - 1.  Under
+    torch.distributed every rank returns the same sums.  2 <= nbins <= 4096 (ValueError); a tail-biting run with
+    local_tables=True raises ValueError("spectrum: ...")."""
+    if not (isinstance(nbins, (int, np.integer)) and 2 <= nbins <= E.SS_MAX_BINS):
+        raise ValueError("spectrum: 2 <= nbins <= %d (got %r)" % (E.SS_MAX_BINS, nbins))
+    if is_tail_biting and local_tables is True:
+        raise ValueError(_SPECTRUM_RING)
+    return _simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats, max_fuckups,
+                             doping_points, rng, seed, batch, device, sweep, local_tables, int(nbins))
 
 
 # Whether simulate_peeling_decoder_ldpc(pick="auto") takes engine.peel_pick_deg (the CN words through cn_build.hip's LDS ring,
@@ -934,7 +987,7 @@ def _cli_options(args, kw):
     device sampling, trials sharded over the ranks of a torch.distributed.run job) — `--sweep first|small|wide|auto` and
     `--local-tables on|off|auto` (local_tables=True | False | None), which only ber_sim (simulate_sc_ldpc) takes, and
     `--pick first|multi|auto`, which only simulate_variance (simulate_peeling_decoder_ldpc) and simulate_covariance
-    (simulate_pd_covariance) take."""
+    (simulate_pd_covariance) take, and `--nbins N`, which only stopping_sets (simulate_sc_ldpc_spectrum) takes."""
     kw, pos, it = dict(kw), [], iter(args)
     for x in it:
         if isinstance(x, str) and x == "--local-tables":
@@ -942,7 +995,7 @@ def _cli_options(args, kw):
             if v not in ("on", "off", "auto"):
                 raise SystemExit("--local-tables takes on, off or auto (got %r)" % (v,))
             kw["local_tables"] = {"on": True, "off": False, "auto": None}[v]
-        elif isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device", "--sweep", "--pick"):
+        elif isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device", "--sweep", "--pick", "--nbins"):
             v = next(it)
             if x == "--sweep" and v not in ("first", "small", "wide", "auto"):
                 raise SystemExit("--sweep takes first, small, wide or auto (got %r)" % (v,))
@@ -971,9 +1024,31 @@ def main_simulate_sc_ldpc(argv=None, **kw):
     if "pick" in kw:
         raise SystemExit("--pick chooses the random-pick decoder of simulate_variance (simulate_peeling_decoder_ldpc): ber_sim "
                          "runs the sweep decoder and takes no such option")
+    if "nbins" in kw:
+        raise SystemExit(_NBINS_ELSEWHERE % "ber_sim")
     joined = _join_job(kw)
     try:
         return _main_simulate_sc_ldpc(a, kw)
+    finally:
+        if joined:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+
+
+_NBINS_ELSEWHERE = "--nbins sizes the histogram of stopping_sets (simulate_sc_ldpc_spectrum): %s takes no such option"
+
+
+def main_stopping_sets(argv=None, **kw):
+    """stopping_sets: ber_sim's command line, OUT l r L M "es" T|N U|P B|N TB|NTB num_repeats max_fuckups "doping", and its
+    options, plus `--nbins N` (256): for every e the row ber_sim would write goes to OUT, and rank 0 pickles
+    (es, hist [E][nbins], pos_hist [E][L'][8]) to OUT + ".spectrum.pkl", numpy arrays only (simulate_sc_ldpc_spectrum)."""
+    a, kw = _cli_options(sys.argv if argv is None else [None] + list(argv), kw)
+    if "pick" in kw:
+        raise SystemExit("--pick chooses the random-pick decoder of simulate_variance (simulate_peeling_decoder_ldpc): "
+                         "stopping_sets runs the sweep decoder and takes no such option")
+    joined = _join_job(kw)
+    try:
+        return _main_simulate_sc_ldpc(a, kw, spectrum=True)
     finally:
         if joined:
             import torch.distributed as dist
@@ -998,7 +1073,7 @@ class _Tee:
             self.f.close()
 
 
-def _main_simulate_sc_ldpc(a, kw):
+def _main_simulate_sc_ldpc(a, kw, spectrum=False):
     fname, l, r, L, M = a[1], int(a[2]), int(a[3]), int(a[4]), int(a[5])
     es = _safe_eval(a[6])
     is_terminated, is_protograph = a[7] == "T", a[8] == "P"
@@ -1010,15 +1085,25 @@ def _main_simulate_sc_ldpc(a, kw):
             f"tail biting:{is_tail_biting}. num_repeats={num_repeats}, max_fuckups={max_fuckups}, "
             f"doping_points={doping_points}.")
     out = _Tee(fname, _dist()[1] == 0)
+    es = list(es if isinstance(es, (list, np.ndarray, range)) else [es])
+    hists, pos_hists = [], []
     try:
         out.line(head)
-        for e in (es if isinstance(es, (list, np.ndarray, range)) else [es]):
-            ber, ber_truncated, plr, plr_exp, fbl, tbl, fbit, tgen, _flrs, _gens, fblocks, tblocks, bler = \
-                simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats,
-                                 max_fuckups, doping_points, **kw)
+        for e in es:
+            args = (e, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats, max_fuckups, doping_points)
+            if spectrum:
+                tuple13, hist, pos_hist = simulate_sc_ldpc_spectrum(*args, **kw)
+                hists.append(hist)
+                pos_hists.append(pos_hist)
+            else:
+                tuple13 = simulate_sc_ldpc(*args, **kw)
+            ber, ber_truncated, plr, plr_exp, fbl, tbl, fbit, tgen, _flrs, _gens, fblocks, tblocks, bler = tuple13
             out.line(e, ber, ber_truncated, plr, plr_exp, fbl, tbl, fbit, tgen, fblocks, tblocks, bler)
     finally:
         out.close()
+    if spectrum and _dist()[1] == 0:                                        # every rank holds the same sums: rank 0 writes
+        with open(fname + ".spectrum.pkl", "wb") as f:
+            pickle.dump((np.asarray(es, dtype=np.float64), np.stack(hists), np.stack(pos_hists)), f)
 
 
 def main_simulate_variance(argv=None, **kw):
@@ -1031,6 +1116,8 @@ def main_simulate_variance(argv=None, **kw):
     if "local_tables" in kw:
         raise SystemExit("--local-tables chooses the tables of ber_sim's sweep decoder (simulate_sc_ldpc): simulate_variance runs "
                          "the random-pick decoder and takes no such option")
+    if "nbins" in kw:
+        raise SystemExit(_NBINS_ELSEWHERE % "simulate_variance")
     joined = _join_job(kw)
     try:
         return _main_simulate_variance(a, kw)
@@ -1076,6 +1163,8 @@ def main_simulate_covariance(argv=None, **kw):
     if "local_tables" in kw:
         raise SystemExit("--local-tables chooses the tables of ber_sim's sweep decoder (simulate_sc_ldpc): simulate_covariance "
                          "runs the random-pick decoder and takes no such option")
+    if "nbins" in kw:
+        raise SystemExit(_NBINS_ELSEWHERE % "simulate_covariance")
     if len(a) != 11:
         raise SystemExit("simulate_covariance takes OUT l r L M e T|N U|P num_runs STRIDE (got %d arguments)" % (len(a) - 1))
     joined = _join_job(dict(kw, rng="philox"))
@@ -1117,5 +1206,7 @@ if __name__ == "__main__":
         main_simulate_variance(sys.argv[2:])
     elif prog == "simulate_covariance":
         main_simulate_covariance(sys.argv[2:])
+    elif prog == "stopping_sets":
+        main_stopping_sets(sys.argv[2:])
     else:
         test_sc_ldpc()
