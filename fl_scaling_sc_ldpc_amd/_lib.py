@@ -85,6 +85,13 @@ SS_MAX_BINS = 4096              # SCLDPC_SS_MAX_BINS
 SS_POS_SIZES = 8                # SCLDPC_SS_POS_SIZES
 SS_BAD_CN = 1                   # SCLDPC_SS_BAD_CN
 
+# every symbol the extension header include/scldpc_runs.h declares (the same shared object; tests/test_runs_host.py)
+EXPORTS_RUNS = ("scldpc_chain_runs_device", "scldpc_stream_runs_device")
+RUNS_MAX_L = 1024               # SCLDPC_RUNS_MAX_L
+RUNS_MAX_BINS = 4096            # SCLDPC_RUNS_MAX_BINS
+RUNS_MAX_PERIOD = 4096          # SCLDPC_RUNS_MAX_PERIOD
+RUNS_CARRY = 8                  # SCLDPC_RUNS_CARRY
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -217,6 +224,8 @@ def lib():
     L.scldpc_ss_spectrum_workspace_bytes.argtypes = [pp, i32]
     L.scldpc_ss_spectrum_workspace_bytes.restype = i64
     L.scldpc_ss_spectrum_device.argtypes = [pp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp]
+    L.scldpc_chain_runs_device.argtypes = [pp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.scldpc_stream_runs_device.argtypes = [pp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     L.scldpc_swc_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_swc_bp_device_adj16.argtypes = L.scldpc_swc_bp_device.argtypes
     L.scldpc_stream_supported.argtypes = [pp, i32]

@@ -51,12 +51,18 @@ one launch, instead of the first-generation sampler and its table pass; same fil
 draws the code and writes the CN -> socket table in one launch, instead of the first-generation sampler and its table pass; same
 files.
 
+`--runs` (bp_lim_iter, also with --window classical; sw_lim_iter; sw): the error-propagation statistics of the frames each ε point
+consumed — where the failed positions sit and how long their runs are (engine.chain_runs over the decoder's erased bits), for `sw`
+runs, events, gaps, time to first failure and the error rate by offset in the doping period (engine.StreamRuns over the trace) —
+pickled by rank 0 as one dict per ε point beside the result file (`<file>.runs.pkl`), which itself is written as without the switch.
+
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
 import collections
 import copy
 import os
+import pickle
 import sys
 import time
 
@@ -97,6 +103,25 @@ DEFAULTS = {
 }
 
 
+def runs_shapes(L):
+    """Names and shapes of the error-propagation accumulators of one ε point (engine.chain_runs), in the order in which they
+    are flattened for an all-reduce."""
+    return (("pos", (L, 4)), ("run_hist", (L + 1, 2)), ("fail_hist", (L + 1,)))
+
+
+def runs_unflatten(L, flat):
+    out, at = {}, 0
+    for name, shape in runs_shapes(L):
+        k = int(np.prod(shape))
+        out[name] = np.array(flat[at:at + k], dtype=np.int64).reshape(shape)
+        at += k
+    return out
+
+
+def runs_flatten(L, runs):
+    return np.concatenate([np.asarray(runs[name], dtype=np.int64).reshape(-1) for name, _ in runs_shapes(L)])
+
+
 def _dist():
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
@@ -107,8 +132,9 @@ def _dist():
 class PointResult:
     """Counters of one ε point after the stop rule, as `risultati` needs them (BPF:499-515)."""
 
-    def __init__(self, eps, n, L, run, bad=False):
+    def __init__(self, eps, n, L, run, bad=False, runs=None):
         self.eps, self.n, self.L = eps, n, L
+        self.runs = runs                # Simulator(runs=True): {"pos", "run_hist", "fail_hist"} of the point's frames, numpy
         self.run = {k: int(v) for k, v in zip(RUN_NAMES, run)}
         self.f = self.run["frames"]
         self.bad = bool(bad)            # a frame broke decodeBP's invariant (BPF:1035-1039): the reference aborts there
@@ -472,7 +498,12 @@ class Simulator:
     def __init__(self, p, decoder="full", W=0, max_it=0, init_it=0, is_term=True, doped=(), batch=2048,
                  rng="philox", seed=1, device=None, rows_cap=0, schedule="flooding", shard_frames=True, index=0,
                  verbose=False, caps=None, wide=None, deg=None, ring=None, fused_caps=None, sampled_table=None,
-                 sampler2=None, sampler2_wide=None):
+                 sampler2=None, sampler2_wide=None, runs=False):
+        # runs: every point also returns the error-propagation statistics of its frames (engine.chain_runs over the decoder's
+        # erased bits): PointResult.runs.  The cap checkpoints keep no erased bits
+        self.runs = bool(runs)
+        if self.runs and caps is not None:
+            raise ValueError("runs=True: the cap checkpoints of one decode (caps) keep no erased bits; run one cap at a time")
         # wide: the 1024-thread 4-bit level decoder for trials of more than 65536 CNs (full_bp_small wide).  None = where
         # WIDE_BY_DEFAULT says, True = wherever it applies, False = never (the first-generation path, for A/B and tests)
         self.want_wide = wide
@@ -609,32 +640,34 @@ class Simulator:
     # -- one device batch ------------------------------------------------------------------------
     def decode_batch(self, nb, want_rows=False):
         path, adj, ch, cnt = self.path, self.d_adj[:nb], self.d_ch[:nb], self.d_cnt[:nb]
+        er = {"want_erased": True} if self.runs else {}                 # (without runs every call is what it was)
         if path.decoder in ("sw_ring", "sw_chain"):
             return E.sw_bp(self.p, adj, ch, self.W, self.max_it, self.init_it, counters=cnt,
                            d_cn_sock=self.d_cn[:nb] if path.cn_table is not None else None,
-                           ring=True if self.ring_deg else None, deg=self.ring_deg)
+                           ring=True if self.ring_deg else None, deg=self.ring_deg, **er)
         if path.decoder in ("swc_ring", "swc_chain"):
             return E.sw_bp(self.p, adj, ch, self.W, self.max_it, counters=cnt, classical=True, ring=path.decoder == "swc_ring",
-                           d_cn_sock=self.d_cn[:nb] if path.cn_table is not None else None)
+                           d_cn_sock=self.d_cn[:nb] if path.cn_table is not None else None, **er)
         # the fixpoint kernels report neither iteration counts nor rows: a call that wants rows walks the iterations
         decoder = path.fix_decoder if (path.fix_decoder is not None and not want_rows) else path.decoder
         sockets, rows_cap = path.cn_table == "sock", self.rows_cap if want_rows else 0
         if decoder == "fixpoint16":
-            return E.full_bp_fixpoint_cn16(self.p, adj, self.d_cn[:nb], ch, is_term=self.is_term, counters=cnt, sockets=sockets)
+            return E.full_bp_fixpoint_cn16(self.p, adj, self.d_cn[:nb], ch, is_term=self.is_term, counters=cnt, sockets=sockets,
+                                           **er)
         if decoder == "level16":
             return E.full_bp_cn16(self.p, adj, self.d_cn[:nb], ch, max_it=self.max_it, is_term=self.is_term, counters=cnt,
-                                  sockets=sockets, rows_cap=rows_cap)
+                                  sockets=sockets, rows_cap=rows_cap, **er)
         if decoder == "fixpoint":
-            return E.full_bp_fixpoint(self.p, adj, ch, is_term=self.is_term, counters=cnt)    # no iteration counts
+            return E.full_bp_fixpoint(self.p, adj, ch, is_term=self.is_term, counters=cnt, **er)    # no iteration counts
         if decoder == "fixpoint_deg":
-            return E.full_bp_fixpoint_deg(self.p, adj, self.d_cn[:nb], ch, is_term=self.is_term, counters=cnt)
+            return E.full_bp_fixpoint_deg(self.p, adj, self.d_cn[:nb], ch, is_term=self.is_term, counters=cnt, **er)
         if decoder in ("deg16", "degwide"):
             return E.full_bp_deg(self.p, adj, self.d_cn[:nb], ch, max_it=self.max_it, is_term=self.is_term, rows_cap=rows_cap,
-                                 counters=cnt, wide=decoder == "degwide")
+                                 counters=cnt, wide=decoder == "degwide", **er)
         if decoder == "wide":
             return E.full_bp_wide(self.p, adj, self.d_cn[:nb], ch, max_it=self.max_it, is_term=self.is_term,
-                                  rows_cap=rows_cap, counters=cnt)
-        return E.full_bp(self.p, adj, ch, max_it=self.max_it, is_term=self.is_term, rows_cap=rows_cap, counters=cnt)
+                                  rows_cap=rows_cap, counters=cnt, **er)
+        return E.full_bp(self.p, adj, ch, max_it=self.max_it, is_term=self.is_term, rows_cap=rows_cap, counters=cnt, **er)
 
     def decode_batch_caps(self, nb):
         """The counters [K, nb, 8] of every cap of self.caps for the batch in place (one decode)."""
@@ -687,7 +720,10 @@ class Simulator:
         asynchronous.  on_batch(frame0, frames_used, result) sees this rank's batches.
         A frame that breaks decodeBP's invariant aborts the process as in the reference (BPF:1035-1039) — every rank of a
         frame-sharded job sees it in the gathered rows and leaves together; with defer_abort the point comes back with
-        .bad set instead, for callers whose other ranks are busy elsewhere and must be told first."""
+        .bad set instead, for callers whose other ranks are busy elsewhere and must be told first.
+        With runs=True the point's .runs holds engine.chain_runs over exactly the frames the point consumed — of every round
+        this rank's first max(0, min(nb, used_round - off)) trials, what on_batch is told — summed over the ranks of a
+        frame-sharded job by one all-reduce."""
         p, B, W = self.p, self.batch, self.world
         i_frames, i_ferr, i_status = RUN_NAMES.index("frames"), RUN_NAMES.index("frame_err"), \
             E.COUNTER_NAMES.index("status")
@@ -696,6 +732,7 @@ class Simulator:
         run = self._new_run()
         bad = torch.zeros((), dtype=torch.bool, device=run.device)
         frame0, consumed = 0, 0
+        racc = None
         while frame0 < max_frames:
             R, sizes, offs = self.split_round(max_frames - frame0, B, W)
             nb, off = sizes[self.rank], offs[self.rank]
@@ -726,6 +763,8 @@ class Simulator:
             bad |= (allcnt[:used_round, i_status] != 0).any()
             if on_batch is not None and nb:
                 on_batch(frame0 + off, max(0, min(nb, used_round - off)), res)
+            if self.runs and nb and used_round - off > 0:
+                racc = E.chain_runs(p, res["erased"][:min(nb, used_round - off)], acc=racc)
             if stopped and snap is not None and used_round < nb:
                 # the reference stops drawing at the tripping frame: rewind the stream to just after it
                 self.glibc.restore(snap)
@@ -735,7 +774,21 @@ class Simulator:
                 break
         if bool(bad) and not defer_abort:
             abort_invariant()
-        return PointResult(eps, p.n, p.L, run.cpu().numpy(), bad=bool(bad))
+        return PointResult(eps, p.n, p.L, run.cpu().numpy(), bad=bool(bad), runs=self._point_runs(racc, run.device))
+
+    def _point_runs(self, racc, device):
+        """run_point's .runs: the three accumulators as numpy arrays (zeros from a rank that decoded nothing), summed over the
+        ranks of a frame-sharded job; None without runs=True."""
+        if not self.runs:
+            return None
+        shapes = runs_shapes(self.p.L)
+        if racc is None:
+            flat = torch.zeros(sum(int(np.prod(sh)) for _, sh in shapes), dtype=torch.int64, device=device)
+        else:
+            flat = torch.cat([racc[name].reshape(-1) for name, _ in shapes])
+        if self.world > 1:
+            self.dist.all_reduce(flat)
+        return runs_unflatten(self.p.L, flat.cpu().numpy())
 
     def run_point_caps(self, sim, eps, min_frame_err, max_frames):
         """run_point for every cap of self.caps from one sampling pass and one decode per batch: one PointResult per cap,
@@ -1017,6 +1070,7 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
         shard = "points" if (world > 1 and grid.num_points >= world) else "frames"
     by_points = shard == "points" and world > 1
     replica = index + rank if shard == "replicas" else index
+    want_runs = _check_runs(prog, opts)
     if getattr(opts, "caps", None) and prog == "bp_lim_iter":
         return _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, shard, by_points)
     # the decoders' loop is do { … } while (iter < MaxNumIt) (BPF:1065, BPT:1076): at least one iteration runs
@@ -1032,11 +1086,21 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                         verbose=rank == 0 and not opts.quiet,
                         wide=_switch(opts, "wide"), deg=_switch(opts, "deg"), ring=ring if decoder in ("sw", "swc") else None,
                         sampled_table=_switch(opts, "sampled_table"), sampler2=_switch(opts, "sampler2"),
-                        sampler2_wide=_switch(opts, "sampler2_wide"))
+                        sampler2_wide=_switch(opts, "sampler2_wide"), **({"runs": True} if want_runs else {}))
     _check_sampler_switches(opts, sim_obj)
     outdir = opts.outdir
     os.makedirs(outdir, exist_ok=True)
     t0 = time.time()
+    runs_out = []                                                   # --runs: one dict per ε point, pickled by rank 0
+    nruns = sum(int(np.prod(sh)) for _, sh in runs_shapes(p.L))
+
+    def keep_runs(point):
+        runs_out.append(dict(eps=point.eps, frames=point.f, **point.runs))
+
+    def write_runs():
+        if want_runs and rank == 0:
+            with open(os.path.join(outdir, result_filename(prog, p, W, max_it, init_it, index)) + ".runs.pkl", "wb") as f:
+                pickle.dump(runs_out, f)
 
     def report(eps, point):
         if rank == 0 and not opts.quiet:
@@ -1055,24 +1119,34 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
         path = os.path.join(outdir, result_filename(prog, p, W, max_it, init_it, index))
         part = path + ".rank%d.part" % rank
         table = torch.zeros((grid.num_points, NRUN + 1), dtype=torch.int64, device=sim_obj.device)
+        rtable = torch.zeros((grid.num_points, nruns), dtype=torch.int64, device=sim_obj.device) if want_runs else None
         for sim in range(rank, grid.num_points, world):
             point = sim_obj.run_point(sim, grid.eps(sim), grid.min_frame_err, grid.max_frames, defer_abort=True)
             table[sim, :NRUN] = torch.tensor([point.run[k] for k in RUN_NAMES], dtype=torch.int64, device=sim_obj.device)
             table[sim, NRUN] = int(point.bad)
+            if want_runs:
+                rtable[sim] = torch.from_numpy(runs_flatten(p.L, point.runs)).to(sim_obj.device)
             with open(part, "a" if sim != rank else "w") as f:
                 f.write("%d %s" % (sim, point.row()))
             if point.bad:
                 break                                   # the reference's process is gone at this point
         dist.all_reduce(table)
+        if want_runs:
+            dist.all_reduce(rtable)                     # the stacked per-point accumulators, once, next to the table
+            rrows = rtable.cpu().numpy()
         rows = table.cpu().numpy()
         first_bad = next((s for s in range(grid.num_points) if rows[s, NRUN]), None)
         if rank == 0:
             for sim in range(grid.num_points if first_bad is None else first_bad):
-                pt = PointResult(grid.eps(sim), p.n, p.L, rows[sim, :NRUN])
+                pt = PointResult(grid.eps(sim), p.n, p.L, rows[sim, :NRUN],
+                                 runs=runs_unflatten(p.L, rrows[sim]) if want_runs else None)
                 if pt.f == 0:
                     break                               # a rank stopped at an abort before reaching this point
                 write_risultati(path, sim, pt)
+                if want_runs:
+                    keep_runs(pt)
                 report(pt.eps, pt)
+        write_runs()
         dist.barrier()
         if os.path.exists(part):
             os.remove(part)
@@ -1094,6 +1168,8 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
             point = sim_obj.run_point(sim, eps, grid.min_frame_err, grid.max_frames)
             if rank == 0:
                 write_risultati(os.path.join(outdir, result_filename(prog, p, W, max_it, init_it, index)), sim, point)
+            if want_runs:
+                keep_runs(point)
         if prog == "bp_traj" and world > 1:
             # the replicas run independently; an abort in one of them (BPF:1035-1039) ends the job for all, together
             flag = torch.tensor([int(point.bad)], dtype=torch.int64, device=sim_obj.device)
@@ -1101,6 +1177,7 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
             if int(flag.item()):
                 abort_invariant()
         report(eps, point)
+    write_runs()
     return 0
 
 
@@ -1116,6 +1193,16 @@ def _check_sampler_switches(opts, sim_obj):
                          ("sampled_table", "sampled_table_reason")):
         if getattr(opts, name, "auto") == "on" and getattr(sim_obj, reason) is not None:
             raise SystemExit("--%s on: %s" % (name.replace("_", "-"), getattr(sim_obj, reason)))
+
+
+def _check_runs(prog, opts):
+    """--runs against the rest of the command line: exits with the reason (before any device work); else whether it is set."""
+    want_runs = bool(getattr(opts, "runs", False))
+    if want_runs and prog == "bp_traj":
+        raise SystemExit("--runs: bp_traj writes trajectories, not block error rates; use bp_lim_iter or sw_lim_iter")
+    if want_runs and getattr(opts, "caps", None):
+        raise SystemExit("--runs: the cap checkpoints of --caps keep no erased bits; run one MAX_IT at a time")
+    return want_runs
 
 
 def _check_window(opts):
@@ -1211,6 +1298,10 @@ def _parser(prog):
                          "N = 5000), where the decoder reads a CN -> socket table: the wide second-generation sampler draws the "
                          "code and writes the table in one launch (on), the first-generation sampler and its table pass (off), or "
                          "the measured default (auto); same files.  'on' where it does not apply is an error that says why")
+    ap.add_argument("--runs", action="store_true",
+                    help="bp_lim_iter, sw_lim_iter: also write <result file>.runs.pkl, a pickled list with one dict per ε point "
+                         "{eps, frames, pos, run_hist, fail_hist}: where the failed positions of the point's frames sit and how "
+                         "long their runs are (engine.chain_runs; include/scldpc_runs.h); the .dat is unchanged.  Not with --caps")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")
@@ -1225,6 +1316,7 @@ def _parser(prog):
 
 def main(prog, argv=None):
     opts = _parser(prog).parse_args(argv)
+    _check_runs(prog, opts)
     if opts.seed is None:
         opts.seed = int((time.time() % 1) * 1e6)                      # te.tv_usec (BPF:2061)
     joined = E.init_distributed()                                     # one process per GPU under torch.distributed.run
@@ -1271,7 +1363,9 @@ def run_streaming(index, W, doped, opts):
     """main_streaming: per ε point, decode positions until num_blocks_err_exp >= max_blocks_err or
     num_blocks_generated_exp >= max_blocks (Def_MaxNumberBlocksError / Def_MaxNumberBlocksSim, BPF:41-42, 2033).
     The reference runs ONE stream; here `--streams` independent streams (× ranks) advance in lock step, `--chunk`
-    positions per launch, and their counters are summed — the stop rule is applied to the sums after every chunk."""
+    positions per launch, and their counters are summed — the stop rule is applied to the sums after every chunk.
+    opts.runs: every chunk is traced and fed to an engine.StreamRuns (with --rng glibc: the rows that count); rank 0 pickles one
+    dict per ε point into <stream file>.runs.pkl, the .dat is what it is without the switch."""
     g0 = DEFAULTS["bp_lim_iter"]["grid"]
     N = opts.N if opts.N else 1000
     L = opts.L if opts.L else 50
@@ -1283,6 +1377,26 @@ def run_streaming(index, W, doped, opts):
     device = E.local_device()
     os.makedirs(opts.outdir, exist_ok=True)
     path = os.path.join(opts.outdir, stream_filename(p, len(doped), W, index))
+    want_runs, nbins = bool(getattr(opts, "runs", False)), getattr(opts, "nbins", None)
+    nbins = 256 if nbins is None else nbins
+    runs_out = []
+
+    def keep_runs(eps, sr, streams):
+        """The point's statistics, summed over the ranks by one all-reduce, as the dict of the pickle."""
+        parts = [sr.hist.reshape(-1), sr.sums, sr.open_hist().reshape(-1)] + ([sr.phase.reshape(-1)] if sr.phase is not None else [])
+        flat = torch.cat(parts)
+        if dist is not None:
+            dist.all_reduce(flat)
+        flat = flat.cpu().numpy()
+        h, o = 4 * nbins, 4 * nbins + 8
+        runs_out.append(dict(eps=eps, nbins=nbins, doped=tuple(int(d) for d in doped), period=sr.period, streams=streams,
+                             hist=flat[:h].reshape(4, nbins).copy(), sums=flat[h:o].copy(),
+                             phase=flat[o + 2 * nbins:].reshape(sr.period, 3).copy() if sr.phase is not None else None,
+                             open_hist=flat[o:o + 2 * nbins].reshape(2, nbins).copy()))
+        if rank == 0:
+            with open(path + ".runs.pkl", "wb") as f:
+                pickle.dump(runs_out, f)
+
     if getattr(opts, "rng", "philox") == "glibc":
         # The reference's own experiment, row for row: ONE stream, ONE srandom(seed), the points back to back with random()
         # carried over, every point stopped at the very position at which main_streaming stops (BPF:2033).
@@ -1296,8 +1410,11 @@ def run_streaming(index, W, doped, opts):
         for sim in range(grid.num_points):
             eps = grid.eps(sim)
             run.new_point(eps)
+            sr = E.StreamRuns(p, 1, doped, nbins, device=device) if want_runs else None
             while True:
                 rows = run.run(opts.chunk, stop=tripped)
+                if want_runs:                           # the rows that count: up to the position at which the reference stops
+                    sr.update(torch.from_numpy(rows.astype(np.int32)[None]).to(device).contiguous())
                 if tripped(rows[-1, 2:]):
                     break
             tot = rows[-1, 2:]
@@ -1307,13 +1424,20 @@ def run_streaming(index, W, doped, opts):
                 f.write(stream_row(eps, tot))
             if not opts.quiet:
                 print("%f %e %e %e %e" % (eps, tot[0] / tot[4], tot[1] / tot[5], tot[2] / tot[6], tot[3] / tot[7]), flush=True)
+            if want_runs:
+                keep_runs(eps, sr, 1)
         return 0
     for sim in range(grid.num_points):
         eps = grid.eps(sim)
         st = E.Streams(p, opts.streams, opts.seed, eps, W, doped,
                        stream0=(sim * world + rank) * opts.streams, device=device)
+        sr = E.StreamRuns(p, opts.streams, doped, nbins, device=device) if want_runs else None
         while True:
-            cnt, _ = st.run(opts.chunk)
+            if want_runs:
+                cnt, tr = st.run(opts.chunk, trace=True)
+                sr.update(tr, cnt)
+            else:
+                cnt, _ = st.run(opts.chunk)
             # (column 9 = positions generated; negative = the stream was marked unusable, include/scldpc.h)
             tot = torch.cat([cnt[:, :8].sum(dim=0), (cnt[:, 9] < 0).sum().reshape(1)])
             if dist is not None:
@@ -1331,6 +1455,8 @@ def run_streaming(index, W, doped, opts):
                 f.write(stream_row(eps, tot))
             if not opts.quiet:
                 print("%f %e %e %e %e" % (eps, tot[0] / tot[4], tot[1] / tot[5], tot[2] / tot[6], tot[3] / tot[7]), flush=True)
+        if want_runs:
+            keep_runs(eps, sr, opts.streams * world)
     return 0
 
 
@@ -1355,9 +1481,19 @@ def streaming(argv=None):
                          "main_streaming draws it (BPF:1942-1945), reproduced row for row; single process")
     ap.add_argument("--chunk", type=int, default=64, help="positions per stream and launch")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--runs", action="store_true",
+                    help="also write <stream file>.runs.pkl, a pickled list with one dict per ε point {eps, nbins, doped, period, "
+                         "streams, hist, sums, phase, open_hist}: runs and events of failed positions, gaps between events, time "
+                         "to first failure and the block error rate by offset in the doping period (engine.StreamRuns; "
+                         "include/scldpc_runs.h); the .dat is unchanged")
+    ap.add_argument("--nbins", type=int, default=None, help="--runs: bins per histogram, the last takes everything beyond (256)")
     ap.add_argument("--outdir", default=".")
     ap.add_argument("--quiet", action="store_true")
     opts = ap.parse_args(argv)
+    if opts.nbins is not None and not opts.runs:
+        raise SystemExit("--nbins sizes the histograms of --runs")
+    if opts.runs and opts.nbins is not None and not 2 <= opts.nbins <= E.RUNS_MAX_BINS:
+        raise SystemExit("--nbins: 2 <= nbins <= %d" % E.RUNS_MAX_BINS)
     if opts.seed is None:
         opts.seed = int((time.time() % 1) * 1e6)
     if len(opts.DOPED) < opts.NUM_DOPED:

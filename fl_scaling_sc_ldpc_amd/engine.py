@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import (CodeParams, MAX_CAPS, NCOUNTERS, NRUN, NPEELRUN, COUNTER_NAMES, RUN_NAMES, PEELRUN_NAMES, ScldpcError,  # noqa: F401
-                   SS_MAX_BINS, SS_POS_SIZES, check, lib)
+                   SS_MAX_BINS, SS_POS_SIZES, RUNS_MAX_L, RUNS_MAX_BINS, RUNS_MAX_PERIOD, RUNS_CARRY, check, lib)
 
 
 def make_params(dv=4, dc=8, L=50, N=1000):
@@ -896,6 +896,81 @@ def ss_spectrum(p, d_adj, d_members, nbins, hist=None, pos_hist=None, want_trial
             raise RuntimeError("ss_spectrum: a CN id lies outside [0, %d): the kernel skipped that edge (status %d, SS_BAD_CN) "
                                "and the sums hold the components without it" % (p.nk, status))
     return {"hist": hist, "pos_hist": pos_hist, "trial": trial}
+
+
+def chain_runs(p, d_bits, acc=None, want_trial=False, want_fail_bits=False):
+    """scldpc_chain_runs_device: the runs of failed positions of a batch of chain trials, one per row of d_bits int32 [T, nw]
+    (a chain decoder's `erased`, a sweep decoder's `lost`).  A position fails where any of its vns_pos bits is set.
+    Accumulates into acc["pos"] int64 [L, 4] (failed, set bits, first failing position, run starts), acc["run_hist"] int64
+    [L + 1, 2] ([0, 0] trials without a failure; per run length: runs, runs that reach the end of the chain) and
+    acc["fail_hist"] int64 [L + 1] (trials by their number of failing positions); zeros where acc is None or lacks the key.
+    want_trial: also int32 [T, 4] = (failing positions, first failing position or L, runs, longest run); want_fail_bits: also
+    the flags as int32 [T, ceil(L / 32)].  Returns {"pos", "run_hist", "fail_hist", "trial", "fail_bits"}.  Enqueue only."""
+    _require_gpu()
+    assert d_bits.is_cuda and d_bits.dtype == torch.int32 and d_bits.is_contiguous() and d_bits.dim() == 2 and d_bits.shape[1] == p.nw
+    T, dev = d_bits.shape[0], d_bits.device
+    acc = dict(acc) if acc is not None else {}
+    out = {}
+    for name, shape in (("pos", (p.L, 4)), ("run_hist", (p.L + 1, 2)), ("fail_hist", (p.L + 1,))):
+        a = acc.get(name)
+        if a is None:
+            a = torch.zeros(shape, dtype=torch.int64, device=dev)
+        assert a.is_cuda and a.dtype == torch.int64 and tuple(a.shape) == shape and a.is_contiguous()
+        out[name] = a
+    trial = _uninit((T, 4), dtype=torch.int32, device=dev) if want_trial else None
+    fail_bits = _uninit((T, (p.L + 31) // 32), dtype=torch.int32, device=dev) if want_fail_bits else None
+    check(lib().scldpc_chain_runs_device(C.byref(p), T, d_bits.data_ptr(), out["pos"].data_ptr(), out["run_hist"].data_ptr(),
+                                         out["fail_hist"].data_ptr(), trial.data_ptr() if trial is not None else None,
+                                         fail_bits.data_ptr() if fail_bits is not None else None, _stream_ptr(dev)))
+    out["trial"], out["fail_bits"] = trial, fail_bits
+    return out
+
+
+class StreamRuns:
+    """Runs, events, gaps and time to first failure of nstreams streaming-decoder streams (scldpc_stream_runs_device), fed with
+    the trace rows of successive Streams.run(npos, trace=True) calls in order.  hist int64 [4, nbins] (runs, events, gaps
+    between events, time to first failure; the last bin takes everything beyond), sums int64 [8], phase int64 [period, 3]
+    (decided, failed, erased bits by offset in the doping period) and the per-stream carry int64 [nstreams, 8] live on the
+    device; include/scldpc_runs.h defines every entry."""
+
+    def __init__(self, p, nstreams, doped=(), nbins=256, device="cuda:0"):
+        _require_gpu()
+        self.p, self.n, self.doped, self.nbins = p, int(nstreams), tuple(int(d) for d in doped), int(nbins)
+        self.period = self.doped[-1] + 1 if self.doped else 1
+        darr, dptr = _lib.doped_array(self.doped)
+        # the parameter checks, before any buffer exists (a refusal names its limit)
+        check(lib().scldpc_stream_runs_device(C.byref(p), 0, 0, None, None, darr.size, dptr, self.nbins, None, None, None,
+                                              C.c_void_p(8) if self.period <= _lib.RUNS_MAX_PERIOD else None, None))
+        self.hist = torch.zeros((4, self.nbins), dtype=torch.int64, device=device)
+        self.sums = torch.zeros((8,), dtype=torch.int64, device=device)
+        self.phase = (torch.zeros((self.period, 3), dtype=torch.int64, device=device)
+                      if self.period <= _lib.RUNS_MAX_PERIOD else None)
+        self.carry = torch.zeros((self.n, _lib.RUNS_CARRY), dtype=torch.int64, device=device)
+
+    def update(self, trace, counters=None):
+        """Feed the next rows: trace int32 [nstreams, npos, 10]; counters int64 [nstreams, 10] (Streams.counters) lets the
+        kernel skip the streams marked unusable.  Enqueue only."""
+        assert trace.is_cuda and trace.dtype == torch.int32 and trace.is_contiguous() and trace.dim() == 3
+        assert trace.shape[0] == self.n and trace.shape[2] == 10
+        if counters is not None:
+            assert counters.is_cuda and counters.dtype == torch.int64 and counters.is_contiguous() and tuple(counters.shape) == (self.n, 10)
+        darr, dptr = _lib.doped_array(self.doped)
+        check(lib().scldpc_stream_runs_device(C.byref(self.p), self.n, int(trace.shape[1]), trace.data_ptr(),
+                                              counters.data_ptr() if counters is not None else None, darr.size, dptr,
+                                              self.nbins, self.carry.data_ptr(), self.hist.data_ptr(), self.sums.data_ptr(),
+                                              self.phase.data_ptr() if self.phase is not None else None,
+                                              _stream_ptr(trace.device)))
+        return self
+
+    def open_hist(self):
+        """int64 [2, nbins]: the runs (row 0) and events (row 1) still open in the carry, by their length so far (censored: they
+        are in none of hist's rows)."""
+        out = torch.zeros((2, self.nbins), dtype=torch.int64, device=self.carry.device)
+        for row, col in ((0, 1), (1, 2)):
+            v = self.carry[:, col]
+            v = v[v > 0].clamp(max=self.nbins - 1)
+            out[row].index_add_(0, v, torch.ones_like(v))
+        return out
 
 
 # ------------------------------------------------------------------------------------------------
