@@ -92,6 +92,11 @@ RUNS_MAX_BINS = 4096            # SCLDPC_RUNS_MAX_BINS
 RUNS_MAX_PERIOD = 4096          # SCLDPC_RUNS_MAX_PERIOD
 RUNS_CARRY = 8                  # SCLDPC_RUNS_CARRY
 
+# every symbol the extension header include/scldpc_eps.h declares (the same shared object; tests/test_eps_host.py)
+EXPORTS_EPS = ("scldpc_channel_levels_device", "scldpc_peel_sweep_eps_device", "scldpc_peel_sweep_eps_device_adj16",
+               "scldpc_peel_sweep_eps_workspace_query")
+EPS_MAX_POINTS = 64             # SCLDPC_EPS_MAX_POINTS
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -226,6 +231,11 @@ def lib():
     L.scldpc_ss_spectrum_device.argtypes = [pp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp]
     L.scldpc_chain_runs_device.argtypes = [pp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.scldpc_stream_runs_device.argtypes = [pp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.scldpc_channel_levels_device.argtypes = [pp, u64, u64, i32, i32, vp, i32, vp, vp, vp]
+    L.scldpc_peel_sweep_eps_device.argtypes = [pp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, u64, vp]
+    L.scldpc_peel_sweep_eps_device_adj16.argtypes = L.scldpc_peel_sweep_eps_device.argtypes
+    L.scldpc_peel_sweep_eps_workspace_query.argtypes = [pp, i32, i32]
+    L.scldpc_peel_sweep_eps_workspace_query.restype = i64
     L.scldpc_swc_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_swc_bp_device_adj16.argtypes = L.scldpc_swc_bp_device.argtypes
     L.scldpc_stream_supported.argtypes = [pp, i32]

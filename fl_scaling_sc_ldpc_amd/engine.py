@@ -6,6 +6,7 @@ channel_doped (sampling), decodeBP / decodeBP_SW (decoding), plr_computation / w
 accumulation).
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -13,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import (CodeParams, MAX_CAPS, NCOUNTERS, NRUN, NPEELRUN, COUNTER_NAMES, RUN_NAMES, PEELRUN_NAMES, ScldpcError,  # noqa: F401
-                   SS_MAX_BINS, SS_POS_SIZES, RUNS_MAX_L, RUNS_MAX_BINS, RUNS_MAX_PERIOD, RUNS_CARRY, check, lib)
+                   SS_MAX_BINS, SS_POS_SIZES, RUNS_MAX_L, RUNS_MAX_BINS, RUNS_MAX_PERIOD, RUNS_CARRY, EPS_MAX_POINTS, check, lib)
 
 
 def make_params(dv=4, dc=8, L=50, N=1000):
@@ -687,6 +688,58 @@ def peel_sweep(p, d_adj, d_chan, total_size, sweep_start=0, lost_lo=0, lost_hi=N
     check(fn(C.byref(p), T, d_adj.data_ptr(), d_chan.data_ptr(), int(total_size), int(sweep_start), int(lost_lo),
              int(total_size if lost_hi is None else lost_hi), out.data_ptr(),
              lost.data_ptr() if lost is not None else None, ws, wsb, _stream_ptr(dev)))
+    return {"out": out, "lost": lost}
+
+
+def erasure_threshold(eps):
+    """The samplers' threshold of an erasure probability: a VN is erased iff its 31-bit draw is below ceil(eps * RAND_MAX)
+    (erasure_threshold, csrc/sampler_common.h).  Two eps with one threshold are one channel."""
+    return int(math.ceil(float(eps) * 2147483647.0))
+
+
+def channel_levels(p, seed, trial0, ntrials, es_desc, doped=(), device="cuda:0", out=None):
+    """The channel of trials trial0 .. trial0 + ntrials - 1 at every point of es_desc (strictly decreasing thresholds, at most
+    _lib.EPS_MAX_POINTS points) as levels: uint8 [T, n], lev[j] = the number of points at which VN j is erased, so that
+    pack(lev > k) is the channel sample_philox writes for es_desc[k] on the same (seed, trial, doped)
+    (scldpc_channel_levels_device)."""
+    _require_gpu()
+    eps = np.ascontiguousarray(es_desc, dtype=np.float64).reshape(-1)
+    d_lev = _uninit((ntrials, p.n), dtype=torch.uint8, device=device) if out is None else out
+    darr, dptr = _lib.doped_array(doped)
+    check(lib().scldpc_channel_levels_device(C.byref(p), int(seed), int(trial0), int(ntrials), eps.size,
+                                             eps.ctypes.data if eps.size else None, darr.size, dptr, d_lev.data_ptr(),
+                                             _stream_ptr(d_lev.device)))
+    return d_lev
+
+
+def peel_sweep_eps_workspace_bytes(p, ntrials, adj16):
+    """Bytes of workspace peel_sweep_eps needs for ntrials trials (0: the CN words stay in LDS); ScldpcError for a shape the
+    entry refuses.  Needs no device."""
+    nbytes = lib().scldpc_peel_sweep_eps_workspace_query(C.byref(p), int(ntrials), 1 if adj16 else 0)
+    if nbytes < 0:
+        check(int(nbytes))
+    return int(nbytes)
+
+
+def peel_sweep_eps(p, d_adj, d_levels, npoints, total_size, lost_lo=0, lost_hi=None, want_lost=False):
+    """peel_sweep with sweep_start = 0 at every point of a descending eps grid in one launch: the code d_adj once, the channel
+    as levels (channel_levels), stage k peeling on from the residual of stage k - 1.  Returns dict with out int32 [K, T, 8] —
+    out[k] is peel_sweep's block for the channel of point k ([0] #lost, [1] #lost_exp, [2] #blocks_failed_exp, [7] #erased;
+    [5] the rounds of stage k, [6] its re-scans after a queue overflow) — and `lost` int32 [K, T, nw] or None (scldpc_peel_sweep_eps_device)."""
+    _require_gpu()
+    T, K = d_adj.shape[0], int(npoints)
+    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
+    assert d_levels.is_cuda and d_levels.dtype == torch.uint8 and d_levels.is_contiguous() and d_levels.shape == (T, p.n)
+    dev = d_adj.device
+    adj16 = _is_adj16(d_adj)
+    nbytes = peel_sweep_eps_workspace_bytes(p, T, adj16)                 # (also refuses the shape before anything is allocated)
+    out = _uninit((max(K, 0), T, 8), dtype=torch.int32, device=dev)
+    lost = _uninit((max(K, 0), T, p.nw), dtype=torch.int32, device=dev) if want_lost else None
+    ws = _uninit(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    fn = lib().scldpc_peel_sweep_eps_device_adj16 if adj16 else lib().scldpc_peel_sweep_eps_device
+    check(fn(C.byref(p), T, d_adj.data_ptr(), d_levels.data_ptr(), K, int(total_size), int(lost_lo),
+             int(total_size if lost_hi is None else lost_hi), out.data_ptr(), lost.data_ptr() if lost is not None else None,
+             ws.data_ptr() if ws is not None else None, nbytes, _stream_ptr(dev)))
     return {"out": out, "lost": lost}
 
 

@@ -487,6 +487,127 @@ def simulate_sc_ldpc_spectrum(e, l, r, L, M, is_terminated, is_protograph, is_bo
                              doping_points, rng, seed, batch, device, sweep, local_tables, int(nbins))
 
 
+# Whether ber_sim --rng philox takes simulate_sc_ldpc_curve (one sampled code and one decoder launch per batch for the whole eps
+# grid: engine.channel_levels + engine.peel_sweep_eps) where --eps-fused is "auto" or absent, instead of one simulate_sc_ldpc per
+# eps: True only if every repetition of the fused run beats every repetition of the loop it replaces on every shape of
+# tools/eps_fused_speed.py, with equal outputs (profiles/eps_fused_speed.json).  Kept False here whatever is
+# measured: the flip is a change of its own.
+EPS_FUSED_BY_DEFAULT = False
+
+_EPS_UNBOUNDED = ("eps_fused: an unbounded chain sweeps from CN position 10 (sweep_start > 0), where a CN below the sweep start "
+                  "fires only on a transition and the residual at one eps is not the residual of the residual at a higher one")
+
+
+def curve_stages(es):
+    """The host side of simulate_sc_ldpc_curve, a pure function: es in the caller's order -> (stage_eps, stage_of) with
+    stage_eps the eps of the distinct thresholds (engine.erasure_threshold) in strictly descending order, the first eps of
+    the caller's that has the threshold standing for it, and stage_of[i] the stage of es[i]."""
+    es = [float(e) for e in es]
+    th = [E.erasure_threshold(e) for e in es]
+    uniq = sorted(set(th), reverse=True)
+    return [es[th.index(t)] for t in uniq], [uniq.index(t) for t in th]
+
+
+def simulate_sc_ldpc_curve(es, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats=int(1e5),
+                           max_fuckups=2000, doping_points=[], seed=0, batch=None, device=None, rng="philox", sweep="first",
+                           local_tables=None):
+    """simulate_sc_ldpc(e, ..., rng="philox", seed=seed, sweep="first") for every e of es, as a list of 13-tuples in the caller's
+    order, value for value — from ONE sampled code per trial and one decoder launch per batch: the codes depend on (seed, trial)
+    only and the erased sets of a descending eps grid are nested, so the channel goes to the device as levels
+    (engine.channel_levels) and engine.peel_sweep_eps peels point k on from the residual of point k - 1.  Points with one
+    threshold are one stage; a point leaves the following rounds once its fuckups reach max_fuckups.  Under torch.distributed one
+    all-gather per round carries the rows of every live point.
+    ValueError("eps_fused: ...") for rng="numpy" (a fresh stream per eps: nothing is shared), is_bounded=False (the sweep starts
+    above CN 0), sweep "small" / "wide" and local_tables=True (this decoder is its own path), more than 64 distinct points, and a
+    shape the entry refuses."""
+    if rng != "philox":
+        raise ValueError("eps_fused: rng=%r draws a fresh stream of codes and channels for every eps: nothing is shared between "
+                         "the points (pass rng='philox')" % (rng,))
+    if not is_bounded:
+        raise ValueError(_EPS_UNBOUNDED)
+    if sweep not in ("first", "auto"):
+        raise ValueError("eps_fused: sweep=%r chooses the 4-bit sweep decoder, which this path does not run: the eps walk is a "
+                         "decoder of its own (engine.peel_sweep_eps)" % (sweep,))
+    if local_tables:
+        raise ValueError("eps_fused: local_tables=True chooses the tables of the 4-bit sweep decoder, which this path does not run")
+    _check_flags(is_protograph, is_tail_biting)
+    es = list(es)
+    if not es:
+        return []
+    stage_eps, stage_of = curve_stages(es)
+    K = len(stage_eps)
+    if K > E.EPS_MAX_POINTS:
+        raise ValueError("eps_fused: at most %d distinct eps points in one run (got %d)" % (E.EPS_MAX_POINTS, K))
+    g = _Geometry(l, r, L, M, is_terminated, is_bounded, doping_points)
+    p = g.params
+    assert g.sweep_start == 0
+    ens = "protograph" if is_protograph else "tail_biting" if is_tail_biting else "olmos"
+    try:
+        E.peel_sweep_eps_workspace_bytes(p, 1, ens == "olmos")              # the entry's own shape rule; needs no device
+    except E.ScldpcError as err:
+        raise ValueError("eps_fused: %s" % err)
+    soft = isinstance(doping_points, dict)
+    if soft and is_protograph:
+        raise NameError("name 'position' is not defined")                   # the reference's own failure for soft doping (PD:228)
+    device = _device(device)
+    dist, rank, world = _dist()
+    print("[scldpc] kernels: sampler (first generation) + channel_levels + peel_sweep_eps (%d eps points from one code)" % K,
+          file=sys.stderr, flush=True)
+    if batch is None:
+        batch = 2048
+    doped = [] if soft else _doped_positions(doping_points)
+    run = torch.zeros((K, E.NPEELRUN), dtype=torch.int64, device=device)
+    i_tr, i_fu = E.PEELRUN_NAMES.index("trials"), E.PEELRUN_NAMES.index("fuckups")
+    live = list(range(K))                                                   # stages still running, by descending eps
+    bound = [0] * K                                                         # upper bound on a stage's fuckups while nobody has looked
+    done = 0                                                                # trials fed to every live stage
+    while live and done < num_repeats:
+        nb = min(batch * world, num_repeats - done)                         # the round of simulate_sc_ldpc: same keys, same split
+        offs = _split(nb, world)
+        lo, mine = offs[rank], offs[rank + 1] - offs[rank]
+        d_adj, _ = E.sample_philox(p, seed, done + lo, mine, max(es), doped, device=device, adj16=(ens == "olmos"), ensemble=ens)
+        d_lev = E.channel_levels(p, seed, done + lo, mine, [stage_eps[k] for k in live], doped, device=device)
+        if soft:                                                            # PD:176-183: the first int(alpha*M) VNs of the position are known
+            for pos, alpha in doping_points.items():
+                d_lev[:, pos * M: pos * M + int(alpha * M)] = 0
+        d_out = E.peel_sweep_eps(p, d_adj, d_lev, len(live), g.total_size, g.lost_lo, g.lost_hi)["out"]
+        if world > 1:
+            m = max(offs[r + 1] - offs[r] for r in range(world))
+            pad = torch.zeros((len(live), m, 8), dtype=d_out.dtype, device=d_out.device)
+            pad[:, :mine] = d_out
+            parts = [torch.empty_like(pad) for _ in range(world)]
+            dist.all_gather(parts, pad)
+            d_out = torch.cat([parts[r][:, :offs[r + 1] - offs[r]] for r in range(world)], dim=1).contiguous()
+        for i, k in enumerate(live):
+            E.accumulate_peel(d_out[i], run[k], max_fuckups)
+            bound[k] += nb
+        if all(bound[k] < max_fuckups for k in live):
+            done += nb                                                      # no stage can have tripped: stay asynchronous
+            continue
+        tot = run.cpu().numpy()                                             # every row in one transfer
+        still = []
+        for k in live:
+            bound[k] = int(tot[k, i_fu])
+            if int(tot[k, i_tr]) - done == nb and tot[k, i_fu] < max_fuckups:
+                still.append(k)
+        live = still
+        done += nb
+    tot = run.cpu().numpy()
+    tuples = []
+    for k in range(K):
+        t = {name: int(v) for name, v in zip(E.PEELRUN_NAMES, tot[k])}
+        o1 = t["trials"]
+        total_generated, total_blocks_generated = o1 * g.generated, o1 * g.blocks
+        tuples.append((t["fuckups"] / o1, t["fuckups_exp"] / o1, t["lost"] / total_generated, t["lost_exp"] / total_generated,
+                       t["fuckups_exp"], o1, t["lost_exp"], total_generated, t["blocks_exp"], total_blocks_generated,
+                       t["blocks_exp"] / total_blocks_generated))
+    out = []
+    for k in stage_of:                                                      # the caller's order, duplicates included
+        a = tuples[k]
+        out.append(a[:8] + (np.zeros(num_repeats), np.zeros(num_repeats)) + a[8:])
+    return out
+
+
 # Whether simulate_peeling_decoder_ldpc(pick="auto") takes engine.peel_pick_deg (the CN words through cn_build.hip's LDS ring,
 # two trials per wave in peel_pick_multi_kernel, for the pairs (3,6), (4,8), (5,10)) where select_pick allows it, instead of
 # engine.peel_pick: True only if every repetition of the new path beats every repetition of the old one on every shape of
@@ -987,7 +1108,9 @@ def _cli_options(args, kw):
     device sampling, trials sharded over the ranks of a torch.distributed.run job) — `--sweep first|small|wide|auto` and
     `--local-tables on|off|auto` (local_tables=True | False | None), which only ber_sim (simulate_sc_ldpc) takes, and
     `--pick first|multi|auto`, which only simulate_variance (simulate_peeling_decoder_ldpc) and simulate_covariance
-    (simulate_pd_covariance) take, and `--nbins N`, which only stopping_sets (simulate_sc_ldpc_spectrum) takes."""
+    (simulate_pd_covariance) take, `--nbins N`, which only stopping_sets (simulate_sc_ldpc_spectrum) takes, and
+    `--eps-fused on|off|auto` (eps_fused=True | False | None), which only ber_sim takes: the whole eps grid from one sampled code
+    (simulate_sc_ldpc_curve); auto is what EPS_FUSED_BY_DEFAULT says."""
     kw, pos, it = dict(kw), [], iter(args)
     for x in it:
         if isinstance(x, str) and x == "--local-tables":
@@ -995,6 +1118,11 @@ def _cli_options(args, kw):
             if v not in ("on", "off", "auto"):
                 raise SystemExit("--local-tables takes on, off or auto (got %r)" % (v,))
             kw["local_tables"] = {"on": True, "off": False, "auto": None}[v]
+        elif isinstance(x, str) and x == "--eps-fused":
+            v = next(it)
+            if v not in ("on", "off", "auto"):
+                raise SystemExit("--eps-fused takes on, off or auto (got %r)" % (v,))
+            kw["eps_fused"] = {"on": True, "off": False, "auto": None}[v]
         elif isinstance(x, str) and x in ("--rng", "--seed", "--batch", "--device", "--sweep", "--pick", "--nbins"):
             v = next(it)
             if x == "--sweep" and v not in ("first", "small", "wide", "auto"):
@@ -1035,6 +1163,8 @@ def main_simulate_sc_ldpc(argv=None, **kw):
             dist.destroy_process_group()
 
 
+_EPS_FUSED_ELSEWHERE = ("--eps-fused walks ber_sim's eps grid on one sampled code (simulate_sc_ldpc_curve): %s takes no such "
+                        "option%s")
 _NBINS_ELSEWHERE = "--nbins sizes the histogram of stopping_sets (simulate_sc_ldpc_spectrum): %s takes no such option"
 
 
@@ -1046,6 +1176,9 @@ def main_stopping_sets(argv=None, **kw):
     if "pick" in kw:
         raise SystemExit("--pick chooses the random-pick decoder of simulate_variance (simulate_peeling_decoder_ldpc): "
                          "stopping_sets runs the sweep decoder and takes no such option")
+    if "eps_fused" in kw:
+        raise SystemExit(_EPS_FUSED_ELSEWHERE % ("stopping_sets", " (the spectrum pass reads the lost bits of simulate_sc_ldpc's "
+                                                 "rounds; engine.peel_sweep_eps writes them, the simulator does not pass them on yet)"))
     joined = _join_job(kw)
     try:
         return _main_simulate_sc_ldpc(a, kw, spectrum=True)
@@ -1087,11 +1220,21 @@ def _main_simulate_sc_ldpc(a, kw, spectrum=False):
     out = _Tee(fname, _dist()[1] == 0)
     es = list(es if isinstance(es, (list, np.ndarray, range)) else [es])
     hists, pos_hists = [], []
+    kw = dict(kw)
+    fused = kw.pop("eps_fused", None)
+    if fused is None:                                                       # absent or auto: only where the fused path applies
+        fused = (EPS_FUSED_BY_DEFAULT and not spectrum and kw.get("rng") == "philox" and is_bounded
+                 and kw.get("sweep", "auto") in ("auto", "first") and not kw.get("local_tables"))
     try:
         out.line(head)
-        for e in es:
+        if fused:                                                           # the same lines in the same order, from one call
+            rows = simulate_sc_ldpc_curve(es, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats,
+                                          max_fuckups, doping_points, **kw)
+        for i, e in enumerate(es):
             args = (e, l, r, L, M, is_terminated, is_protograph, is_bounded, is_tail_biting, num_repeats, max_fuckups, doping_points)
-            if spectrum:
+            if fused:
+                tuple13 = rows[i]
+            elif spectrum:
                 tuple13, hist, pos_hist = simulate_sc_ldpc_spectrum(*args, **kw)
                 hists.append(hist)
                 pos_hists.append(pos_hist)
@@ -1118,6 +1261,8 @@ def main_simulate_variance(argv=None, **kw):
                          "the random-pick decoder and takes no such option")
     if "nbins" in kw:
         raise SystemExit(_NBINS_ELSEWHERE % "simulate_variance")
+    if "eps_fused" in kw:
+        raise SystemExit(_EPS_FUSED_ELSEWHERE % ("simulate_variance", ""))
     joined = _join_job(kw)
     try:
         return _main_simulate_variance(a, kw)
@@ -1165,6 +1310,8 @@ def main_simulate_covariance(argv=None, **kw):
                          "runs the random-pick decoder and takes no such option")
     if "nbins" in kw:
         raise SystemExit(_NBINS_ELSEWHERE % "simulate_covariance")
+    if "eps_fused" in kw:
+        raise SystemExit(_EPS_FUSED_ELSEWHERE % ("simulate_covariance", ""))
     if len(a) != 11:
         raise SystemExit("simulate_covariance takes OUT l r L M e T|N U|P num_runs STRIDE (got %d arguments)" % (len(a) - 1))
     joined = _join_job(dict(kw, rng="philox"))
