@@ -97,6 +97,9 @@ EXPORTS_EPS = ("scldpc_channel_levels_device", "scldpc_peel_sweep_eps_device", "
                "scldpc_peel_sweep_eps_workspace_query")
 EPS_MAX_POINTS = 64             # SCLDPC_EPS_MAX_POINTS
 
+# every symbol the extension header include/scldpc_bp_eps.h declares (the same shared object; tests/test_bp_eps_host.py)
+EXPORTS_BP_EPS = ("scldpc_full_bp_eps_device", "scldpc_full_bp_eps_device_adj16", "scldpc_full_bp_eps_workspace_query")
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -236,6 +239,10 @@ def lib():
     L.scldpc_peel_sweep_eps_device_adj16.argtypes = L.scldpc_peel_sweep_eps_device.argtypes
     L.scldpc_peel_sweep_eps_workspace_query.argtypes = [pp, i32, i32]
     L.scldpc_peel_sweep_eps_workspace_query.restype = i64
+    L.scldpc_full_bp_eps_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
+    L.scldpc_full_bp_eps_device_adj16.argtypes = L.scldpc_full_bp_eps_device.argtypes
+    L.scldpc_full_bp_eps_workspace_query.argtypes = [pp, i32, i32]
+    L.scldpc_full_bp_eps_workspace_query.restype = i64
     L.scldpc_swc_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_swc_bp_device_adj16.argtypes = L.scldpc_swc_bp_device.argtypes
     L.scldpc_stream_supported.argtypes = [pp, i32]

@@ -56,6 +56,15 @@ consumed — where the failed positions sit and how long their runs are (engine.
 runs, events, gaps, time to first failure and the error rate by offset in the doping period (engine.StreamRuns over the trace) —
 pickled by rank 0 as one dict per ε point beside the result file (`<file>.runs.pkl`), which itself is written as without the switch.
 
+`bp_lim_iter INDEX W NUM_DOPED MAX_IT --schedule fixpoint --eps-fused on` (MAX_IT >= 10^6) decodes every ε point of the grid from
+ONE sampled code per frame: one sampler call, engine.channel_levels and one engine.full_bp_eps per batch instead of a sampler and a
+decode per point (run_grid_fused).  This is the one switch that does NOT write the same file: the unfused program keys frame f of
+point sim as trial_key(INDEX, sim, f), so its points see different codes; the fused run keys every point's frame f as
+trial_key(INDEX, 0, f).  Row 0 is byte for byte the unfused row 0, and row k is byte for byte what the unfused program's point 0
+gives at ε_k — another sample of the same distribution than the unfused row k, and positively correlated with the other rows
+(common random numbers).  `off`, and `auto` while BP_EPS_FUSED_BY_DEFAULT is False, write the unfused file.  With --runs the
+.runs.pkl has the same layout, over the frames each point consumed.
+
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
@@ -1021,8 +1030,203 @@ def _write_traj_rows(fh, rows, counters, nb, cols=4):
     fh.write("".join(out))
 
 
-def run_program(prog, index, W, num_doped, max_it, extra, opts):
-    """The body of main_terminated for one of the three executables."""
+# Whether bp_lim_iter --schedule fixpoint takes run_grid_fused (one sampled code and one decoder launch per batch for the whole ε
+# grid: engine.channel_levels + engine.full_bp_eps) where --eps-fused is "auto" or absent, instead of one run_point per ε.  Unlike
+# the other *_BY_DEFAULT this switch changes the FILE (every point decodes the codes of point 0, see run_grid_fused), so no
+# measurement alone can flip it; kept False here: the flip is a change of its own.
+BP_EPS_FUSED_BY_DEFAULT = False
+
+
+def eps_fused_reason(prog, p, es, schedule="fixpoint", max_it=0, caps=None, window="off", rng="philox", shard="auto"):
+    """Why `--eps-fused on` cannot run this configuration, or None where it can.  A pure function (the shape rule is the
+    library's workspace query, a host function): no device work.  prog: the program; es: the ε of the grid; max_it: the cap as
+    the Simulator takes it (0: none — the command line's MAX_IT = 0 arrives here as 1, BPF:1065); caps: --caps; shard: --shard
+    as given."""
+    if prog != "bp_lim_iter":
+        return ("the ε walk is unlimited full BP on one sampled code (bp_lim_iter --schedule fixpoint); %s takes no such path"
+                % prog)
+    if schedule != "fixpoint":
+        return ("--schedule %s counts flooding iterations, which the ε walk does not have: peeling on from the residual of the "
+                "point before gives the fixpoint, not the iterations (pass --schedule fixpoint)" % schedule)
+    if 0 < max_it < 1000000:
+        return ("MAX_IT = %d binds: a capped result depends on the schedule, and only the fixpoint of unlimited full BP is the "
+                "maximal stopping set the ε walk computes (pass MAX_IT >= 1000000)" % max_it)
+    if caps:
+        return "--caps asks for capped results, which depend on the schedule: the ε walk computes the fixpoint only"
+    if window == "classical":
+        return ("--window classical decodes window by window with MAX_IT iterations each: its result depends on the schedule, "
+                "not on the stopping sets alone")
+    if rng != "philox":
+        return ("--rng %s replays one sequential random() stream, a fresh code for every frame of every point: nothing is shared "
+                "between the points (pass --rng philox)" % rng)
+    if shard == "points":
+        return ("--shard points gives every rank ε points of its own, and the ε walk decodes all points of a frame in one launch: "
+                "its ranks share the frames (--shard frames, or auto)")
+    from .peeling_decoding import curve_stages
+    K = len(curve_stages(es)[0])
+    if K > E.EPS_MAX_POINTS:
+        return "at most %d distinct ε points in one run (got %d)" % (E.EPS_MAX_POINTS, K)
+    try:
+        E.full_bp_eps_workspace_bytes(p, 1, p.cns_pos <= 65536)             # the entry's own shape rule; needs no device
+    except E.ScldpcError as err:
+        return str(err)
+    return None
+
+
+def run_grid_fused(p, es, min_frame_err, max_frames, seed, index=0, is_term=True, doped=(), batch=2048, device=None,
+                   shard_frames=True, runs=False, defer_abort=False, verbose=False):
+    """Unlimited full BP at every ε of es from ONE sampled code per frame: a list of PointResult in the caller's order, point i
+    what Simulator(p, schedule="fixpoint", seed=seed, index=index, …).run_point(0, es[i], min_frame_err, max_frames) returns,
+    value for value (.runs included with runs=True) — except run["iterations"], the sum of the kernels' round counts, which every
+    fixpoint kernel fills with rounds of its own and no file holds.
+
+    NOT what a loop over run_point(sim, es[sim], …) returns: that loop keys frame f of point sim as trial_key(index, sim, f), so
+    its points see different codes; here every point decodes the frames trial_key(index, 0, f), the codes of point 0.  Point 0
+    is the same; every other point is another sample of the same distribution, and the points are positively correlated with
+    each other (common random numbers) — differences between neighbouring points are less noisy, a sum over points more.
+
+    Per round: one first-generation sampler call at max(es) for the codes (2-byte rows where the sampler offers them; its
+    channel is not used), engine.channel_levels over the live points, one engine.full_bp_eps (the fixpoint of point k by
+    peeling on from the residual of point k - 1: the erased sets of a descending grid are nested, and what unlimited flooding
+    converges to is the maximal stopping set of the erased set, whatever the schedule), engine.accumulate_run per live point.
+    ε with one threshold are one stage.  A point is finished when its frame_err reaches min_frame_err or its frames reach
+    max_frames, and leaves the later rounds.  Rounds and the frame split over the ranks are run_point's (split_round); one
+    all-gather per round carries the [K_live, m, 8] rows, so every rank cuts every point at the same frame; the host looks at the
+    run counters only in rounds in which the stop rule could trip.  A frame that breaks decodeBP's invariant (status != 0) aborts
+    as in run_point; with defer_abort the points come back with .bad set."""
+    from .peeling_decoding import curve_stages
+    es = [float(e) for e in es]
+    if not es:
+        return []
+    stage_eps, stage_of = curve_stages(es)
+    K = len(stage_eps)
+    if K > E.EPS_MAX_POINTS:
+        raise ValueError("eps_fused: at most %d distinct ε points in one run (got %d)" % (E.EPS_MAX_POINTS, K))
+    adj16 = p.cns_pos <= 65536
+    try:
+        E.full_bp_eps_workspace_bytes(p, 1, adj16)
+    except E.ScldpcError as err:
+        raise ValueError("eps_fused: %s" % err)
+    dist, rank, W = _dist() if shard_frames else (None, 0, 1)
+    device = torch.device(device) if device is not None else E.local_device()
+    if verbose:
+        print("[scldpc] kernels: sampler (first generation) + channel_levels + full_bp_eps (%d ε points from one code)" % K,
+              file=sys.stderr, flush=True)
+    i_frames, i_ferr, i_status = RUN_NAMES.index("frames"), RUN_NAMES.index("frame_err"), E.COUNTER_NAMES.index("status")
+    B, doped = int(batch), tuple(doped)
+    d_adj = torch.empty((B, p.n, p.dv), dtype=torch.int16 if adj16 else torch.int32, device=device)
+    d_ch = torch.empty((B, p.nw), dtype=torch.int32, device=device)
+    d_lev = torch.empty((B, p.n), dtype=torch.uint8, device=device)
+    d_cnt = torch.empty(K * B * NCOUNTERS, dtype=torch.int32, device=device)
+    run = torch.zeros((K, NRUN), dtype=torch.int64, device=device)
+    bad = torch.zeros(K, dtype=torch.bool, device=device)
+    racc = [None] * K
+    consumed = [0] * K
+    live = list(range(K))                                               # stages still running, by descending ε
+    frame0 = 0
+    while live and frame0 < max_frames:
+        R, sizes, offs = Simulator.split_round(max_frames - frame0, B, W)
+        nb, off = sizes[rank], offs[rank]
+        Kl = len(live)
+        res = None
+        if nb:
+            key = trial_key(index, 0, frame0 + off)
+            E.sample_philox(p, seed, key, nb, stage_eps[0], doped, out=(d_adj[:nb], d_ch[:nb]))
+            E.channel_levels(p, seed, key, nb, [stage_eps[k] for k in live], doped, device=device, out=d_lev[:nb])
+            res = E.full_bp_eps(p, d_adj[:nb], d_lev[:nb], Kl, is_term=is_term, want_erased=runs,
+                                counters=d_cnt[:Kl * nb * NCOUNTERS].view(Kl, nb, NCOUNTERS))
+        if W > 1:
+            m = max(sizes)
+            mine = torch.zeros((Kl, m, NCOUNTERS), dtype=torch.int32, device=device)
+            if nb:
+                mine[:, :nb] = res["counters"]
+            gathered = [torch.empty_like(mine) for _ in range(W)]
+            dist.all_gather(gathered, mine)
+            allcnt = torch.cat([g[:, :s] for g, s in zip(gathered, sizes)], dim=1).contiguous()
+        else:
+            allcnt = res["counters"]
+        for i, k in enumerate(live):
+            E.accumulate_run(allcnt[i], run[k], min_frame_err)
+        can_trip = min_frame_err > 0 and frame0 + R >= min_frame_err
+        tot = run.cpu().numpy() if can_trip else None                   # every row in one transfer
+        still = []
+        for i, k in enumerate(live):
+            if can_trip:
+                used_round = int(tot[k, i_frames]) - consumed[k]
+                consumed[k] = int(tot[k, i_frames])
+                stopped = tot[k, i_ferr] >= min_frame_err
+            else:
+                used_round, stopped = R, False
+                consumed[k] += R
+            bad[k] |= (allcnt[i, :used_round, i_status] != 0).any()
+            if runs and nb and used_round - off > 0:
+                racc[k] = E.chain_runs(p, res["erased"][i][:min(nb, used_round - off)], acc=racc[k])
+            if not stopped:
+                still.append(k)
+        live = still
+        frame0 += R
+    bad = bad.cpu().tolist()
+    if any(bad) and not defer_abort:
+        abort_invariant()
+    tot = run.cpu().numpy()
+    stage_runs = [None] * K
+    if runs:
+        shapes = runs_shapes(p.L)
+        for k in range(K):                                              # one all-reduce per point, as run_point's
+            flat = (torch.cat([racc[k][name].reshape(-1) for name, _ in shapes]) if racc[k] is not None else
+                    torch.zeros(sum(int(np.prod(sh)) for _, sh in shapes), dtype=torch.int64, device=device))
+            if W > 1:
+                dist.all_reduce(flat)
+            stage_runs[k] = runs_unflatten(p.L, flat.cpu().numpy())
+    return [PointResult(e, p.n, p.L, tot[k], bad=bad[k], runs=copy.deepcopy(stage_runs[k])) for e, k in zip(es, stage_of)]
+
+
+def _check_eps_fused(prog, opts):
+    """--eps-fused against the rest of the command line: exits with the reason for `on` where the ε walk cannot run (before any
+    device work); else whether the run takes it."""
+    explicit = _switch(opts, "eps_fused")                               # auto: where it applies, if BP_EPS_FUSED_BY_DEFAULT
+    want = BP_EPS_FUSED_BY_DEFAULT if explicit is None else explicit
+    if not want:
+        return False
+    p, grid = _ensemble_and_grid(prog, opts)
+    reason = eps_fused_reason(prog, p, [grid.eps(k) for k in range(grid.num_points)], getattr(opts, "schedule", "flooding"),
+                              max(1, opts.MAX_IT), getattr(opts, "caps", None), getattr(opts, "window", "off"), opts.rng,
+                              getattr(opts, "shard", "auto"))
+    if reason is not None and explicit:
+        raise SystemExit("--eps-fused on: " + reason)
+    return reason is None
+
+
+def _run_eps_fused(prog, index, W, max_it, opts, p, grid, doped, want_runs):
+    """`bp_lim_iter … --schedule fixpoint --eps-fused on`: the file (and .runs.pkl) of the grid from run_grid_fused.  The ranks
+    of a job share the frames."""
+    dist, rank, world = _dist()
+    es = [grid.eps(k) for k in range(grid.num_points)]
+    t0 = time.time()
+    points = run_grid_fused(p, es, grid.min_frame_err, grid.max_frames, opts.seed, index=index, doped=doped, batch=opts.batch,
+                            device=getattr(opts, "device", None), runs=want_runs, defer_abort=True,
+                            verbose=rank == 0 and not opts.quiet)
+    first_bad = next((k for k, pt in enumerate(points) if pt.bad), None)
+    points = points[:first_bad]                                         # the reference's process is gone at that point
+    os.makedirs(opts.outdir, exist_ok=True)
+    path = os.path.join(opts.outdir, result_filename(prog, p, W, max_it, 0, index))
+    if rank == 0:
+        for sim, pt in enumerate(points):
+            write_risultati(path, sim, pt)
+            if not opts.quiet:
+                r = pt.run
+                print("%f %e %e %e   (f=%d, %.1fs)" % (pt.eps, r["users_err"] / p.n / pt.f, r["frame_err"] / pt.f,
+                                                       r["block_err"] / p.L / pt.f, pt.f, time.time() - t0), flush=True)
+        if want_runs:
+            with open(path + ".runs.pkl", "wb") as f:
+                pickle.dump([dict(eps=pt.eps, frames=pt.f, **pt.runs) for pt in points], f)
+    if first_bad is not None:
+        abort_invariant()
+    return 0
+
+
+def _ensemble_and_grid(prog, opts):
+    """The ensemble and the ε grid of a command line: the program's shipped #defines where no option overrides them."""
     d = DEFAULTS[prog]
     N = opts.N if opts.N else d["N"]
     L = opts.L if opts.L else d["L"]
@@ -1032,7 +1236,12 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
                     opts.num_points if opts.num_points else g.num_points,
                     opts.min_frame_err if opts.min_frame_err is not None else g.min_frame_err,
                     opts.max_frames if opts.max_frames else g.max_frames)
-    p = E.make_params(opts.dv, opts.dc, L, N)
+    return E.make_params(opts.dv, opts.dc, L, N), grid
+
+
+def run_program(prog, index, W, num_doped, max_it, extra, opts):
+    """The body of main_terminated for one of the three executables."""
+    p, grid = _ensemble_and_grid(prog, opts)
     # argv quirk kept: main_terminated reads the doped positions starting at argv[4], which is also
     # MAX_IT (BPF:2083-2091) — so with NUM_DOPED > 0 the first doped position equals MAX_IT.
     tail = [max_it] + list(opts.doped_argv)
@@ -1071,6 +1280,8 @@ def run_program(prog, index, W, num_doped, max_it, extra, opts):
     by_points = shard == "points" and world > 1
     replica = index + rank if shard == "replicas" else index
     want_runs = _check_runs(prog, opts)
+    if _check_eps_fused(prog, opts):
+        return _run_eps_fused(prog, index, W, max_it, opts, p, grid, doped, want_runs)
     if getattr(opts, "caps", None) and prog == "bp_lim_iter":
         return _run_caps(prog, index, W, num_doped, max_it, extra, opts, p, grid, doped, shard, by_points)
     # the decoders' loop is do { … } while (iter < MaxNumIt) (BPF:1065, BPT:1076): at least one iteration runs
@@ -1302,6 +1513,14 @@ def _parser(prog):
                     help="bp_lim_iter, sw_lim_iter: also write <result file>.runs.pkl, a pickled list with one dict per ε point "
                          "{eps, frames, pos, run_hist, fail_hist}: where the failed positions of the point's frames sit and how "
                          "long their runs are (engine.chain_runs; include/scldpc_runs.h); the .dat is unchanged.  Not with --caps")
+    ap.add_argument("--eps-fused", choices=("auto", "on", "off"), default="auto",
+                    help="bp_lim_iter --schedule fixpoint with MAX_IT >= 10^6: every ε point of the grid from ONE sampled code per "
+                         "frame and one decoder launch per batch (engine.channel_levels + engine.full_bp_eps).  NOT the same "
+                         "file: every point decodes the codes of point 0 (frame f of every point is keyed as frame f of point "
+                         "0), so row 0 is the unfused row 0 and every row k is the unfused program's point-0 run at ε_k — "
+                         "another sample of the same distribution than the unfused row k, and positively correlated with the "
+                         "other rows (common random numbers).  off, and auto for now: one sampler and one decode per point.  "
+                         "'on' where it cannot apply is an error that says why")
     ap.add_argument("--shard", choices=("auto", "points", "frames"), default="auto",
                     help="multi-GPU: ε points over the ranks (the reference's cluster model; default when there are at "
                          "least as many points as ranks) or the frames of every point")
@@ -1317,6 +1536,7 @@ def _parser(prog):
 def main(prog, argv=None):
     opts = _parser(prog).parse_args(argv)
     _check_runs(prog, opts)
+    _check_eps_fused(prog, opts)
     if opts.seed is None:
         opts.seed = int((time.time() % 1) * 1e6)                      # te.tv_usec (BPF:2061)
     joined = E.init_distributed()                                     # one process per GPU under torch.distributed.run

@@ -743,6 +743,42 @@ def peel_sweep_eps(p, d_adj, d_levels, npoints, total_size, lost_lo=0, lost_hi=N
     return {"out": out, "lost": lost}
 
 
+def full_bp_eps_workspace_bytes(p, ntrials, adj16):
+    """Bytes of workspace full_bp_eps needs for ntrials trials (0: the CN words stay in LDS); ScldpcError for a shape the
+    entry refuses.  Needs no device."""
+    nbytes = lib().scldpc_full_bp_eps_workspace_query(C.byref(p), int(ntrials), 1 if adj16 else 0)
+    if nbytes < 0:
+        check(int(nbytes))
+    return int(nbytes)
+
+
+def full_bp_eps(p, d_adj, d_levels, npoints, is_term=True, want_erased=False, counters=None):
+    """full_bp_fixpoint at every point of a descending eps grid in one launch: the code d_adj once, the channel as levels
+    (channel_levels), stage k peeling on from the residual of stage k - 1.  Returns dict with counters int32 [K, T, 8] —
+    counters[k] is full_bp_fixpoint's block for the channel of point k except column 5 (the peeling rounds of stage k), what
+    accumulate_run reads — and `erased` int32 [K, T, nw] or None (scldpc_full_bp_eps_device).  counters: a contiguous int32
+    [K, T, 8] tensor to write into."""
+    _require_gpu()
+    T, K = d_adj.shape[0], int(npoints)
+    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
+    assert tuple(d_adj.shape[1:]) == (p.n, p.dv)
+    assert d_levels.is_cuda and d_levels.dtype == torch.uint8 and d_levels.is_contiguous() and d_levels.shape == (T, p.n)
+    dev = d_adj.device
+    adj16 = _is_adj16(d_adj)
+    nbytes = full_bp_eps_workspace_bytes(p, T, adj16)                    # (also refuses the shape before anything is allocated)
+    shape = (max(K, 0), T, NCOUNTERS)
+    if counters is None:
+        counters = _uninit(shape, dtype=torch.int32, device=dev)
+    assert counters.is_cuda and counters.is_contiguous() and counters.dtype == torch.int32 and tuple(counters.shape) == shape
+    erased = _uninit((max(K, 0), T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
+    ws = _uninit(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    fn = lib().scldpc_full_bp_eps_device_adj16 if adj16 else lib().scldpc_full_bp_eps_device
+    check(fn(C.byref(p), T, d_adj.data_ptr(), d_levels.data_ptr(), K, 1 if is_term else 0, counters.data_ptr(),
+             erased.data_ptr() if erased is not None else None, ws.data_ptr() if ws is not None else None, nbytes,
+             _stream_ptr(dev)))
+    return {"counters": counters, "erased": erased}
+
+
 def peel_sweep_sock16_supported(p):
     """The pairs (3,6), (4,8), (5,10) with 16-bit sockets and at most 65536 CNs per trial: peel_sweep_sock16 takes the ensemble
     (scldpc_peel_sweep_sock16_supported).  Needs no device."""
