@@ -4,6 +4,8 @@
 // and limit checks, the ladder Packed -> Wide -> WideG with its workspace, the prebuild switch, the launch itself).
 // Every device function is inlined into its kernel.  The release lambdas and the round loops are NOT here: they differ in what
 // they count and when they stop, and stay in their kernels (profiles/flood_common_static.txt has the generated code's figures).
+// The two eps-grid decoders (peel_sweep_eps.hip, full_bp_eps.hip) do share theirs, which count the same things: eps_stages.h, on
+// top of this header, has their walk over the stages as one kernel template and their launch front.
 #pragma once
 #include "common.h"
 #include "kernel_util.h"

@@ -712,13 +712,17 @@ def channel_levels(p, seed, trial0, ntrials, es_desc, doped=(), device="cuda:0",
     return d_lev
 
 
-def peel_sweep_eps_workspace_bytes(p, ntrials, adj16):
-    """Bytes of workspace peel_sweep_eps needs for ntrials trials (0: the CN words stay in LDS); ScldpcError for a shape the
-    entry refuses.  Needs no device."""
-    nbytes = lib().scldpc_peel_sweep_eps_workspace_query(C.byref(p), int(ntrials), 1 if adj16 else 0)
+def _eps_workspace_bytes(query, p, ntrials, adj16):
+    nbytes = getattr(lib(), query)(C.byref(p), int(ntrials), 1 if adj16 else 0)
     if nbytes < 0:
         check(int(nbytes))
     return int(nbytes)
+
+
+def peel_sweep_eps_workspace_bytes(p, ntrials, adj16):
+    """Bytes of workspace peel_sweep_eps needs for ntrials trials (0: the CN words stay in LDS); ScldpcError for a shape the
+    entry refuses.  Needs no device."""
+    return _eps_workspace_bytes("scldpc_peel_sweep_eps_workspace_query", p, ntrials, adj16)
 
 
 def peel_sweep_eps(p, d_adj, d_levels, npoints, total_size, lost_lo=0, lost_hi=None, want_lost=False):
@@ -746,10 +750,7 @@ def peel_sweep_eps(p, d_adj, d_levels, npoints, total_size, lost_lo=0, lost_hi=N
 def full_bp_eps_workspace_bytes(p, ntrials, adj16):
     """Bytes of workspace full_bp_eps needs for ntrials trials (0: the CN words stay in LDS); ScldpcError for a shape the
     entry refuses.  Needs no device."""
-    nbytes = lib().scldpc_full_bp_eps_workspace_query(C.byref(p), int(ntrials), 1 if adj16 else 0)
-    if nbytes < 0:
-        check(int(nbytes))
-    return int(nbytes)
+    return _eps_workspace_bytes("scldpc_full_bp_eps_workspace_query", p, ntrials, adj16)
 
 
 def full_bp_eps(p, d_adj, d_levels, npoints, is_term=True, want_erased=False, counters=None):

@@ -5,6 +5,10 @@ side; each child times every kernel with device synchronisation around a fixed n
 
     python tools/ab_flood_common.py --parent-lib /path/to/parent/libscldpc_hip.so [--reps 5] [--bench] > profiles/flood_common_ab.txt
 
+--set eps times the eps-grid decoders instead (csrc/eps_stages.h against its parent): engine.peel_sweep_eps on the nine-point grid
+of tools/eps_fused_speed.py and engine.full_bp_eps on the 26-point grid of tools/bp_eps_fused_speed.py, the decoder launch alone on
+one sampled code and its levels, written to profiles/eps_walk_ab.txt.
+
 A kernel passes when this tree's median lies inside the range the parent's own repetitions span, or below it."""
 import argparse
 import hashlib
@@ -20,7 +24,7 @@ BENCHES = (("bench.py --config C2 --flooding --gen1", ["--config", "C2", "--floo
            ("bench.py --config C2 --gen1", ["--config", "C2", "--gen1"]))
 
 
-def child():
+def child(kset):
     import torch
     sys.path.insert(0, ROOT)
     from fl_scaling_sc_ldpc_amd import engine as E
@@ -36,6 +40,25 @@ def child():
         for k in outs(r): h.update(k.cpu().numpy().tobytes())
         print(json.dumps({"kernel": name, "ms": ms, "sha": h.hexdigest()[:12]}), flush=True)
 
+    if kset == "eps":
+        grids = (("peel_sweep_eps", [round(0.48 - 0.005 * k, 3) for k in range(9)]),
+                 ("full_bp_eps", [0.48 - k * 0.00125 for k in range(26)]))
+        for dv, dc, N, T, calls, what in ((4, 8, 1000, 2048, 20, "packed words, dv = 4"), (3, 6, 1000, 2048, 20, "generic dv"),
+                                          (4, 8, 5000, 512, 5, "CN words in the workspace")):
+            g = PD._Geometry(dv, dc, 50, N, True, True, [])
+            p = g.params
+            a, _ = E.sample_philox(p, 3, 0, T, 0.48, adj16=True)
+            for name, es in grids:
+                lev = E.channel_levels(p, 3, 0, T, es)
+                if name == "peel_sweep_eps":
+                    fn, outs = (lambda: E.peel_sweep_eps(p, a, lev, len(es), g.total_size, g.lost_lo, g.lost_hi)), lambda r: [r["out"]]
+                else:
+                    fn, outs = (lambda: E.full_bp_eps(p, a, lev, len(es))), lambda r: [r["counters"]]
+                timed("%s (%d,%d) L=50 N=%d, %d points from 0.48, %d trials, 2-byte table (%s)" % (name, dv, dc, N, len(es), T, what),
+                      calls, fn, outs)
+            del a, lev
+            torch.cuda.empty_cache()
+        return
     T = 2048
     p = E.make_params(4, 8, 50, 1000)
     a, ch = E.sample_philox(p, 3, 0, T, 0.48, adj16=True)
@@ -74,17 +97,19 @@ def main():
     ap.add_argument("--parent-lib")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--bench", action="store_true", help="also bench.py --config C2 [--flooding] --gen1 on both sides")
+    ap.add_argument("--set", choices=("flood", "eps"), default="flood", help="which kernels the children time")
     ap.add_argument("--child", action="store_true")
     a = ap.parse_args()
     if a.child:
-        return child()
+        return child(a.set)
     sides = (("parent", a.parent_lib), ("this", os.path.join(ROOT, "fl_scaling_sc_ldpc_amd", "libscldpc_hip.so")))
     runs, order = {}, []
     for rep in range(a.reps):
         for side, lib in sides:
             env = dict(os.environ, SCLDPC_LIB_PATH=lib)
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, check=True, capture_output=True,
-                                 text=True, timeout=600).stdout
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--set", a.set], env=env, check=True,
+                                 capture_output=True, text=True, timeout=600).stdout
+            print("repetition %d, %s: done" % (rep + 1, side), file=sys.stderr, flush=True)
             for line in out.splitlines():
                 if line.startswith("{"):
                     r = json.loads(line)
