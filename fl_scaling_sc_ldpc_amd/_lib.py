@@ -100,6 +100,13 @@ EPS_MAX_POINTS = 64             # SCLDPC_EPS_MAX_POINTS
 # every symbol the extension header include/scldpc_bp_eps.h declares (the same shared object; tests/test_bp_eps_host.py)
 EXPORTS_BP_EPS = ("scldpc_full_bp_eps_device", "scldpc_full_bp_eps_device_adj16", "scldpc_full_bp_eps_workspace_query")
 
+# every symbol the extension header include/scldpc_thresh.h declares (the same shared object; tests/test_thresh_host.py)
+EXPORTS_THRESH = ("scldpc_channel_keys_device", "scldpc_frame_threshold_device", "scldpc_frame_threshold_device_adj16",
+                  "scldpc_frame_threshold_workspace_query")
+THRESH_NCOLS = 8                # SCLDPC_THRESH_NCOLS
+THRESH_MAX = 2147483647         # SCLDPC_THRESH_MAX
+THRESH_NAMES = ("thresh", "status", "size", "first_pos", "last_pos", "stages", "rescans", "channel_erasures")
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -243,6 +250,11 @@ def lib():
     L.scldpc_full_bp_eps_device_adj16.argtypes = L.scldpc_full_bp_eps_device.argtypes
     L.scldpc_full_bp_eps_workspace_query.argtypes = [pp, i32, i32]
     L.scldpc_full_bp_eps_workspace_query.restype = i64
+    L.scldpc_channel_keys_device.argtypes = [pp, u64, u64, i32, i32, vp, vp, vp]
+    L.scldpc_frame_threshold_device.argtypes = [pp, i32, vp, vp, u32, u32, i32, vp, vp, vp, u64, vp]
+    L.scldpc_frame_threshold_device_adj16.argtypes = L.scldpc_frame_threshold_device.argtypes
+    L.scldpc_frame_threshold_workspace_query.argtypes = [pp, i32, i32]
+    L.scldpc_frame_threshold_workspace_query.restype = i64
     L.scldpc_swc_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_swc_bp_device_adj16.argtypes = L.scldpc_swc_bp_device.argtypes
     L.scldpc_stream_supported.argtypes = [pp, i32]

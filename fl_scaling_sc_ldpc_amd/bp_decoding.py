@@ -65,6 +65,13 @@ gives at ε_k — another sample of the same distribution than the unfused row k
 (common random numbers).  `off`, and `auto` while BP_EPS_FUSED_BY_DEFAULT is False, write the unfused file.  With --runs the
 .runs.pkl has the same layout, over the frames each point consumed.
 
+`bp_thresholds INDEX W NUM_DOPED FRAMES [doped…]` (no counterpart in the reference; W = 0) takes the nesting to its end: not a
+grid but, for every frame trial_key(INDEX, 0, f), the one integer threshold T* at which unlimited full BP starts to fail
+(run_thresholds: engine.channel_keys + engine.frame_threshold, a bisection on the device inside the residual of the decode at
+--eps-hi).  The frame fails at ε iff T* <= erasure_threshold(ε), so the rows give FER(ε) at every ε of [--eps-lo, --eps-hi] from
+the same frames, the moments of ε*, and the stopping set that kills each frame; rank 0 pickles them to
+`<bp_lim_iter's result file at MAX_IT 1000000>.thresholds.pkl`.
+
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
@@ -1225,6 +1232,110 @@ def _run_eps_fused(prog, index, W, max_it, opts, p, grid, doped, want_runs):
     return 0
 
 
+class FrameThresholds:
+    """What run_thresholds returns: one row per frame, in frame order.
+      rows    int64 [frames, 8], engine.frame_threshold's columns (E.THRESH_NAMES): thresh, status, size, first_pos, last_pos,
+              stages, rescans, channel_erasures
+      t_lo, t_hi   the window as integer thresholds, erasure_threshold(eps_lo) and erasure_threshold(eps_hi)
+      bits    uint32 [frames, nw], the critical residuals (run_thresholds(want_bits=True)), else None"""
+
+    def __init__(self, rows, t_lo, t_hi, bits=None):
+        self.rows, self.t_lo, self.t_hi, self.bits = rows, int(t_lo), int(t_hi), bits
+
+    def eps_star(self):
+        """float64 [frames]: thresh / RAND_MAX of the frames whose threshold lies in the window, nan where it is censored
+        (status 1: above the window; status 2: at or below its lower end)."""
+        out = np.full(len(self.rows), np.nan)
+        inside = self.rows[:, 1] == 0
+        out[inside] = self.rows[inside, 0] / 2147483647.0
+        return out
+
+    def fer_at(self, es):
+        """int64 [len(es)]: the number of frames that fail at each ε — status 2, or status 0 with thresh <=
+        erasure_threshold(ε): what unlimited full BP of the same frames at ε counts as frame errors.  ValueError for an ε whose
+        threshold lies outside [t_lo, t_hi], where the rows do not decide it."""
+        thresh, status = self.rows[:, 0], self.rows[:, 1]
+        out = []
+        for e in np.asarray(es, dtype=np.float64).reshape(-1):
+            th = E.erasure_threshold(e)
+            if not self.t_lo <= th <= self.t_hi:
+                raise ValueError("thresholds: ε = %.17g (threshold %d) lies outside the window [%d, %d]" % (e, th, self.t_lo, self.t_hi))
+            out.append(int(((status == 2) | ((status == 0) & (thresh <= th))).sum()))
+        return np.array(out, dtype=np.int64)
+
+
+def run_thresholds(p, eps_lo, eps_hi, frames, seed, index=0, is_term=True, doped=(), batch=2048, device=None, shard_frames=True,
+                   want_bits=False, verbose=False):
+    """The exact erasure threshold of every frame under unlimited full BP, for the window [eps_lo, eps_hi]: a FrameThresholds
+    over the frames f = 0 … frames - 1, keyed trial_key(index, 0, f) — the codes and draws run_grid_fused decodes, so that
+    .fer_at(es) is the frame_err column of run_grid_fused(p, es, 0, frames, seed, index=index, …), point for point, at every ε
+    of the window and without a grid.
+
+    Per round: one first-generation sampler call at eps_hi for the codes (2-byte rows where the sampler offers them; its
+    channel is not used), engine.channel_keys, one engine.frame_threshold (the decode at erasure_threshold(eps_hi), then a
+    bisection on the integer threshold inside its residual).  Rounds and the frame split over the ranks are run_point's
+    (split_round); under torch.distributed one all-gather per round carries the [m, 8] rows.  A shape the entry refuses is a
+    ValueError("thresholds: …") with the library's text, before anything is allocated."""
+    t_lo, t_hi = E.erasure_threshold(eps_lo), E.erasure_threshold(eps_hi)
+    if not (0.0 <= float(eps_lo) <= 1.0 and 0.0 <= float(eps_hi) <= 1.0 and t_lo < t_hi):
+        raise ValueError("thresholds: the window needs 0 <= eps_lo < eps_hi <= 1 with two distinct thresholds (got [%.17g, %.17g])"
+                         % (eps_lo, eps_hi))
+    frames = int(frames)
+    if frames < 0:
+        raise ValueError("thresholds: a negative number of frames (%d)" % frames)
+    adj16 = p.cns_pos <= 65536
+    try:
+        E.frame_threshold_workspace_bytes(p, 1, adj16)
+    except E.ScldpcError as err:
+        raise ValueError("thresholds: %s" % err)
+    dist, rank, W = _dist() if shard_frames else (None, 0, 1)
+    device = torch.device(device) if device is not None else E.local_device()
+    if verbose:
+        print("[scldpc] kernels: sampler (first generation) + channel_keys + frame_threshold (window [%d, %d])" % (t_lo, t_hi),
+              file=sys.stderr, flush=True)
+    NC = E.THRESH_NCOLS
+    B, doped = int(batch), tuple(doped)
+    d_adj = torch.empty((B, p.n, p.dv), dtype=torch.int16 if adj16 else torch.int32, device=device)
+    d_ch = torch.empty((B, p.nw), dtype=torch.int32, device=device)
+    d_keys = torch.empty((B, p.n), dtype=torch.int32, device=device)
+    d_rows = torch.empty((B, NC), dtype=torch.int32, device=device)
+    all_rows, all_bits = [], []
+    frame0 = 0
+    while frame0 < frames:
+        R, sizes, offs = Simulator.split_round(frames - frame0, B, W)
+        nb, off = sizes[rank], offs[rank]
+        res = None
+        if nb:
+            key = trial_key(index, 0, frame0 + off)
+            E.sample_philox(p, seed, key, nb, eps_hi, doped, out=(d_adj[:nb], d_ch[:nb]))
+            E.channel_keys(p, seed, key, nb, doped, device=device, out=d_keys[:nb])
+            res = E.frame_threshold(p, d_adj[:nb], d_keys[:nb], t_lo, t_hi, is_term=is_term, want_bits=want_bits, rows=d_rows[:nb])
+        if W > 1:
+            m = max(sizes)
+
+            def gather(mine_part, width):
+                mine = torch.zeros((m, width), dtype=torch.int32, device=device)
+                if nb:
+                    mine[:nb] = mine_part
+                got = [torch.empty_like(mine) for _ in range(W)]
+                dist.all_gather(got, mine)
+                return torch.cat([g[:s] for g, s in zip(got, sizes)], dim=0)
+            all_rows.append(gather(res["rows"] if nb else None, NC).cpu())
+            if want_bits:
+                all_bits.append(gather(res["bits"] if nb else None, p.nw).cpu())
+        else:
+            all_rows.append(res["rows"].to("cpu", copy=True))                # (a copy: d_rows is written again in the next round)
+            if want_bits:
+                all_bits.append(res["bits"].to("cpu", copy=True))
+        frame0 += R
+    rows = (torch.cat(all_rows, dim=0).numpy().astype(np.int64) if all_rows else np.zeros((0, NC), dtype=np.int64))
+    bits = None
+    if want_bits:
+        bits = (np.ascontiguousarray(torch.cat(all_bits, dim=0).numpy()).view(np.uint32) if all_bits
+                else np.zeros((0, p.nw), dtype=np.uint32))
+    return FrameThresholds(rows, t_lo, t_hi, bits)
+
+
 def _ensemble_and_grid(prog, opts):
     """The ensemble and the ε grid of a command line: the program's shipped #defines where no option overrides them."""
     d = DEFAULTS[prog]
@@ -1561,6 +1672,99 @@ def bp_traj(argv=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# bp_thresholds: the exact erasure threshold of every frame (no counterpart in the reference)
+# ------------------------------------------------------------------------------------------------
+def _thresholds_parser():
+    g = DEFAULTS["bp_lim_iter"]["grid"]
+    ap = argparse.ArgumentParser(prog="bp_thresholds",
+                                 description="exact per-frame erasure thresholds of unlimited full BP: for every frame the least "
+                                             "integer threshold at which the decoder leaves a residual, bisected on the device")
+    ap.add_argument("INDEX", type=int)
+    ap.add_argument("W", type=int, help="0: full BP (a window decoder's result depends on the schedule, not on the stopping sets)")
+    ap.add_argument("NUM_DOPED", type=int)
+    ap.add_argument("FRAMES", type=int, help="frames 0 … FRAMES - 1 of the replica: the codes of bp_lim_iter's point 0")
+    ap.add_argument("doped_argv", nargs="*", type=int, help="the NUM_DOPED doped positions")
+    ap.add_argument("--dv", type=int, default=4)
+    ap.add_argument("--dc", type=int, default=8)
+    ap.add_argument("--L", type=int, default=0, help="Def_L (default: bp_lim_iter's)")
+    ap.add_argument("--N", type=int, default=0, help="VNs per position (default: bp_lim_iter's)")
+    ap.add_argument("--eps-lo", type=float, default=g.eps(g.num_points - 1), help="lower end of the window (default: the last "
+                                                                                  "point of bp_lim_iter's grid)")
+    ap.add_argument("--eps-hi", type=float, default=g.eps(0), help="upper end of the window (default: the first point of that grid)")
+    ap.add_argument("--is-term", type=int, default=1, help="0: the truncated chain (the CNs beyond position L never fire)")
+    ap.add_argument("--batch", type=int, default=2048, help="frames per device batch and rank")
+    ap.add_argument("--seed", type=int, default=None, help="default: time-based, as bp_lim_iter's")
+    ap.add_argument("--outdir", default=".")
+    ap.add_argument("--quiet", action="store_true")
+    return ap
+
+
+def _check_thresholds(opts):
+    """The command line of bp_thresholds against what the run can do: exits with `bp_thresholds: <reason>` (before any device
+    work), else (p, doped)."""
+    def refuse(why):
+        raise SystemExit("bp_thresholds: " + why)
+    d = DEFAULTS["bp_lim_iter"]
+    if opts.W != 0:
+        refuse("W = %d: a threshold is defined for unlimited full BP only (W = 0); a window decoder's result depends on its "
+               "schedule" % opts.W)
+    if opts.FRAMES < 1:
+        refuse("FRAMES = %d: at least one frame" % opts.FRAMES)
+    if not (0.0 <= opts.eps_lo < opts.eps_hi <= 1.0) or E.erasure_threshold(opts.eps_lo) >= E.erasure_threshold(opts.eps_hi):
+        refuse("the window needs 0 <= --eps-lo < --eps-hi <= 1 with two distinct thresholds (got [%.17g, %.17g])"
+               % (opts.eps_lo, opts.eps_hi))
+    if opts.batch < 1:
+        refuse("--batch %d: at least one frame per batch" % opts.batch)
+    try:
+        p = E.make_params(opts.dv, opts.dc, opts.L if opts.L else d["L"], opts.N if opts.N else d["N"])
+    except ValueError as err:
+        refuse(str(err))
+    # (bp_lim_iter's argv quirk — its first doped position is MAX_IT, BPF:2083-2091 — has nothing to mirror here)
+    if opts.NUM_DOPED < 0 or len(opts.doped_argv) < opts.NUM_DOPED:
+        refuse("NUM_DOPED=%d but only %d position arguments" % (opts.NUM_DOPED, len(opts.doped_argv)))
+    doped = [int(x) for x in opts.doped_argv[:opts.NUM_DOPED]]
+    if any(not 0 <= x < p.L for x in doped):
+        refuse("doped positions outside [0,%d): %s" % (p.L, doped))
+    try:
+        E.frame_threshold_workspace_bytes(p, 1, p.cns_pos <= 65536)        # the entry's own shape rule; needs no device
+    except E.ScldpcError as err:
+        refuse(str(err))
+    return p, doped
+
+
+def bp_thresholds(argv=None):
+    """`bp_thresholds INDEX W NUM_DOPED FRAMES [doped…]`: run_thresholds over the frames of the replica; rank 0 pickles
+    dict(eps_lo, eps_hi, t_lo, t_hi, seed, index, rows) to <bp_lim_iter's result file at MAX_IT 1000000>.thresholds.pkl."""
+    opts = _thresholds_parser().parse_args(argv)
+    p, doped = _check_thresholds(opts)
+    if opts.seed is None:
+        opts.seed = int((time.time() % 1) * 1e6)
+    joined = E.init_distributed()
+    dist, rank, world = _dist()
+    res = run_thresholds(p, opts.eps_lo, opts.eps_hi, opts.FRAMES, opts.seed, index=opts.INDEX, is_term=bool(opts.is_term),
+                         doped=doped, batch=opts.batch, verbose=rank == 0 and not opts.quiet)
+    if rank == 0:
+        os.makedirs(opts.outdir, exist_ok=True)
+        path = os.path.join(opts.outdir, result_filename("bp_lim_iter", p, 0, 1000000, 0, opts.INDEX) + ".thresholds.pkl")
+        with open(path, "wb") as f:
+            pickle.dump(dict(eps_lo=opts.eps_lo, eps_hi=opts.eps_hi, t_lo=res.t_lo, t_hi=res.t_hi, seed=opts.seed, index=opts.INDEX,
+                             rows=res.rows), f)
+        if not opts.quiet:
+            status = res.rows[:, 1]
+            share = [float((status == s).mean()) for s in (0, 1, 2)]
+            es = res.eps_star()[status == 0]
+            print("frames %d   inside the window %.4f   above (decode at eps_hi) %.4f   at or below eps_lo %.4f"
+                  % (len(status), share[0], share[1], share[2]), flush=True)
+            if es.size:
+                print("eps*: mean %.6f   std %.6f   (%d uncensored frames)" % (es.mean(), es.std(ddof=1) if es.size > 1 else 0.0,
+                                                                              es.size), flush=True)
+    if joined:
+        import torch.distributed as dist_mod
+        dist_mod.destroy_process_group()
+    return 0
+
+
+# ------------------------------------------------------------------------------------------------
 # streaming mode: the CIRCULAR build of the reference (`sw INDEX W NUM_DOPED DOPED_POSITIONS…`, BPF:1934-2054)
 # ------------------------------------------------------------------------------------------------
 STREAM_HEADER = ("p BER BLER BER_EXP BLER_EXP bit_err bit_gen block_err block_gen bit_err_exp bit_gen_exp "
@@ -1729,6 +1933,8 @@ def streaming(argv=None):
 if __name__ == "__main__":
     if len(sys.argv) >= 2 and sys.argv[1] == "sw":
         sys.exit(streaming(sys.argv[2:]))
+    if len(sys.argv) >= 2 and sys.argv[1] == "bp_thresholds":
+        sys.exit(bp_thresholds(sys.argv[2:]))
     if len(sys.argv) < 2 or sys.argv[1] not in DEFAULTS:
-        raise SystemExit("usage: python -m fl_scaling_sc_ldpc_amd.bp_decoding {bp_lim_iter|sw_lim_iter|bp_traj|sw} ARGS…")
+        raise SystemExit("usage: python -m fl_scaling_sc_ldpc_amd.bp_decoding {bp_lim_iter|sw_lim_iter|bp_traj|sw|bp_thresholds} ARGS…")
     sys.exit(main(sys.argv[1], sys.argv[2:]))

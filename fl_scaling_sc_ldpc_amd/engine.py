@@ -14,7 +14,8 @@ import torch
 
 from . import _lib
 from ._lib import (CodeParams, MAX_CAPS, NCOUNTERS, NRUN, NPEELRUN, COUNTER_NAMES, RUN_NAMES, PEELRUN_NAMES, ScldpcError,  # noqa: F401
-                   SS_MAX_BINS, SS_POS_SIZES, RUNS_MAX_L, RUNS_MAX_BINS, RUNS_MAX_PERIOD, RUNS_CARRY, EPS_MAX_POINTS, check, lib)
+                   SS_MAX_BINS, SS_POS_SIZES, RUNS_MAX_L, RUNS_MAX_BINS, RUNS_MAX_PERIOD, RUNS_CARRY, EPS_MAX_POINTS, THRESH_NCOLS, THRESH_MAX,
+                   THRESH_NAMES, check, lib)
 
 
 def make_params(dv=4, dc=8, L=50, N=1000):
@@ -778,6 +779,55 @@ def full_bp_eps(p, d_adj, d_levels, npoints, is_term=True, want_erased=False, co
              erased.data_ptr() if erased is not None else None, ws.data_ptr() if ws is not None else None, nbytes,
              _stream_ptr(dev)))
     return {"counters": counters, "erased": erased}
+
+
+def channel_keys(p, seed, trial0, ntrials, doped=(), device="cuda:0", out=None):
+    """The 31-bit channel keys of trials trial0 .. trial0 + ntrials - 1: int32 [T, n] holding uint32 bit patterns, key[j] = the
+    draw >> 1 the samplers compare with the erasure threshold, -1 (0xFFFFFFFF, never erased) in a doped position — so that
+    pack(key.view(uint32) < erasure_threshold(eps)) is the channel sample_philox writes at eps on the same (seed, trial, doped),
+    for every eps (scldpc_channel_keys_device)."""
+    _require_gpu()
+    d_keys = _uninit((ntrials, p.n), dtype=torch.int32, device=device) if out is None else out
+    darr, dptr = _lib.doped_array(doped)
+    check(lib().scldpc_channel_keys_device(C.byref(p), int(seed), int(trial0), int(ntrials), darr.size, dptr, d_keys.data_ptr(),
+                                           _stream_ptr(d_keys.device)))
+    return d_keys
+
+
+def frame_threshold_workspace_bytes(p, ntrials, adj16):
+    """Bytes of workspace frame_threshold needs for ntrials frames (0: the CN words stay in LDS); ScldpcError for a shape the
+    entry refuses.  Needs no device."""
+    return _eps_workspace_bytes("scldpc_frame_threshold_workspace_query", p, ntrials, adj16)
+
+
+def frame_threshold(p, d_adj, d_keys, t_lo, t_hi, is_term=True, want_bits=False, rows=None):
+    """The critical erasure threshold of every frame under unlimited full BP: VN j of frame f is erased at threshold t iff
+    d_keys[f, j] (as uint32; channel_keys, or any keys) < t, and T*(f) is the least t in (t_lo, t_hi] at which full_bp without a
+    cap leaves a residual, found by bisection inside the residual of the decode at t_hi.  Returns dict with rows int32 [T, 8] —
+    _lib.THRESH_NAMES: [0] T* (status 0), t_lo (status 2) or -1 (status 1); [1] status 0: t_lo < T* <= t_hi, 1: decodes at t_hi,
+    2: fails at t_lo; [2] the size of the critical residual, [3], [4] its first and last position; [5] stages, [6] re-scans;
+    [7] #VNs erased at t_hi — and `bits` int32 [T, nw], the critical residual in the layout of `erased`, or None
+    (scldpc_frame_threshold_device).  rows: a contiguous int32 [T, 8] tensor to write into."""
+    _require_gpu()
+    if not 0 <= int(t_lo) <= 0xFFFFFFFF or not 0 <= int(t_hi) <= 0xFFFFFFFF:
+        raise ValueError("frame_threshold: the thresholds are unsigned 32-bit integers (got t_lo = %d, t_hi = %d)" % (t_lo, t_hi))
+    T = d_adj.shape[0]
+    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
+    assert tuple(d_adj.shape[1:]) == (p.n, p.dv)
+    assert d_keys.is_cuda and d_keys.dtype == torch.int32 and d_keys.is_contiguous() and d_keys.shape == (T, p.n)
+    dev = d_adj.device
+    adj16 = _is_adj16(d_adj)
+    nbytes = frame_threshold_workspace_bytes(p, T, adj16)               # (also refuses the shape before anything is allocated)
+    shape = (T, _lib.THRESH_NCOLS)
+    if rows is None:
+        rows = _uninit(shape, dtype=torch.int32, device=dev)
+    assert rows.is_cuda and rows.is_contiguous() and rows.dtype == torch.int32 and tuple(rows.shape) == shape
+    bits = _uninit((T, p.nw), dtype=torch.int32, device=dev) if want_bits else None
+    ws = _uninit(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    fn = lib().scldpc_frame_threshold_device_adj16 if adj16 else lib().scldpc_frame_threshold_device
+    check(fn(C.byref(p), T, d_adj.data_ptr(), d_keys.data_ptr(), int(t_lo), int(t_hi), 1 if is_term else 0, rows.data_ptr(),
+             bits.data_ptr() if bits is not None else None, ws.data_ptr() if ws is not None else None, nbytes, _stream_ptr(dev)))
+    return {"rows": rows, "bits": bits}
 
 
 def peel_sweep_sock16_supported(p):
