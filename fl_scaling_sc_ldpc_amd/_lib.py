@@ -107,6 +107,13 @@ THRESH_NCOLS = 8                # SCLDPC_THRESH_NCOLS
 THRESH_MAX = 2147483647         # SCLDPC_THRESH_MAX
 THRESH_NAMES = ("thresh", "status", "size", "first_pos", "last_pos", "stages", "rescans", "channel_erasures")
 
+# every symbol the extension header include/scldpc_vn_thresh.h declares (the same shared object; tests/test_vn_thresh_host.py)
+EXPORTS_VN_THRESH = ("scldpc_vn_threshold_device", "scldpc_vn_threshold_device_adj16", "scldpc_vn_threshold_workspace_query")
+VNT_NCOLS = 8                   # SCLDPC_VNT_NCOLS
+VNT_MAX_POINTS = 256            # SCLDPC_VNT_MAX_POINTS
+VNT_NONE = 0xFFFFFFFF           # SCLDPC_VNT_NONE
+VNT_NAMES = ("thresh", "status", "top_size", "size", "steps", "scans", "rescans", "channel_erasures")
+
 
 class ScldpcError(RuntimeError):
     pass
@@ -255,6 +262,10 @@ def lib():
     L.scldpc_frame_threshold_device_adj16.argtypes = L.scldpc_frame_threshold_device.argtypes
     L.scldpc_frame_threshold_workspace_query.argtypes = [pp, i32, i32]
     L.scldpc_frame_threshold_workspace_query.restype = i64
+    L.scldpc_vn_threshold_device.argtypes = [pp, i32, vp, vp, u32, u32, i32, i32, vp, vp, vp, vp, vp, vp, u64, vp]
+    L.scldpc_vn_threshold_device_adj16.argtypes = L.scldpc_vn_threshold_device.argtypes
+    L.scldpc_vn_threshold_workspace_query.argtypes = [pp, i32, i32]
+    L.scldpc_vn_threshold_workspace_query.restype = i64
     L.scldpc_swc_bp_device.argtypes = [pp, i32, vp, vp, i32, i32, vp, vp, vp, u64, vp]
     L.scldpc_swc_bp_device_adj16.argtypes = L.scldpc_swc_bp_device.argtypes
     L.scldpc_stream_supported.argtypes = [pp, i32]

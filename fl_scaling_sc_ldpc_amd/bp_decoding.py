@@ -72,6 +72,13 @@ grid but, for every frame trial_key(INDEX, 0, f), the one integer threshold T* a
 the same frames, the moments of ε*, and the stopping set that kills each frame; rank 0 pickles them to
 `<bp_lim_iter's result file at MAX_IT 1000000>.thresholds.pkl`.
 
+`bp_curves INDEX W NUM_DOPED FRAMES [doped…] [--points K]` (no counterpart in the reference; W = 0) resolves those frames by
+position: for every VN the one integer tau at which it starts to be lost (run_vn_thresholds: engine.channel_keys +
+engine.vn_threshold, one walk down the keys of the residual of the decode at --eps-hi, no rebuild of the CN words), reduced on
+the device to the threshold of every position and the lost VNs at K points.  BER at the K points, and the block error rate of
+every position and FER at every ε of the window, come from the same frames; rank 0 pickles them to
+`<bp_lim_iter's result file at MAX_IT 1000000>.curves.pkl` and prints the K rows in the column order of `risultati`.
+
 All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 """
 import argparse
@@ -1336,6 +1343,139 @@ def run_thresholds(p, eps_lo, eps_hi, frames, seed, index=0, is_term=True, doped
     return FrameThresholds(rows, t_lo, t_hi, bits)
 
 
+class VnThresholds:
+    """What run_vn_thresholds returns: the thresholds of every frame's positions (and VNs), in frame order.
+      rows        int64 [frames, 8], engine.vn_threshold's columns (E.VNT_NAMES): thresh, status, top_size, size, steps, scans,
+                  rescans, channel_erasures
+      pos_thresh  int64 [frames, L]: the least tau over the VNs of the position, E.VNT_NONE where it never fails in the window;
+                  t_lo means "at or below t_lo"
+      counts      int64 [frames, len(grid)]: the VNs lost at each threshold of grid
+      grid        the distinct thresholds of the caller's es, ascending
+      t_lo, t_hi  the window as integer thresholds
+      tau         int64 [frames, n], tau of every VN (run_vn_thresholds(want_tau=True)), else None"""
+
+    def __init__(self, rows, pos_thresh, counts, grid, t_lo, t_hi, tau=None):
+        self.rows, self.pos_thresh, self.counts, self.grid = rows, pos_thresh, counts, [int(t) for t in grid]
+        self.t_lo, self.t_hi, self.tau = int(t_lo), int(t_hi), tau
+
+    def _thresholds(self, es):
+        out = []
+        for e in np.asarray(es, dtype=np.float64).reshape(-1):
+            th = E.erasure_threshold(e)
+            if not self.t_lo <= th <= self.t_hi:
+                raise ValueError("thresholds: ε = %.17g (threshold %d) lies outside the window [%d, %d]" % (e, th, self.t_lo, self.t_hi))
+            out.append(th)
+        return out
+
+    def fer_at(self, es):
+        """int64 [len(es)]: the frames that fail at each ε; FrameThresholds.fer_at of the same frames."""
+        return FrameThresholds(self.rows, self.t_lo, self.t_hi).fer_at(es)
+
+    def bler_at(self, es):
+        """int64 [len(es), L]: the frames in which position q fails at each ε, for any ε of the window."""
+        ths = self._thresholds(es)
+        return np.array([(self.pos_thresh <= th).sum(axis=0) for th in ths], dtype=np.int64).reshape(len(ths), self.pos_thresh.shape[1])
+
+    def block_err_at(self, es):
+        """int64 [len(es)]: the failing positions summed over the frames: the block_err column of the grid decoders."""
+        return self.bler_at(es).sum(axis=1)
+
+    def ber_at(self, es):
+        """int64 [len(es)]: the lost VNs summed over the frames (users_err): for ε whose threshold is on the grid, or for any ε
+        of the window where tau was kept."""
+        out = []
+        for e, th in zip(np.asarray(es, dtype=np.float64).reshape(-1), self._thresholds(es)):
+            if self.tau is not None:
+                out.append(int((self.tau <= th).sum()))
+            elif th in self.grid:
+                out.append(int(self.counts[:, self.grid.index(th)].sum()))
+            else:
+                raise ValueError("thresholds: ε = %.17g (threshold %d) is not on the grid of counts, and tau was not kept" % (e, th))
+        return np.array(out, dtype=np.int64)
+
+    def pos_eps_star(self):
+        """float64 [frames, L]: pos_thresh / RAND_MAX where the position's threshold lies inside the window, nan where it is
+        censored (never fails in the window, or fails at or below its lower end)."""
+        out = np.full(self.pos_thresh.shape, np.nan)
+        inside = (self.pos_thresh > self.t_lo) & (self.pos_thresh <= self.t_hi)
+        out[inside] = self.pos_thresh[inside] / 2147483647.0
+        return out
+
+
+def run_vn_thresholds(p, eps_lo, eps_hi, frames, seed, es=(), index=0, is_term=True, doped=(), batch=2048, device=None,
+                      shard_frames=True, want_tau=False, verbose=False):
+    """The exact erasure threshold of every position (and, with want_tau, of every VN) under unlimited full BP, for the window
+    [eps_lo, eps_hi]: a VnThresholds over the frames run_thresholds decodes, keyed trial_key(index, 0, f), so that bler_at,
+    block_err_at and fer_at give the block_err and frame_err of run_grid_fused on the same frames at every ε of the window, and
+    ber_at its users_err at the points of es (their thresholds, sorted, merged where equal: the grid of `counts`).
+
+    Per round: run_thresholds' sampler call and engine.channel_keys, then one engine.vn_threshold.  Under torch.distributed one
+    all-gather per round carries the rows, positions, counts (and tau) of the round.  A shape the entry refuses, a grid outside
+    the window or of more than E.VNT_MAX_POINTS thresholds is a ValueError("thresholds: …") before anything is allocated."""
+    t_lo, t_hi = E.erasure_threshold(eps_lo), E.erasure_threshold(eps_hi)
+    if not (0.0 <= float(eps_lo) <= 1.0 and 0.0 <= float(eps_hi) <= 1.0 and t_lo < t_hi):
+        raise ValueError("thresholds: the window needs 0 <= eps_lo < eps_hi <= 1 with two distinct thresholds (got [%.17g, %.17g])"
+                         % (eps_lo, eps_hi))
+    frames = int(frames)
+    if frames < 0:
+        raise ValueError("thresholds: a negative number of frames (%d)" % frames)
+    grid = sorted(set(E.erasure_threshold(e) for e in np.asarray(es, dtype=np.float64).reshape(-1)))
+    if grid and not (t_lo <= grid[0] and grid[-1] <= t_hi):
+        raise ValueError("thresholds: the points of es lie outside the window [%d, %d]" % (t_lo, t_hi))
+    if len(grid) > E.VNT_MAX_POINTS:
+        raise ValueError("thresholds: %d distinct thresholds in es, at most %d" % (len(grid), E.VNT_MAX_POINTS))
+    adj16 = p.cns_pos <= 65536
+    try:
+        E.vn_threshold_workspace_bytes(p, 1, adj16)
+    except E.ScldpcError as err:
+        raise ValueError("thresholds: %s" % err)
+    dist, rank, W = _dist() if shard_frames else (None, 0, 1)
+    device = torch.device(device) if device is not None else E.local_device()
+    if verbose:
+        print("[scldpc] kernels: sampler (first generation) + channel_keys + vn_threshold (window [%d, %d], %d grid points)"
+              % (t_lo, t_hi, len(grid)), file=sys.stderr, flush=True)
+    NC, K = E.VNT_NCOLS, len(grid)
+    B, doped = int(batch), tuple(doped)
+    d_adj = torch.empty((B, p.n, p.dv), dtype=torch.int16 if adj16 else torch.int32, device=device)
+    d_ch = torch.empty((B, p.nw), dtype=torch.int32, device=device)
+    d_keys = torch.empty((B, p.n), dtype=torch.int32, device=device)
+    d_rows = torch.empty((B, NC), dtype=torch.int32, device=device)
+    names = ["rows", "pos_thresh"] + (["counts"] if K else []) + (["tau"] if want_tau else [])
+    widths = {"rows": NC, "pos_thresh": p.L, "counts": K, "tau": p.n}
+    parts = {name: [] for name in names}
+    frame0 = 0
+    while frame0 < frames:
+        R, sizes, offs = Simulator.split_round(frames - frame0, B, W)
+        nb, off = sizes[rank], offs[rank]
+        res = None
+        if nb:
+            key = trial_key(index, 0, frame0 + off)
+            E.sample_philox(p, seed, key, nb, eps_hi, doped, out=(d_adj[:nb], d_ch[:nb]))
+            E.channel_keys(p, seed, key, nb, doped, device=device, out=d_keys[:nb])
+            res = E.vn_threshold(p, d_adj[:nb], d_keys[:nb], t_lo, t_hi, grid=grid, is_term=is_term, want_tau=want_tau,
+                                 rows=d_rows[:nb])
+        for name in names:
+            if W > 1:
+                m = max(sizes)
+                mine = torch.zeros((m, widths[name]), dtype=torch.int32, device=device)
+                if nb:
+                    mine[:nb] = res[name]
+                got = [torch.empty_like(mine) for _ in range(W)]
+                dist.all_gather(got, mine)
+                parts[name].append(torch.cat([g[:s] for g, s in zip(got, sizes)], dim=0).cpu())
+            else:
+                parts[name].append(res[name].to("cpu", copy=True))       # (a copy: d_rows is written again in the next round)
+        frame0 += R
+
+    def joined(name, unsigned):
+        if not parts[name]:
+            return np.zeros((0, widths[name]), dtype=np.int64)
+        a = np.ascontiguousarray(torch.cat(parts[name], dim=0).numpy())
+        return (a.view(np.uint32) if unsigned else a).astype(np.int64)
+    return VnThresholds(joined("rows", False), joined("pos_thresh", True), joined("counts", False) if K else np.zeros((frames, 0), dtype=np.int64),
+                        grid, t_lo, t_hi, joined("tau", True) if want_tau else None)
+
+
 def _ensemble_and_grid(prog, opts):
     """The ensemble and the ε grid of a command line: the program's shipped #defines where no option overrides them."""
     d = DEFAULTS[prog]
@@ -1699,11 +1839,12 @@ def _thresholds_parser():
     return ap
 
 
-def _check_thresholds(opts):
-    """The command line of bp_thresholds against what the run can do: exits with `bp_thresholds: <reason>` (before any device
-    work), else (p, doped)."""
+def _check_thresholds(opts, prog="bp_thresholds", workspace_bytes=None):
+    """The command line of `prog` — bp_thresholds, or bp_curves, which shares its arguments — against what the run can do: exits
+    with `<prog>: <reason>` (before any device work), else (p, doped).  workspace_bytes: the workspace query of the program's
+    entry, whose shape rule decides (default: frame_threshold's)."""
     def refuse(why):
-        raise SystemExit("bp_thresholds: " + why)
+        raise SystemExit(prog + ": " + why)
     d = DEFAULTS["bp_lim_iter"]
     if opts.W != 0:
         refuse("W = %d: a threshold is defined for unlimited full BP only (W = 0); a window decoder's result depends on its "
@@ -1726,7 +1867,7 @@ def _check_thresholds(opts):
     if any(not 0 <= x < p.L for x in doped):
         refuse("doped positions outside [0,%d): %s" % (p.L, doped))
     try:
-        E.frame_threshold_workspace_bytes(p, 1, p.cns_pos <= 65536)        # the entry's own shape rule; needs no device
+        (workspace_bytes or E.frame_threshold_workspace_bytes)(p, 1, p.cns_pos <= 65536)   # the entry's own shape rule; needs no device
     except E.ScldpcError as err:
         refuse(str(err))
     return p, doped
@@ -1758,6 +1899,65 @@ def bp_thresholds(argv=None):
             if es.size:
                 print("eps*: mean %.6f   std %.6f   (%d uncensored frames)" % (es.mean(), es.std(ddof=1) if es.size > 1 else 0.0,
                                                                               es.size), flush=True)
+    if joined:
+        import torch.distributed as dist_mod
+        dist_mod.destroy_process_group()
+    return 0
+
+
+# ------------------------------------------------------------------------------------------------
+# bp_curves: BER, FER and block error rate over a window from the exact thresholds of every VN (no counterpart in the reference)
+# ------------------------------------------------------------------------------------------------
+def _curves_parser():
+    ap = _thresholds_parser()
+    ap.prog = "bp_curves"
+    ap.description = ("exact per-position erasure thresholds of unlimited full BP and, from the same frames, BER, FER and block "
+                      "error rate at K evenly spaced points of the window")
+    ap.add_argument("--points", type=int, default=DEFAULTS["bp_lim_iter"]["grid"].num_points,
+                    help="K, the points printed and counted (default: bp_lim_iter's grid)")
+    return ap
+
+
+def _curves_points(opts):
+    """The K points of the command line, descending from --eps-hi; bp_lim_iter's own grid where nothing moved it."""
+    g = DEFAULTS["bp_lim_iter"]["grid"]
+    if (opts.eps_lo, opts.eps_hi, opts.points) == (g.eps(g.num_points - 1), g.eps(0), g.num_points):
+        return [g.eps(i) for i in range(g.num_points)]
+    if opts.points == 1:
+        return [opts.eps_hi]
+    return [opts.eps_hi + (opts.eps_lo - opts.eps_hi) * i / (opts.points - 1) if i < opts.points - 1 else opts.eps_lo
+            for i in range(opts.points)]
+
+
+def bp_curves(argv=None):
+    """`bp_curves INDEX W NUM_DOPED FRAMES [doped…]`: run_vn_thresholds over the frames of the replica; rank 0 pickles
+    dict(eps_lo, eps_hi, t_lo, t_hi, seed, index, es, rows, pos_thresh, counts) to <bp_lim_iter's result file at MAX_IT
+    1000000>.curves.pkl and prints, per point, the columns of PointResult.row() it has (the expurgated ones are 0)."""
+    opts = _curves_parser().parse_args(argv)
+    if not 1 <= opts.points <= E.VNT_MAX_POINTS:
+        raise SystemExit("bp_curves: --points %d: between 1 and %d points" % (opts.points, E.VNT_MAX_POINTS))
+    p, doped = _check_thresholds(opts, "bp_curves", E.vn_threshold_workspace_bytes)
+    es = _curves_points(opts)
+    if opts.seed is None:
+        opts.seed = int((time.time() % 1) * 1e6)
+    joined = E.init_distributed()
+    dist, rank, world = _dist()
+    res = run_vn_thresholds(p, opts.eps_lo, opts.eps_hi, opts.FRAMES, opts.seed, es=es, index=opts.INDEX, is_term=bool(opts.is_term),
+                            doped=doped, batch=opts.batch, verbose=rank == 0 and not opts.quiet)
+    if rank == 0:
+        os.makedirs(opts.outdir, exist_ok=True)
+        path = os.path.join(opts.outdir, result_filename("bp_lim_iter", p, 0, 1000000, 0, opts.INDEX) + ".curves.pkl")
+        with open(path, "wb") as f:
+            pickle.dump(dict(eps_lo=opts.eps_lo, eps_hi=opts.eps_hi, t_lo=res.t_lo, t_hi=res.t_hi, seed=opts.seed, index=opts.INDEX,
+                             es=es, rows=res.rows, pos_thresh=res.pos_thresh, counts=res.counts), f)
+        if not opts.quiet:
+            users, frame, block = res.ber_at(es), res.fer_at(es), res.block_err_at(es)
+            sys.stdout.write(RISULTATI_HEADER)
+            for e, u, fe, b in zip(es, users, frame, block):
+                run = dict.fromkeys(RUN_NAMES, 0)
+                run.update(users_err=int(u), frame_err=int(fe), block_err=int(b), frames=opts.FRAMES)
+                sys.stdout.write(PointResult(e, p.n, p.L, [run[k] for k in RUN_NAMES]).row())
+            sys.stdout.flush()
     if joined:
         import torch.distributed as dist_mod
         dist_mod.destroy_process_group()
@@ -1935,6 +2135,8 @@ if __name__ == "__main__":
         sys.exit(streaming(sys.argv[2:]))
     if len(sys.argv) >= 2 and sys.argv[1] == "bp_thresholds":
         sys.exit(bp_thresholds(sys.argv[2:]))
+    if len(sys.argv) >= 2 and sys.argv[1] == "bp_curves":
+        sys.exit(bp_curves(sys.argv[2:]))
     if len(sys.argv) < 2 or sys.argv[1] not in DEFAULTS:
-        raise SystemExit("usage: python -m fl_scaling_sc_ldpc_amd.bp_decoding {bp_lim_iter|sw_lim_iter|bp_traj|sw|bp_thresholds} ARGS…")
+        raise SystemExit("usage: python -m fl_scaling_sc_ldpc_amd.bp_decoding {bp_lim_iter|sw_lim_iter|bp_traj|sw|bp_thresholds|bp_curves} ARGS…")
     sys.exit(main(sys.argv[1], sys.argv[2:]))

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from ._lib import (CodeParams, MAX_CAPS, NCOUNTERS, NRUN, NPEELRUN, COUNTER_NAMES, RUN_NAMES, PEELRUN_NAMES, ScldpcError,  # noqa: F401
                    SS_MAX_BINS, SS_POS_SIZES, RUNS_MAX_L, RUNS_MAX_BINS, RUNS_MAX_PERIOD, RUNS_CARRY, EPS_MAX_POINTS, THRESH_NCOLS, THRESH_MAX,
-                   THRESH_NAMES, check, lib)
+                   THRESH_NAMES, VNT_NCOLS, VNT_MAX_POINTS, VNT_NONE, VNT_NAMES, check, lib)
 
 
 def make_params(dv=4, dc=8, L=50, N=1000):
@@ -828,6 +828,50 @@ def frame_threshold(p, d_adj, d_keys, t_lo, t_hi, is_term=True, want_bits=False,
     check(fn(C.byref(p), T, d_adj.data_ptr(), d_keys.data_ptr(), int(t_lo), int(t_hi), 1 if is_term else 0, rows.data_ptr(),
              bits.data_ptr() if bits is not None else None, ws.data_ptr() if ws is not None else None, nbytes, _stream_ptr(dev)))
     return {"rows": rows, "bits": bits}
+
+
+def vn_threshold_workspace_bytes(p, ntrials, adj16):
+    """Bytes of workspace vn_threshold needs for ntrials frames (0: the CN words stay in LDS); ScldpcError for a shape the
+    entry refuses.  Needs no device."""
+    return _eps_workspace_bytes("scldpc_vn_threshold_workspace_query", p, ntrials, adj16)
+
+
+def vn_threshold(p, d_adj, d_keys, t_lo, t_hi, grid=(), is_term=True, want_tau=False, rows=None):
+    """The erasure threshold of every VN under unlimited full BP: tau(j) = the least t at which VN j is in the residual S(t) that
+    full_bp without a cap leaves of {key < t}, walked down from the decode at t_hi with no rebuild of the CN words.  Returns dict
+    with rows int32 [T, 8] — _lib.VNT_NAMES: [0] T* / t_lo / -1 and [1] the status, both frame_threshold's; [2] |S(t_hi)|; [3] the
+    size of the critical residual; [4] steps = the distinct tau in (t_lo, t_hi]; [5] candidate scans, [6] re-scans; [7] #VNs
+    erased at t_hi —, pos_thresh int32 [T, L] holding uint32 bit patterns (the least tau of the position, -1 = VNT_NONE where it
+    never fails), counts int32 [T, len(grid)] or None (counts[k] = #{j : tau(j) <= grid[k]}, grid: ascending thresholds inside
+    the window, at most _lib.VNT_MAX_POINTS) and tau int32 [T, n] (uint32 bit patterns; t_lo means "at or below t_lo") or None
+    (scldpc_vn_threshold_device).  rows: a contiguous int32 [T, 8] tensor to write into."""
+    _require_gpu()
+    if not 0 <= int(t_lo) <= 0xFFFFFFFF or not 0 <= int(t_hi) <= 0xFFFFFFFF:
+        raise ValueError("vn_threshold: the thresholds are unsigned 32-bit integers (got t_lo = %d, t_hi = %d)" % (t_lo, t_hi))
+    g = [int(t) for t in grid]
+    if any(not 0 <= t <= 0xFFFFFFFF for t in g):
+        raise ValueError("vn_threshold: the grid's thresholds are unsigned 32-bit integers")
+    garr = np.ascontiguousarray(g, dtype=np.uint32)
+    T, K = d_adj.shape[0], garr.size
+    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
+    assert tuple(d_adj.shape[1:]) == (p.n, p.dv)
+    assert d_keys.is_cuda and d_keys.dtype == torch.int32 and d_keys.is_contiguous() and d_keys.shape == (T, p.n)
+    dev = d_adj.device
+    adj16 = _is_adj16(d_adj)
+    nbytes = vn_threshold_workspace_bytes(p, T, adj16)                  # (also refuses the shape before anything is allocated)
+    shape = (T, _lib.VNT_NCOLS)
+    if rows is None:
+        rows = _uninit(shape, dtype=torch.int32, device=dev)
+    assert rows.is_cuda and rows.is_contiguous() and rows.dtype == torch.int32 and tuple(rows.shape) == shape
+    pos = _uninit((T, p.L), dtype=torch.int32, device=dev)
+    counts = _uninit((T, K), dtype=torch.int32, device=dev) if K else None
+    tau = _uninit((T, p.n), dtype=torch.int32, device=dev) if want_tau else None
+    ws = _uninit(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    fn = lib().scldpc_vn_threshold_device_adj16 if adj16 else lib().scldpc_vn_threshold_device
+    check(fn(C.byref(p), T, d_adj.data_ptr(), d_keys.data_ptr(), int(t_lo), int(t_hi), 1 if is_term else 0, K,
+             garr.ctypes.data if K else None, rows.data_ptr(), pos.data_ptr(), counts.data_ptr() if counts is not None else None,
+             tau.data_ptr() if tau is not None else None, ws.data_ptr() if ws is not None else None, nbytes, _stream_ptr(dev)))
+    return {"rows": rows, "pos_thresh": pos, "counts": counts, "tau": tau}
 
 
 def peel_sweep_sock16_supported(p):
