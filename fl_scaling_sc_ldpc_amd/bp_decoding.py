@@ -84,6 +84,7 @@ All compute is in libscldpc_hip.so; this file is orchestration and file formats.
 import argparse
 import collections
 import copy
+import functools
 import os
 import pickle
 import sys
@@ -834,16 +835,7 @@ class Simulator:
             if nb:
                 self.fill_batch(sim, eps, frame0 + off, nb)
                 cnt = self.decode_batch_caps(nb)
-            if W > 1:
-                m = max(sizes)
-                mine = torch.zeros((K, m, NCOUNTERS), dtype=torch.int32, device=self.d_cnt.device)
-                if nb:
-                    mine[:, :nb] = cnt
-                gathered = [torch.empty_like(mine) for _ in range(W)]
-                self.dist.all_gather(gathered, mine)
-                allcnt = torch.cat([g[:, :s] for g, s in zip(gathered, sizes)], dim=1)
-            else:
-                allcnt = cnt
+            allcnt = E.gather_frames(self.dist, cnt, sizes, dim=1, shape=(K, 0, NCOUNTERS), device=self.d_cnt.device)
             can_trip = min_frame_err > 0 and frame0 + R >= min_frame_err
             live = [k for k in range(K) if not stopped[k]]
             for k in live:
@@ -1087,6 +1079,49 @@ def eps_fused_reason(prog, p, es, schedule="fixpoint", max_it=0, caps=None, wind
     return None
 
 
+def _refuse_shape(workspace_bytes, p, who):
+    """ValueError(who + the library's text) for a shape the entry of the workspace query refuses; needs no device."""
+    try:
+        workspace_bytes(p, 1, p.cns_pos <= 65536)
+    except E.ScldpcError as err:
+        raise ValueError("%s: %s" % (who, err))
+
+
+class _CodeRounds:
+    """The rounds of the drivers that decode one sampled code per frame (run_grid_fused, run_thresholds, run_vn_thresholds):
+    the ranks and the device, the code buffers of `batch` frames (2-byte rows where the sampler offers them), and per round
+    run_point's split (split_round) with the first-generation sampler call at eps_top for this rank's frames, keyed
+    trial_key(index, 0, frame); the sampler's channel is not used."""
+
+    def __init__(self, p, seed, index, eps_top, doped, batch, device, shard_frames):
+        self.p, self.seed, self.index, self.eps_top, self.doped, self.B = p, seed, index, eps_top, tuple(doped), int(batch)
+        self.dist, self.rank, self.W = _dist() if shard_frames else (None, 0, 1)
+        self.device = torch.device(device) if device is not None else E.local_device()
+        adj16 = p.cns_pos <= 65536
+        self.d_adj = self.buffer(p.n, p.dv, dtype=torch.int16 if adj16 else torch.int32)
+        self.d_ch = self.buffer(p.nw)
+
+    def buffer(self, *width, dtype=torch.int32):
+        return torch.empty((self.B,) + width, dtype=dtype, device=self.device)
+
+    def __call__(self, frames):
+        """Yields (frame0, R, nb, off, key, d_adj[:nb], gather) per round of up to `frames` frames: the round's first frame and
+        size, this rank's share, its offset in the round and first key, its codes (sampled only where nb > 0), and
+        engine.gather_frames bound to the round's split.  Lazy: a caller that leaves the loop samples nothing further."""
+        frame0 = 0
+        while frame0 < frames:
+            R, sizes, offs = Simulator.split_round(frames - frame0, self.B, self.W)
+            nb, off = sizes[self.rank], offs[self.rank]
+            key = trial_key(self.index, 0, frame0 + off) if nb else None
+            if nb:
+                E.sample_philox(self.p, self.seed, key, nb, self.eps_top, self.doped, out=(self.d_adj[:nb], self.d_ch[:nb]))
+
+            def gather(part, dim=0, shape=None, sizes=sizes):
+                return E.gather_frames(self.dist, part, sizes, dim, shape, device=self.device)
+            yield frame0, R, nb, off, key, self.d_adj[:nb], gather
+            frame0 += R
+
+
 def run_grid_fused(p, es, min_frame_err, max_frames, seed, index=0, is_term=True, doped=(), batch=2048, device=None,
                    shard_frames=True, runs=False, defer_abort=False, verbose=False):
     """Unlimited full BP at every ε of es from ONE sampled code per frame: a list of PointResult in the caller's order, point i
@@ -1116,49 +1151,28 @@ def run_grid_fused(p, es, min_frame_err, max_frames, seed, index=0, is_term=True
     K = len(stage_eps)
     if K > E.EPS_MAX_POINTS:
         raise ValueError("eps_fused: at most %d distinct ε points in one run (got %d)" % (E.EPS_MAX_POINTS, K))
-    adj16 = p.cns_pos <= 65536
-    try:
-        E.full_bp_eps_workspace_bytes(p, 1, adj16)
-    except E.ScldpcError as err:
-        raise ValueError("eps_fused: %s" % err)
-    dist, rank, W = _dist() if shard_frames else (None, 0, 1)
-    device = torch.device(device) if device is not None else E.local_device()
+    _refuse_shape(E.full_bp_eps_workspace_bytes, p, "eps_fused")
+    rounds = _CodeRounds(p, seed, index, stage_eps[0], doped, batch, device, shard_frames)
+    device, doped = rounds.device, rounds.doped
     if verbose:
         print("[scldpc] kernels: sampler (first generation) + channel_levels + full_bp_eps (%d ε points from one code)" % K,
               file=sys.stderr, flush=True)
     i_frames, i_ferr, i_status = RUN_NAMES.index("frames"), RUN_NAMES.index("frame_err"), E.COUNTER_NAMES.index("status")
-    B, doped = int(batch), tuple(doped)
-    d_adj = torch.empty((B, p.n, p.dv), dtype=torch.int16 if adj16 else torch.int32, device=device)
-    d_ch = torch.empty((B, p.nw), dtype=torch.int32, device=device)
-    d_lev = torch.empty((B, p.n), dtype=torch.uint8, device=device)
-    d_cnt = torch.empty(K * B * NCOUNTERS, dtype=torch.int32, device=device)
+    d_lev = rounds.buffer(p.n, dtype=torch.uint8)
+    d_cnt = torch.empty(K * rounds.B * NCOUNTERS, dtype=torch.int32, device=device)
     run = torch.zeros((K, NRUN), dtype=torch.int64, device=device)
     bad = torch.zeros(K, dtype=torch.bool, device=device)
     racc = [None] * K
     consumed = [0] * K
     live = list(range(K))                                               # stages still running, by descending ε
-    frame0 = 0
-    while live and frame0 < max_frames:
-        R, sizes, offs = Simulator.split_round(max_frames - frame0, B, W)
-        nb, off = sizes[rank], offs[rank]
+    for frame0, R, nb, off, key, d_adj, gather in rounds(max_frames):
         Kl = len(live)
         res = None
         if nb:
-            key = trial_key(index, 0, frame0 + off)
-            E.sample_philox(p, seed, key, nb, stage_eps[0], doped, out=(d_adj[:nb], d_ch[:nb]))
             E.channel_levels(p, seed, key, nb, [stage_eps[k] for k in live], doped, device=device, out=d_lev[:nb])
-            res = E.full_bp_eps(p, d_adj[:nb], d_lev[:nb], Kl, is_term=is_term, want_erased=runs,
+            res = E.full_bp_eps(p, d_adj, d_lev[:nb], Kl, is_term=is_term, want_erased=runs,
                                 counters=d_cnt[:Kl * nb * NCOUNTERS].view(Kl, nb, NCOUNTERS))
-        if W > 1:
-            m = max(sizes)
-            mine = torch.zeros((Kl, m, NCOUNTERS), dtype=torch.int32, device=device)
-            if nb:
-                mine[:, :nb] = res["counters"]
-            gathered = [torch.empty_like(mine) for _ in range(W)]
-            dist.all_gather(gathered, mine)
-            allcnt = torch.cat([g[:, :s] for g, s in zip(gathered, sizes)], dim=1).contiguous()
-        else:
-            allcnt = res["counters"]
+        allcnt = gather(res["counters"] if nb else None, dim=1, shape=(Kl, 0, NCOUNTERS))
         for i, k in enumerate(live):
             E.accumulate_run(allcnt[i], run[k], min_frame_err)
         can_trip = min_frame_err > 0 and frame0 + R >= min_frame_err
@@ -1178,7 +1192,8 @@ def run_grid_fused(p, es, min_frame_err, max_frames, seed, index=0, is_term=True
             if not stopped:
                 still.append(k)
         live = still
-        frame0 += R
+        if not live:
+            break                                                       # (before the generator samples the next round)
     bad = bad.cpu().tolist()
     if any(bad) and not defer_abort:
         abort_invariant()
@@ -1189,8 +1204,8 @@ def run_grid_fused(p, es, min_frame_err, max_frames, seed, index=0, is_term=True
         for k in range(K):                                              # one all-reduce per point, as run_point's
             flat = (torch.cat([racc[k][name].reshape(-1) for name, _ in shapes]) if racc[k] is not None else
                     torch.zeros(sum(int(np.prod(sh)) for _, sh in shapes), dtype=torch.int64, device=device))
-            if W > 1:
-                dist.all_reduce(flat)
+            if rounds.W > 1:
+                rounds.dist.all_reduce(flat)
             stage_runs[k] = runs_unflatten(p.L, flat.cpu().numpy())
     return [PointResult(e, p.n, p.L, tot[k], bad=bad[k], runs=copy.deepcopy(stage_runs[k])) for e, k in zip(es, stage_of)]
 
@@ -1239,6 +1254,14 @@ def _run_eps_fused(prog, index, W, max_it, opts, p, grid, doped, want_runs):
     return 0
 
 
+def _threshold_inside(e, t_lo, t_hi):
+    """erasure_threshold(ε), or ValueError where it lies outside the window, in which the rows do not decide it."""
+    th = E.erasure_threshold(e)
+    if not t_lo <= th <= t_hi:
+        raise ValueError("thresholds: ε = %.17g (threshold %d) lies outside the window [%d, %d]" % (e, th, t_lo, t_hi))
+    return th
+
+
 class FrameThresholds:
     """What run_thresholds returns: one row per frame, in frame order.
       rows    int64 [frames, 8], engine.frame_threshold's columns (E.THRESH_NAMES): thresh, status, size, first_pos, last_pos,
@@ -1264,11 +1287,39 @@ class FrameThresholds:
         thresh, status = self.rows[:, 0], self.rows[:, 1]
         out = []
         for e in np.asarray(es, dtype=np.float64).reshape(-1):
-            th = E.erasure_threshold(e)
-            if not self.t_lo <= th <= self.t_hi:
-                raise ValueError("thresholds: ε = %.17g (threshold %d) lies outside the window [%d, %d]" % (e, th, self.t_lo, self.t_hi))
+            th = _threshold_inside(e, self.t_lo, self.t_hi)
             out.append(int(((status == 2) | ((status == 0) & (thresh <= th))).sum()))
         return np.array(out, dtype=np.int64)
+
+
+def _window(eps_lo, eps_hi, frames):
+    """(t_lo, t_hi, frames) of a threshold driver's window and frame count, or the ValueError of either."""
+    t_lo, t_hi = E.erasure_threshold(eps_lo), E.erasure_threshold(eps_hi)
+    if not (0.0 <= float(eps_lo) <= 1.0 and 0.0 <= float(eps_hi) <= 1.0 and t_lo < t_hi):
+        raise ValueError("thresholds: the window needs 0 <= eps_lo < eps_hi <= 1 with two distinct thresholds (got [%.17g, %.17g])"
+                         % (eps_lo, eps_hi))
+    if int(frames) < 0:
+        raise ValueError("thresholds: a negative number of frames (%d)" % int(frames))
+    return t_lo, t_hi, int(frames)
+
+
+def _threshold_rounds(rounds, frames, ncols, widths, entry):
+    """The rounds of run_thresholds and run_vn_thresholds: engine.channel_keys on the round's keys, entry(d_adj, d_keys, rows)
+    with rows the round's slice of one [batch, ncols] buffer, and of its result the outputs named in widths (name -> columns),
+    gathered over the ranks and copied to the host (a copy: the row buffer is written again in the next round).  Returns
+    name -> int32 [frames, width], in frame order."""
+    p = rounds.p
+    d_keys, d_rows = rounds.buffer(p.n), rounds.buffer(ncols)
+    parts = {name: [] for name in widths}
+    for _, _, nb, _, key, d_adj, gather in rounds(frames):
+        res = None
+        if nb:
+            E.channel_keys(p, rounds.seed, key, nb, rounds.doped, device=rounds.device, out=d_keys[:nb])
+            res = entry(d_adj, d_keys[:nb], d_rows[:nb])
+        for name, width in widths.items():
+            parts[name].append(gather(res[name] if nb else None, shape=(0, width)).to("cpu", copy=True))
+    return {name: np.ascontiguousarray(torch.cat(parts[name], dim=0).numpy()) if parts[name] else np.zeros((0, width), dtype=np.int32)
+            for name, width in widths.items()}
 
 
 def run_thresholds(p, eps_lo, eps_hi, frames, seed, index=0, is_term=True, doped=(), batch=2048, device=None, shard_frames=True,
@@ -1283,64 +1334,16 @@ def run_thresholds(p, eps_lo, eps_hi, frames, seed, index=0, is_term=True, doped
     bisection on the integer threshold inside its residual).  Rounds and the frame split over the ranks are run_point's
     (split_round); under torch.distributed one all-gather per round carries the [m, 8] rows.  A shape the entry refuses is a
     ValueError("thresholds: …") with the library's text, before anything is allocated."""
-    t_lo, t_hi = E.erasure_threshold(eps_lo), E.erasure_threshold(eps_hi)
-    if not (0.0 <= float(eps_lo) <= 1.0 and 0.0 <= float(eps_hi) <= 1.0 and t_lo < t_hi):
-        raise ValueError("thresholds: the window needs 0 <= eps_lo < eps_hi <= 1 with two distinct thresholds (got [%.17g, %.17g])"
-                         % (eps_lo, eps_hi))
-    frames = int(frames)
-    if frames < 0:
-        raise ValueError("thresholds: a negative number of frames (%d)" % frames)
-    adj16 = p.cns_pos <= 65536
-    try:
-        E.frame_threshold_workspace_bytes(p, 1, adj16)
-    except E.ScldpcError as err:
-        raise ValueError("thresholds: %s" % err)
-    dist, rank, W = _dist() if shard_frames else (None, 0, 1)
-    device = torch.device(device) if device is not None else E.local_device()
+    t_lo, t_hi, frames = _window(eps_lo, eps_hi, frames)
+    _refuse_shape(E.frame_threshold_workspace_bytes, p, "thresholds")
+    rounds = _CodeRounds(p, seed, index, eps_hi, doped, batch, device, shard_frames)
     if verbose:
         print("[scldpc] kernels: sampler (first generation) + channel_keys + frame_threshold (window [%d, %d])" % (t_lo, t_hi),
               file=sys.stderr, flush=True)
-    NC = E.THRESH_NCOLS
-    B, doped = int(batch), tuple(doped)
-    d_adj = torch.empty((B, p.n, p.dv), dtype=torch.int16 if adj16 else torch.int32, device=device)
-    d_ch = torch.empty((B, p.nw), dtype=torch.int32, device=device)
-    d_keys = torch.empty((B, p.n), dtype=torch.int32, device=device)
-    d_rows = torch.empty((B, NC), dtype=torch.int32, device=device)
-    all_rows, all_bits = [], []
-    frame0 = 0
-    while frame0 < frames:
-        R, sizes, offs = Simulator.split_round(frames - frame0, B, W)
-        nb, off = sizes[rank], offs[rank]
-        res = None
-        if nb:
-            key = trial_key(index, 0, frame0 + off)
-            E.sample_philox(p, seed, key, nb, eps_hi, doped, out=(d_adj[:nb], d_ch[:nb]))
-            E.channel_keys(p, seed, key, nb, doped, device=device, out=d_keys[:nb])
-            res = E.frame_threshold(p, d_adj[:nb], d_keys[:nb], t_lo, t_hi, is_term=is_term, want_bits=want_bits, rows=d_rows[:nb])
-        if W > 1:
-            m = max(sizes)
-
-            def gather(mine_part, width):
-                mine = torch.zeros((m, width), dtype=torch.int32, device=device)
-                if nb:
-                    mine[:nb] = mine_part
-                got = [torch.empty_like(mine) for _ in range(W)]
-                dist.all_gather(got, mine)
-                return torch.cat([g[:s] for g, s in zip(got, sizes)], dim=0)
-            all_rows.append(gather(res["rows"] if nb else None, NC).cpu())
-            if want_bits:
-                all_bits.append(gather(res["bits"] if nb else None, p.nw).cpu())
-        else:
-            all_rows.append(res["rows"].to("cpu", copy=True))                # (a copy: d_rows is written again in the next round)
-            if want_bits:
-                all_bits.append(res["bits"].to("cpu", copy=True))
-        frame0 += R
-    rows = (torch.cat(all_rows, dim=0).numpy().astype(np.int64) if all_rows else np.zeros((0, NC), dtype=np.int64))
-    bits = None
-    if want_bits:
-        bits = (np.ascontiguousarray(torch.cat(all_bits, dim=0).numpy()).view(np.uint32) if all_bits
-                else np.zeros((0, p.nw), dtype=np.uint32))
-    return FrameThresholds(rows, t_lo, t_hi, bits)
+    got = _threshold_rounds(rounds, frames, E.THRESH_NCOLS, {"rows": E.THRESH_NCOLS, **({"bits": p.nw} if want_bits else {})},
+                            lambda d_adj, d_keys, rows: E.frame_threshold(p, d_adj, d_keys, t_lo, t_hi, is_term=is_term,
+                                                                          want_bits=want_bits, rows=rows))
+    return FrameThresholds(got["rows"].astype(np.int64), t_lo, t_hi, got["bits"].view(np.uint32) if want_bits else None)
 
 
 class VnThresholds:
@@ -1359,13 +1362,7 @@ class VnThresholds:
         self.t_lo, self.t_hi, self.tau = int(t_lo), int(t_hi), tau
 
     def _thresholds(self, es):
-        out = []
-        for e in np.asarray(es, dtype=np.float64).reshape(-1):
-            th = E.erasure_threshold(e)
-            if not self.t_lo <= th <= self.t_hi:
-                raise ValueError("thresholds: ε = %.17g (threshold %d) lies outside the window [%d, %d]" % (e, th, self.t_lo, self.t_hi))
-            out.append(th)
-        return out
+        return [_threshold_inside(e, self.t_lo, self.t_hi) for e in np.asarray(es, dtype=np.float64).reshape(-1)]
 
     def fer_at(self, es):
         """int64 [len(es)]: the frames that fail at each ε; FrameThresholds.fer_at of the same frames."""
@@ -1412,68 +1409,24 @@ def run_vn_thresholds(p, eps_lo, eps_hi, frames, seed, es=(), index=0, is_term=T
     Per round: run_thresholds' sampler call and engine.channel_keys, then one engine.vn_threshold.  Under torch.distributed one
     all-gather per round carries the rows, positions, counts (and tau) of the round.  A shape the entry refuses, a grid outside
     the window or of more than E.VNT_MAX_POINTS thresholds is a ValueError("thresholds: …") before anything is allocated."""
-    t_lo, t_hi = E.erasure_threshold(eps_lo), E.erasure_threshold(eps_hi)
-    if not (0.0 <= float(eps_lo) <= 1.0 and 0.0 <= float(eps_hi) <= 1.0 and t_lo < t_hi):
-        raise ValueError("thresholds: the window needs 0 <= eps_lo < eps_hi <= 1 with two distinct thresholds (got [%.17g, %.17g])"
-                         % (eps_lo, eps_hi))
-    frames = int(frames)
-    if frames < 0:
-        raise ValueError("thresholds: a negative number of frames (%d)" % frames)
+    t_lo, t_hi, frames = _window(eps_lo, eps_hi, frames)
     grid = sorted(set(E.erasure_threshold(e) for e in np.asarray(es, dtype=np.float64).reshape(-1)))
     if grid and not (t_lo <= grid[0] and grid[-1] <= t_hi):
         raise ValueError("thresholds: the points of es lie outside the window [%d, %d]" % (t_lo, t_hi))
     if len(grid) > E.VNT_MAX_POINTS:
         raise ValueError("thresholds: %d distinct thresholds in es, at most %d" % (len(grid), E.VNT_MAX_POINTS))
-    adj16 = p.cns_pos <= 65536
-    try:
-        E.vn_threshold_workspace_bytes(p, 1, adj16)
-    except E.ScldpcError as err:
-        raise ValueError("thresholds: %s" % err)
-    dist, rank, W = _dist() if shard_frames else (None, 0, 1)
-    device = torch.device(device) if device is not None else E.local_device()
+    _refuse_shape(E.vn_threshold_workspace_bytes, p, "thresholds")
+    rounds = _CodeRounds(p, seed, index, eps_hi, doped, batch, device, shard_frames)
     if verbose:
         print("[scldpc] kernels: sampler (first generation) + channel_keys + vn_threshold (window [%d, %d], %d grid points)"
               % (t_lo, t_hi, len(grid)), file=sys.stderr, flush=True)
-    NC, K = E.VNT_NCOLS, len(grid)
-    B, doped = int(batch), tuple(doped)
-    d_adj = torch.empty((B, p.n, p.dv), dtype=torch.int16 if adj16 else torch.int32, device=device)
-    d_ch = torch.empty((B, p.nw), dtype=torch.int32, device=device)
-    d_keys = torch.empty((B, p.n), dtype=torch.int32, device=device)
-    d_rows = torch.empty((B, NC), dtype=torch.int32, device=device)
-    names = ["rows", "pos_thresh"] + (["counts"] if K else []) + (["tau"] if want_tau else [])
-    widths = {"rows": NC, "pos_thresh": p.L, "counts": K, "tau": p.n}
-    parts = {name: [] for name in names}
-    frame0 = 0
-    while frame0 < frames:
-        R, sizes, offs = Simulator.split_round(frames - frame0, B, W)
-        nb, off = sizes[rank], offs[rank]
-        res = None
-        if nb:
-            key = trial_key(index, 0, frame0 + off)
-            E.sample_philox(p, seed, key, nb, eps_hi, doped, out=(d_adj[:nb], d_ch[:nb]))
-            E.channel_keys(p, seed, key, nb, doped, device=device, out=d_keys[:nb])
-            res = E.vn_threshold(p, d_adj[:nb], d_keys[:nb], t_lo, t_hi, grid=grid, is_term=is_term, want_tau=want_tau,
-                                 rows=d_rows[:nb])
-        for name in names:
-            if W > 1:
-                m = max(sizes)
-                mine = torch.zeros((m, widths[name]), dtype=torch.int32, device=device)
-                if nb:
-                    mine[:nb] = res[name]
-                got = [torch.empty_like(mine) for _ in range(W)]
-                dist.all_gather(got, mine)
-                parts[name].append(torch.cat([g[:s] for g, s in zip(got, sizes)], dim=0).cpu())
-            else:
-                parts[name].append(res[name].to("cpu", copy=True))       # (a copy: d_rows is written again in the next round)
-        frame0 += R
-
-    def joined(name, unsigned):
-        if not parts[name]:
-            return np.zeros((0, widths[name]), dtype=np.int64)
-        a = np.ascontiguousarray(torch.cat(parts[name], dim=0).numpy())
-        return (a.view(np.uint32) if unsigned else a).astype(np.int64)
-    return VnThresholds(joined("rows", False), joined("pos_thresh", True), joined("counts", False) if K else np.zeros((frames, 0), dtype=np.int64),
-                        grid, t_lo, t_hi, joined("tau", True) if want_tau else None)
+    widths = {"rows": E.VNT_NCOLS, "pos_thresh": p.L, **({"counts": len(grid)} if grid else {}), **({"tau": p.n} if want_tau else {})}
+    got = _threshold_rounds(rounds, frames, E.VNT_NCOLS, widths,
+                            lambda d_adj, d_keys, rows: E.vn_threshold(p, d_adj, d_keys, t_lo, t_hi, grid=grid, is_term=is_term,
+                                                                       want_tau=want_tau, rows=rows))
+    return VnThresholds(got["rows"].astype(np.int64), got["pos_thresh"].view(np.uint32).astype(np.int64),
+                        got["counts"].astype(np.int64) if grid else np.zeros((frames, 0), dtype=np.int64), grid, t_lo, t_hi,
+                        got["tau"].view(np.uint32).astype(np.int64) if want_tau else None)
 
 
 def _ensemble_and_grid(prog, opts):
@@ -1873,36 +1826,48 @@ def _check_thresholds(opts, prog="bp_thresholds", workspace_bytes=None):
     return p, doped
 
 
-def bp_thresholds(argv=None):
-    """`bp_thresholds INDEX W NUM_DOPED FRAMES [doped…]`: run_thresholds over the frames of the replica; rank 0 pickles
-    dict(eps_lo, eps_hi, t_lo, t_hi, seed, index, rows) to <bp_lim_iter's result file at MAX_IT 1000000>.thresholds.pkl."""
-    opts = _thresholds_parser().parse_args(argv)
-    p, doped = _check_thresholds(opts)
+def _thresholds_main(prog, argv, parser, workspace_bytes, run, suffix, payload, report, check=lambda opts: None):
+    """A program over the thresholds of a replica's frames (bp_thresholds, bp_curves): the command line against check(opts) and
+    _check_thresholds, the time-based seed, the job, run(opts)(p, eps_lo, eps_hi, FRAMES, seed, …) — run_thresholds' arguments —
+    and on rank 0 the pickle dict(eps_lo, eps_hi, t_lo, t_hi, seed, index, **payload(opts, res)) at <bp_lim_iter's result file at
+    MAX_IT 1000000> + suffix, then report(opts, p, res) unless --quiet."""
+    opts = parser.parse_args(argv)
+    check(opts)
+    p, doped = _check_thresholds(opts, prog, workspace_bytes)
     if opts.seed is None:
         opts.seed = int((time.time() % 1) * 1e6)
     joined = E.init_distributed()
-    dist, rank, world = _dist()
-    res = run_thresholds(p, opts.eps_lo, opts.eps_hi, opts.FRAMES, opts.seed, index=opts.INDEX, is_term=bool(opts.is_term),
-                         doped=doped, batch=opts.batch, verbose=rank == 0 and not opts.quiet)
+    rank = _dist()[1]
+    res = run(opts)(p, opts.eps_lo, opts.eps_hi, opts.FRAMES, opts.seed, index=opts.INDEX, is_term=bool(opts.is_term),
+                    doped=doped, batch=opts.batch, verbose=rank == 0 and not opts.quiet)
     if rank == 0:
         os.makedirs(opts.outdir, exist_ok=True)
-        path = os.path.join(opts.outdir, result_filename("bp_lim_iter", p, 0, 1000000, 0, opts.INDEX) + ".thresholds.pkl")
+        path = os.path.join(opts.outdir, result_filename("bp_lim_iter", p, 0, 1000000, 0, opts.INDEX) + suffix)
         with open(path, "wb") as f:
             pickle.dump(dict(eps_lo=opts.eps_lo, eps_hi=opts.eps_hi, t_lo=res.t_lo, t_hi=res.t_hi, seed=opts.seed, index=opts.INDEX,
-                             rows=res.rows), f)
+                             **payload(opts, res)), f)
         if not opts.quiet:
-            status = res.rows[:, 1]
-            share = [float((status == s).mean()) for s in (0, 1, 2)]
-            es = res.eps_star()[status == 0]
-            print("frames %d   inside the window %.4f   above (decode at eps_hi) %.4f   at or below eps_lo %.4f"
-                  % (len(status), share[0], share[1], share[2]), flush=True)
-            if es.size:
-                print("eps*: mean %.6f   std %.6f   (%d uncensored frames)" % (es.mean(), es.std(ddof=1) if es.size > 1 else 0.0,
-                                                                              es.size), flush=True)
+            report(opts, p, res)
     if joined:
         import torch.distributed as dist_mod
         dist_mod.destroy_process_group()
     return 0
+
+
+def bp_thresholds(argv=None):
+    """`bp_thresholds INDEX W NUM_DOPED FRAMES [doped…]`: run_thresholds over the frames of the replica; rank 0 pickles
+    dict(eps_lo, eps_hi, t_lo, t_hi, seed, index, rows) to <bp_lim_iter's result file at MAX_IT 1000000>.thresholds.pkl."""
+    def report(opts, p, res):
+        status = res.rows[:, 1]
+        share = [float((status == s).mean()) for s in (0, 1, 2)]
+        es = res.eps_star()[status == 0]
+        print("frames %d   inside the window %.4f   above (decode at eps_hi) %.4f   at or below eps_lo %.4f"
+              % (len(status), share[0], share[1], share[2]), flush=True)
+        if es.size:
+            print("eps*: mean %.6f   std %.6f   (%d uncensored frames)" % (es.mean(), es.std(ddof=1) if es.size > 1 else 0.0,
+                                                                          es.size), flush=True)
+    return _thresholds_main("bp_thresholds", argv, _thresholds_parser(), E.frame_threshold_workspace_bytes,
+                            lambda opts: run_thresholds, ".thresholds.pkl", lambda opts, res: dict(rows=res.rows), report)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1933,35 +1898,23 @@ def bp_curves(argv=None):
     """`bp_curves INDEX W NUM_DOPED FRAMES [doped…]`: run_vn_thresholds over the frames of the replica; rank 0 pickles
     dict(eps_lo, eps_hi, t_lo, t_hi, seed, index, es, rows, pos_thresh, counts) to <bp_lim_iter's result file at MAX_IT
     1000000>.curves.pkl and prints, per point, the columns of PointResult.row() it has (the expurgated ones are 0)."""
-    opts = _curves_parser().parse_args(argv)
-    if not 1 <= opts.points <= E.VNT_MAX_POINTS:
-        raise SystemExit("bp_curves: --points %d: between 1 and %d points" % (opts.points, E.VNT_MAX_POINTS))
-    p, doped = _check_thresholds(opts, "bp_curves", E.vn_threshold_workspace_bytes)
-    es = _curves_points(opts)
-    if opts.seed is None:
-        opts.seed = int((time.time() % 1) * 1e6)
-    joined = E.init_distributed()
-    dist, rank, world = _dist()
-    res = run_vn_thresholds(p, opts.eps_lo, opts.eps_hi, opts.FRAMES, opts.seed, es=es, index=opts.INDEX, is_term=bool(opts.is_term),
-                            doped=doped, batch=opts.batch, verbose=rank == 0 and not opts.quiet)
-    if rank == 0:
-        os.makedirs(opts.outdir, exist_ok=True)
-        path = os.path.join(opts.outdir, result_filename("bp_lim_iter", p, 0, 1000000, 0, opts.INDEX) + ".curves.pkl")
-        with open(path, "wb") as f:
-            pickle.dump(dict(eps_lo=opts.eps_lo, eps_hi=opts.eps_hi, t_lo=res.t_lo, t_hi=res.t_hi, seed=opts.seed, index=opts.INDEX,
-                             es=es, rows=res.rows, pos_thresh=res.pos_thresh, counts=res.counts), f)
-        if not opts.quiet:
-            users, frame, block = res.ber_at(es), res.fer_at(es), res.block_err_at(es)
-            sys.stdout.write(RISULTATI_HEADER)
-            for e, u, fe, b in zip(es, users, frame, block):
-                run = dict.fromkeys(RUN_NAMES, 0)
-                run.update(users_err=int(u), frame_err=int(fe), block_err=int(b), frames=opts.FRAMES)
-                sys.stdout.write(PointResult(e, p.n, p.L, [run[k] for k in RUN_NAMES]).row())
-            sys.stdout.flush()
-    if joined:
-        import torch.distributed as dist_mod
-        dist_mod.destroy_process_group()
-    return 0
+    def check(opts):
+        if not 1 <= opts.points <= E.VNT_MAX_POINTS:
+            raise SystemExit("bp_curves: --points %d: between 1 and %d points" % (opts.points, E.VNT_MAX_POINTS))
+
+    def report(opts, p, res):
+        es = _curves_points(opts)
+        users, frame, block = res.ber_at(es), res.fer_at(es), res.block_err_at(es)
+        sys.stdout.write(RISULTATI_HEADER)
+        for e, u, fe, b in zip(es, users, frame, block):
+            run = dict.fromkeys(RUN_NAMES, 0)
+            run.update(users_err=int(u), frame_err=int(fe), block_err=int(b), frames=opts.FRAMES)
+            sys.stdout.write(PointResult(e, p.n, p.L, [run[k] for k in RUN_NAMES]).row())
+        sys.stdout.flush()
+    return _thresholds_main(
+        "bp_curves", argv, _curves_parser(), E.vn_threshold_workspace_bytes,
+        lambda opts: functools.partial(run_vn_thresholds, es=_curves_points(opts)), ".curves.pkl",
+        lambda opts, res: dict(es=_curves_points(opts), rows=res.rows, pos_thresh=res.pos_thresh, counts=res.counts), report, check)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -40,6 +40,7 @@
 #pragma once
 #include "flood_common.h"
 #include "../../include/scldpc_eps.h"
+#include "../../include/scldpc_thresh.h"
 #include <string>
 
 namespace scldpc_dev {
@@ -78,9 +79,41 @@ __device__ __forceinline__ uint32_t level_word(const uint8_t *lv, int w, int n, 
     return x;
 }
 
+// bits (key < t) of the 32 VNs of word w, none at or past n; wide: the row is 16-byte aligned and n % 4 == 0.
+// per(b, key): called with every key of the word and its bit number.
+template <class Per>
+__device__ __forceinline__ uint32_t key_word(const uint32_t *kr, int w, int n, bool wide, uint32_t t, Per &&per)
+{
+    uint32_t x = 0;
+    const int j0 = w * 32;
+    if (wide) {
+#pragma unroll 2
+        for (int q = 0; q < 8; q++) {
+            if (j0 + 4 * q >= n) break;                             // n % 4 == 0: a whole group or none
+            const uint4 v = *reinterpret_cast<const uint4 *>(kr + j0 + 4 * q);
+            const uint32_t k4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                per(4 * q + u, k4[u]);
+                x |= (uint32_t)(k4[u] < t) << (4 * q + u);
+            }
+        }
+    } else {
+        for (int b = 0; b < 32 && j0 + b < n; b++) {
+            const uint32_t k = kr[j0 + b];
+            per(b, k);
+            x |= (uint32_t)(k < t) << b;
+        }
+    }
+    return x;
+}
+
+__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ uint32_t uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+
 // Two 1024-thread workgroups per CU (8 waves per SIMD: at most 64 VGPRs, and 72 SGPRs as in full_bp.hip) wherever the LDS
 // admits them.  peel_sweep_kernel stays below 64 VGPRs unasked; with the stages in a loop the scheduler, left to the 128 VGPRs
-// that one workgroup per CU allows, takes up to 118, so the bound is stated.  No spills: tests/test_eps_walk_resources.py.
+// that one workgroup per CU allows, takes up to 118, so the bound is stated.  No spills: tests/test_walk_resources.py.
 template <int DV, bool A16, class ST, class End>
 __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(72))) void eps_walk_kernel(const typename End::Args a)
 {
@@ -245,29 +278,30 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(72))) voi
 
 namespace scldpc {
 
-// The front of both launches, and the launch.  d_rows: the entry's result rows, for the null test only.  fill(a, ncn) sets the
-// entry's own fields of Args once the parameters have been checked, and refuses what the entry refuses about them.
-template <class End, class Fill>
-inline int eps_walk_launch(const char *who, const scldpc_code_params *p, int32_t ntrials, const void *d_vn_adj, bool adj16,
-                           const uint8_t *d_levels, int32_t npoints, const void *d_rows, uint32_t *d_bits, const Scratch &scratch,
-                           void *stream, Fill &&fill)
+// The front of every launch on one sampled code per frame (the two eps walks here, frame_threshold.hip, vn_threshold.hip), and
+// the launch.  Args is the kernel's argument struct: Geo, then dv, L, cns_pos, n, ncn, ntrials, lay, vn_adj and ws under these
+// names.  own(a, ncn) refuses what the entry refuses about its own arguments and sets the entry's own fields; pos_a(p) and
+// max(the words of R and the level counts, pos_b_floor) size the two position regions, which with the 2-byte adjacency decide the
+// CN-word form a shape takes; pick names the kernel instance as flood_pick asks.
+template <class Args, class Own, class Pick>
+inline int walk_launch(const char *who, const scldpc_code_params *p, int32_t ntrials, bool any_null, const void *d_vn_adj, bool adj16,
+                       const Scratch &scratch, void *stream, int (*pos_a)(const scldpc_code_params *), int pos_b_floor, Own &&own,
+                       Pick &&pick)
 {
     using namespace scldpc_dev;
-    using Args = typename End::Args;
     if (int rc = check_params(p)) return rc;
-    if (int rc = flood_check_call(who, scratch, ntrials, !d_rows || !d_vn_adj || !d_levels)) return rc;
+    if (int rc = flood_check_call(who, scratch, ntrials, any_null || !d_vn_adj)) return rc;
     const int n = n_of(p), ncn = nk_of(p);
-    if (npoints < 1 || npoints > SCLDPC_EPS_MAX_POINTS)
-        return set_error(SCLDPC_ERR_BAD_ARG, "%s: 1 <= npoints <= %d (got npoints = %d)", who, SCLDPC_EPS_MAX_POINTS, npoints);
     Args a{};
-    if (int rc = fill(a, ncn)) return rc;
+    if (int rc = own(a, ncn)) return rc;
     if (ntrials <= 0) return SCLDPC_OK;
     if (!flood_limits_ok(p))
         return set_error(SCLDPC_ERR_TOO_LARGE, "%s: needs dc <= 15, dv <= 8, dc*n < 2^24", who);
     int words;
-    // packed 16-bit words for position-structured graphs only = the 2-byte adjacency; R and the level counts in pos_b
+    // packed 16-bit words for position-structured graphs only = the 2-byte adjacency
     auto carve = [&](int w) {
-        return flood_carve_roomy(p, {flood_cn_lds_words(w, ncn), false, End::pos_words(p), ((nw_of(p) + 3) & ~3) + kBins, 256}, &a.lay);
+        const int pos_b = ((nw_of(p) + 3) & ~3) + kBins;
+        return flood_carve_roomy(p, {flood_cn_lds_words(w, ncn), false, pos_a(p), pos_b > pos_b_floor ? pos_b : pos_b_floor, 256}, &a.lay);
     };
     const std::string nofit = std::string(who) + ": %d VN bits + %d scan bits do not fit 160 KiB of LDS";
     if (int rc = flood_choose_words(who, nofit.c_str(), p, ntrials, scratch, adj16 && (int64_t)p->dv * p->vns_pos <= 4096, carve,
@@ -277,15 +311,45 @@ inline int eps_walk_launch(const char *who, const scldpc_code_params *p, int32_t
         const int cap = atoi(v);
         if (cap > 0 && cap < a.lay.qcap) a.lay.qcap = cap;
     }
-    a.dv = p->dv; a.L = p->L; a.cns_pos = p->cns_pos; a.n = n; a.ncn = ncn; a.npoints = npoints; a.ntrials = ntrials;
+    a.dv = p->dv; a.L = p->L; a.cns_pos = p->cns_pos; a.n = n; a.ncn = ncn; a.ntrials = ntrials; a.vn_adj = d_vn_adj;
     const std::string inexact = std::string(who) + ": reciprocal division inexact";
     if (int rc = flood_geo(inexact.c_str(), p, n > 4096 ? n : 4096, &a)) return rc;
-    a.vn_adj = d_vn_adj; a.levels = d_levels; a.bits_out = d_bits;
-    a.lev_wide = (n & 3) == 0 && (reinterpret_cast<uintptr_t>(d_levels) & 3) == 0;
-    void (*kern)(const Args) = flood_pick(words, p->dv == 4, adj16, [](auto st, auto dv, auto a16) -> void (*)(const Args) {
-        return eps_walk_kernel<decltype(dv)::value, decltype(a16)::value, decltype(st), End>;
-    });
+    void (*kern)(const Args) = flood_pick(words, p->dv == 4, adj16, pick);
     return flood_launch(kern, ntrials, kBlock, stream, a);
+}
+
+// The eps walks' launch.  d_rows: the entry's result rows, for the null test only.  fill(a, ncn) sets the End policy's own
+// fields of Args and refuses what the entry refuses about them.  R and the level counts in pos_b.
+template <class End, class Fill>
+inline int eps_walk_launch(const char *who, const scldpc_code_params *p, int32_t ntrials, const void *d_vn_adj, bool adj16,
+                           const uint8_t *d_levels, int32_t npoints, const void *d_rows, uint32_t *d_bits, const Scratch &scratch,
+                           void *stream, Fill &&fill)
+{
+    using Args = typename End::Args;
+    return walk_launch<Args>(who, p, ntrials, !d_rows || !d_levels, d_vn_adj, adj16, scratch, stream, &End::pos_words, 0,
+                             [&](Args &a, int ncn) {
+        if (npoints < 1 || npoints > SCLDPC_EPS_MAX_POINTS)
+            return set_error(SCLDPC_ERR_BAD_ARG, "%s: 1 <= npoints <= %d (got npoints = %d)", who, SCLDPC_EPS_MAX_POINTS, npoints);
+        a.npoints = npoints; a.levels = d_levels; a.bits_out = d_bits;
+        a.lev_wide = (n_of(p) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_levels) & 3) == 0;
+        return fill(a, ncn);
+    }, [](auto st, auto dv, auto a16) -> void (*)(const Args) {
+        return scldpc_dev::eps_walk_kernel<decltype(dv)::value, decltype(a16)::value, decltype(st), End>;
+    });
+}
+
+// The window and the keys of both threshold launches (frame_threshold.hip, vn_threshold.hip): the check and the fields.
+template <class Args>
+inline int thresh_window(const char *who, const scldpc_code_params *p, int ncn, const uint32_t *d_keys, uint32_t t_lo, uint32_t t_hi,
+                         int32_t is_term, Args &a)
+{
+    if (!(t_lo < t_hi && t_hi <= SCLDPC_THRESH_MAX))
+        return set_error(SCLDPC_ERR_BAD_ARG, "%s: 0 <= t_lo < t_hi <= %u (got t_lo = %u, t_hi = %u)", who, SCLDPC_THRESH_MAX, t_lo,
+                         t_hi);
+    a.cn_lim = is_term ? ncn : p->L * p->cns_pos;
+    a.t_lo = t_lo; a.t_hi = t_hi; a.keys = d_keys;
+    a.key_wide = (n_of(p) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_keys) & 15) == 0;
+    return SCLDPC_OK;
 }
 
 }  // namespace scldpc

@@ -44,39 +44,8 @@ struct TArgs : Geo {            // Geo: vns_pos, magic_v, magic_c
     uint32_t *ws;               // [T][ncn] CN words in global memory (ensembles beyond the LDS)
 };
 
-// bits (key < t) of the 32 VNs of word w, none at or past n; wide: the row is 16-byte aligned and n % 4 == 0.
-// per(b, key): called with every key of the word and its bit number.
-template <class Per>
-__device__ __forceinline__ uint32_t key_word(const uint32_t *kr, int w, int n, bool wide, uint32_t t, Per &&per)
-{
-    uint32_t x = 0;
-    const int j0 = w * 32;
-    if (wide) {
-#pragma unroll 2
-        for (int q = 0; q < 8; q++) {
-            if (j0 + 4 * q >= n) break;                             // n % 4 == 0: a whole group or none
-            const uint4 v = *reinterpret_cast<const uint4 *>(kr + j0 + 4 * q);
-            const uint32_t k4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                per(4 * q + u, k4[u]);
-                x |= (uint32_t)(k4[u] < t) << (4 * q + u);
-            }
-        }
-    } else {
-        for (int b = 0; b < 32 && j0 + b < n; b++) {
-            const uint32_t k = kr[j0 + b];
-            per(b, k);
-            x |= (uint32_t)(k < t) << b;
-        }
-    }
-    return x;
-}
-
-__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
-
 // Two 1024-thread workgroups per CU (8 waves per SIMD: at most 64 VGPRs, and 72 SGPRs) wherever the LDS admits them, as
-// eps_walk_kernel.  No spills: tests/test_thresh_resources.py.
+// eps_walk_kernel.  No spills: tests/test_walk_resources.py.
 template <int DV, bool A16, class ST>
 __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(72))) void frame_threshold_kernel(const TArgs a)
 {
@@ -262,48 +231,20 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(72))) voi
 
 }  // namespace
 
-// The front of the launch: eps_walk_launch's shape rule and LDS carve, region for region (full_bp_eps.hip's sizes, so that a
-// shape takes the same CN-word form in both kernels; R is the one region of pos_a / pos_b this kernel uses).
+// The launch on walk_launch's front: the shape rule and LDS carve of the eps walks, region for region (full_bp_eps.hip's sizes, so
+// that a shape takes the same CN-word form in both kernels; R is the one region of pos_a / pos_b this kernel uses: the 2 L
+// position words and the kBins words beside R are deliberately unused).
 static int launch_frame_threshold(const char *who, const scldpc_code_params *p, int32_t ntrials, const void *d_vn_adj, bool adj16,
                                   const uint32_t *d_keys, uint32_t t_lo, uint32_t t_hi, int32_t is_term, int32_t *d_rows,
                                   uint32_t *d_bits, const scldpc::Scratch &scratch, void *stream)
 {
-    using namespace scldpc;
-    using namespace scldpc_dev;
-    if (int rc = check_params(p)) return rc;
-    if (int rc = flood_check_call(who, scratch, ntrials, !d_rows || !d_vn_adj || !d_keys)) return rc;
-    if (!(t_lo < t_hi && t_hi <= SCLDPC_THRESH_MAX))
-        return set_error(SCLDPC_ERR_BAD_ARG, "%s: 0 <= t_lo < t_hi <= %u (got t_lo = %u, t_hi = %u)", who, SCLDPC_THRESH_MAX, t_lo,
-                         t_hi);
-    if (ntrials <= 0) return SCLDPC_OK;
-    if (!flood_limits_ok(p))
-        return set_error(SCLDPC_ERR_TOO_LARGE, "%s: needs dc <= 15, dv <= 8, dc*n < 2^24", who);
-    const int n = n_of(p), ncn = nk_of(p);
-    TArgs a{};
-    int words;
-    // (the 2 L position words and the kBins words beside R are deliberately unused: they keep the shape rule full_bp_eps's)
-    auto carve = [&](int w) {
-        return flood_carve_roomy(p, {flood_cn_lds_words(w, ncn), false, 2 * p->L, ((nw_of(p) + 3) & ~3) + kBins, 256}, &a.lay);
-    };
-    const std::string nofit = std::string(who) + ": %d VN bits + %d scan bits do not fit 160 KiB of LDS";
-    if (int rc = flood_choose_words(who, nofit.c_str(), p, ntrials, scratch, adj16 && (int64_t)p->dv * p->vns_pos <= 4096, carve,
-                                    &words, &a.ws)) return rc;
-    if (words == kWordsQueryDone) return SCLDPC_OK;
-    if (const char *v = getenv("SCLDPC_DEBUG_EPS_QCAP")) {          // tests: forces the overflow re-scan at a small shape
-        const int cap = atoi(v);
-        if (cap > 0 && cap < a.lay.qcap) a.lay.qcap = cap;
-    }
-    a.dv = p->dv; a.L = p->L; a.cns_pos = p->cns_pos; a.n = n; a.ncn = ncn; a.ntrials = ntrials;
-    a.cn_lim = is_term ? ncn : p->L * p->cns_pos;
-    a.t_lo = t_lo; a.t_hi = t_hi;
-    const std::string inexact = std::string(who) + ": reciprocal division inexact";
-    if (int rc = flood_geo(inexact.c_str(), p, n > 4096 ? n : 4096, &a)) return rc;
-    a.vn_adj = d_vn_adj; a.keys = d_keys; a.rows = d_rows; a.bits_out = d_bits;
-    a.key_wide = (n & 3) == 0 && (reinterpret_cast<uintptr_t>(d_keys) & 15) == 0;
-    void (*kern)(const TArgs) = flood_pick(words, p->dv == 4, adj16, [](auto st, auto dv, auto a16) -> void (*)(const TArgs) {
+    return scldpc::walk_launch<TArgs>(who, p, ntrials, !d_rows || !d_keys, d_vn_adj, adj16, scratch, stream,
+                                      [](const scldpc_code_params *p) { return 2 * p->L; }, 0, [&](TArgs &a, int ncn) {
+        a.rows = d_rows; a.bits_out = d_bits;
+        return scldpc::thresh_window(who, p, ncn, d_keys, t_lo, t_hi, is_term, a);
+    }, [](auto st, auto dv, auto a16) -> void (*)(const TArgs) {
         return frame_threshold_kernel<decltype(dv)::value, decltype(a16)::value, decltype(st)>;
     });
-    return flood_launch(kern, ntrials, kBlock, stream, a);
 }
 
 extern "C" int scldpc_frame_threshold_device(const scldpc_code_params *p, int32_t ntrials, const int32_t *d_vn_adj,

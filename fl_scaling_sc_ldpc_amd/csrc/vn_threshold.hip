@@ -68,40 +68,8 @@ struct VArgs : Geo {            // Geo: vns_pos, magic_v, magic_c
     uint32_t grid[SCLDPC_VNT_MAX_POINTS];
 };
 
-// bits (key < t) of the 32 VNs of word w, none at or past n; wide: the row is 16-byte aligned and n % 4 == 0.
-// per(b, key): called with every key of the word and its bit number.  (frame_threshold.hip's, which keeps its own.)
-template <class Per>
-__device__ __forceinline__ uint32_t key_word(const uint32_t *kr, int w, int n, bool wide, uint32_t t, Per &&per)
-{
-    uint32_t x = 0;
-    const int j0 = w * 32;
-    if (wide) {
-#pragma unroll 2
-        for (int q = 0; q < 8; q++) {
-            if (j0 + 4 * q >= n) break;                             // n % 4 == 0: a whole group or none
-            const uint4 v = *reinterpret_cast<const uint4 *>(kr + j0 + 4 * q);
-            const uint32_t k4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                per(4 * q + u, k4[u]);
-                x |= (uint32_t)(k4[u] < t) << (4 * q + u);
-            }
-        }
-    } else {
-        for (int b = 0; b < 32 && j0 + b < n; b++) {
-            const uint32_t k = kr[j0 + b];
-            per(b, k);
-            x |= (uint32_t)(k < t) << b;
-        }
-    }
-    return x;
-}
-
-__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ uint32_t uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-
 // Two 1024-thread workgroups per CU (8 waves per SIMD: at most 64 VGPRs) wherever the LDS admits them, as
-// frame_threshold_kernel.  No spills: tests/test_vn_thresh_resources.py.
+// frame_threshold_kernel.  No spills: tests/test_walk_resources.py.
 template <int DV, bool A16, class ST>
 __global__ __launch_bounds__(kBlock, 8) void vn_threshold_kernel(const VArgs a)
 {
@@ -347,66 +315,40 @@ __global__ __launch_bounds__(kBlock, 8) void vn_threshold_kernel(const VArgs a)
 
 }  // namespace
 
-// The front of the launch: launch_frame_threshold's checks, form ladder and workspace rule; the LDS carve is this kernel's own
-// (pos_a: the position words; pos_b: the grid, the count differences and the candidate list).
+// The launch on walk_launch's front, with launch_frame_threshold's window check, form ladder and workspace rule; the LDS carve is
+// this kernel's own (pos_a: the position words; pos_b: the grid, the count differences and the candidate list).  pos_a and pos_b
+// are never smaller than launch_frame_threshold's, of which pos_a's second L words stay unused: from n = 47 000 on the shape rule
+// is that kernel's and full_bp_eps's, so that a shape takes the same CN-word form in all three.
 static int launch_vn_threshold(const char *who, const scldpc_code_params *p, int32_t ntrials, const void *d_vn_adj, bool adj16,
                                const uint32_t *d_keys, uint32_t t_lo, uint32_t t_hi, int32_t is_term, int32_t npoints,
                                const uint32_t *grid, int32_t *d_rows, uint32_t *d_pos_thresh, int32_t *d_counts, uint32_t *d_tau,
                                const scldpc::Scratch &scratch, void *stream)
 {
-    using namespace scldpc;
-    using namespace scldpc_dev;
-    if (int rc = check_params(p)) return rc;
-    if (int rc = flood_check_call(who, scratch, ntrials, !d_rows || !d_vn_adj || !d_keys || !d_pos_thresh)) return rc;
-    if (!(t_lo < t_hi && t_hi <= SCLDPC_THRESH_MAX))
-        return set_error(SCLDPC_ERR_BAD_ARG, "%s: 0 <= t_lo < t_hi <= %u (got t_lo = %u, t_hi = %u)", who, SCLDPC_THRESH_MAX, t_lo,
-                         t_hi);
-    VArgs a{};
-    if (npoints < 0 || npoints > SCLDPC_VNT_MAX_POINTS)
-        return set_error(SCLDPC_ERR_BAD_ARG, "%s: 0 <= npoints <= %d (got npoints = %d)", who, SCLDPC_VNT_MAX_POINTS, npoints);
-    if (npoints > 0 && (!grid || (ntrials > 0 && !d_counts)))
-        return set_error(SCLDPC_ERR_BAD_ARG, "%s: npoints = %d needs a grid and d_counts", who, npoints);
-    for (int k = 0; k < npoints; k++) {
-        if (grid[k] < t_lo || grid[k] > t_hi || (k > 0 && grid[k] <= grid[k - 1]))
-            return set_error(SCLDPC_ERR_BAD_ARG, "%s: the grid must ascend strictly inside [t_lo, t_hi] (grid[%d] = %u)", who, k,
-                             grid[k]);
-        a.grid[k] = grid[k];
-    }
-    if (ntrials <= 0) return SCLDPC_OK;
-    if (!flood_limits_ok(p))
-        return set_error(SCLDPC_ERR_TOO_LARGE, "%s: needs dc <= 15, dv <= 8, dc*n < 2^24", who);
-    const int n = n_of(p), ncn = nk_of(p);
-    int words;
-    // (pos_a and pos_b are never smaller than launch_frame_threshold's, of which pos_a's second L words stay unused: from
-    // n = 47 000 on the shape rule is that kernel's and full_bp_eps's, so that a shape takes the same CN-word form in all three)
-    auto carve = [&](int w) {
-        const int sibling = ((nw_of(p) + 3) & ~3) + kBins, own = 2 * kGridWords + 2 * kListCap;
-        return flood_carve_roomy(p, {flood_cn_lds_words(w, ncn), false, 2 * p->L, sibling > own ? sibling : own, 256}, &a.lay);
-    };
-    const std::string nofit = std::string(who) + ": %d VN bits + %d scan bits do not fit 160 KiB of LDS";
-    if (int rc = flood_choose_words(who, nofit.c_str(), p, ntrials, scratch, adj16 && (int64_t)p->dv * p->vns_pos <= 4096, carve,
-                                    &words, &a.ws)) return rc;
-    if (words == kWordsQueryDone) return SCLDPC_OK;
-    if (const char *v = getenv("SCLDPC_DEBUG_EPS_QCAP")) {          // tests: forces the overflow re-scan at a small shape
-        const int cap = atoi(v);
-        if (cap > 0 && cap < a.lay.qcap) a.lay.qcap = cap;
-    }
-    a.ccap = kListCap;
-    if (const char *v = getenv("SCLDPC_DEBUG_VNT_CCAP")) {          // tests: forces list overflows and tie rounds
-        const int cap = atoi(v);
-        if (cap > 0 && cap < a.ccap) a.ccap = cap;
-    }
-    a.dv = p->dv; a.L = p->L; a.cns_pos = p->cns_pos; a.n = n; a.ncn = ncn; a.ntrials = ntrials; a.npoints = npoints;
-    a.cn_lim = is_term ? ncn : p->L * p->cns_pos;
-    a.t_lo = t_lo; a.t_hi = t_hi;
-    const std::string inexact = std::string(who) + ": reciprocal division inexact";
-    if (int rc = flood_geo(inexact.c_str(), p, n > 4096 ? n : 4096, &a)) return rc;
-    a.vn_adj = d_vn_adj; a.keys = d_keys; a.rows = d_rows; a.pos_thresh = d_pos_thresh; a.counts = d_counts; a.tau = d_tau;
-    a.key_wide = (n & 3) == 0 && (reinterpret_cast<uintptr_t>(d_keys) & 15) == 0;
-    void (*kern)(const VArgs) = flood_pick(words, p->dv == 4, adj16, [](auto st, auto dv, auto a16) -> void (*)(const VArgs) {
+    using scldpc::set_error;
+    return scldpc::walk_launch<VArgs>(who, p, ntrials, !d_rows || !d_keys || !d_pos_thresh, d_vn_adj, adj16, scratch, stream,
+                                      [](const scldpc_code_params *p) { return 2 * p->L; }, 2 * kGridWords + 2 * kListCap,
+                                      [&](VArgs &a, int ncn) {
+        if (int rc = scldpc::thresh_window(who, p, ncn, d_keys, t_lo, t_hi, is_term, a)) return rc;
+        if (npoints < 0 || npoints > SCLDPC_VNT_MAX_POINTS)
+            return set_error(SCLDPC_ERR_BAD_ARG, "%s: 0 <= npoints <= %d (got npoints = %d)", who, SCLDPC_VNT_MAX_POINTS, npoints);
+        if (npoints > 0 && (!grid || (ntrials > 0 && !d_counts)))
+            return set_error(SCLDPC_ERR_BAD_ARG, "%s: npoints = %d needs a grid and d_counts", who, npoints);
+        for (int k = 0; k < npoints; k++) {
+            if (grid[k] < t_lo || grid[k] > t_hi || (k > 0 && grid[k] <= grid[k - 1]))
+                return set_error(SCLDPC_ERR_BAD_ARG, "%s: the grid must ascend strictly inside [t_lo, t_hi] (grid[%d] = %u)", who, k,
+                                 grid[k]);
+            a.grid[k] = grid[k];
+        }
+        a.npoints = npoints; a.rows = d_rows; a.pos_thresh = d_pos_thresh; a.counts = d_counts; a.tau = d_tau;
+        a.ccap = kListCap;
+        if (const char *v = getenv("SCLDPC_DEBUG_VNT_CCAP")) {      // tests: forces list overflows and tie rounds
+            const int cap = atoi(v);
+            if (cap > 0 && cap < a.ccap) a.ccap = cap;
+        }
+        return (int)SCLDPC_OK;
+    }, [](auto st, auto dv, auto a16) -> void (*)(const VArgs) {
         return vn_threshold_kernel<decltype(dv)::value, decltype(a16)::value, decltype(st)>;
     });
-    return flood_launch(kern, ntrials, kBlock, stream, a);
 }
 
 extern "C" int scldpc_vn_threshold_device(const scldpc_code_params *p, int32_t ntrials, const int32_t *d_vn_adj,

@@ -182,6 +182,23 @@ def init_distributed():
     return True
 
 
+def gather_frames(dist, part, sizes, dim=0, shape=None, dtype=torch.int32, device=None):
+    """The frames of one round from every rank, in frame order: rank r holds sizes[r] entries of `part` along `dim`; every rank
+    pads to max(sizes) with zeros, all-gathers, and gets the concatenation of each rank's first sizes[r] entries, contiguous.
+    A rank without frames may pass None with the shape (its entry at `dim` is ignored), dtype and device its part would have had.
+    With one rank, or dist None, `part` itself comes back."""
+    if dist is None or len(sizes) == 1:
+        return part
+    shape = list(part.shape if part is not None else shape)
+    shape[dim] = max(sizes)
+    pad = torch.zeros(shape, dtype=part.dtype if part is not None else dtype, device=part.device if part is not None else device)
+    if part is not None:
+        pad.narrow(dim, 0, part.shape[dim]).copy_(part)
+    got = [_uninit(pad.shape, pad.dtype, pad.device) for _ in sizes]
+    dist.all_gather(got, pad)
+    return torch.cat([g.narrow(dim, 0, s) for g, s in zip(got, sizes)], dim=dim).contiguous()
+
+
 def cn16_supported(p):
     """The (4,8) chain with N <= 2048 and fewer than 65535 VNs: the second-generation sampler + the 4-bits-per-CN decoder take it."""
     return bool(lib().scldpc_sample_philox_cn16_supported(C.byref(p))) and bool(lib().scldpc_full_bp_cn16_supported(C.byref(p)))
@@ -720,6 +737,28 @@ def _eps_workspace_bytes(query, p, ntrials, adj16):
     return int(nbytes)
 
 
+def _ptr(t):
+    """The device pointer of an optional tensor."""
+    return t.data_ptr() if t is not None else None
+
+
+def _walk_call(entry, p, d_adj):
+    """The front of the four wrappers over one sampled code per frame (peel_sweep_eps, full_bp_eps, frame_threshold,
+    vn_threshold): the adjacency's contract and the workspace query, which also refuses the shape before anything is allocated.
+    Returns (T, device, call); call(*args) allocates the workspace, after the wrapper's outputs, and launches
+    scldpc_<entry>_device or its _adj16 twin with the entry's own arguments between the adjacency and the workspace."""
+    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
+    assert tuple(d_adj.shape[1:]) == (p.n, p.dv)
+    T, dev, adj16 = d_adj.shape[0], d_adj.device, _is_adj16(d_adj)
+    nbytes = _eps_workspace_bytes("scldpc_%s_workspace_query" % entry, p, T, adj16)
+    fn = getattr(lib(), "scldpc_%s_device%s" % (entry, "_adj16" if adj16 else ""))
+
+    def call(*args):
+        ws = _uninit(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        check(fn(C.byref(p), T, d_adj.data_ptr(), *args, _ptr(ws), nbytes, _stream_ptr(dev)))
+    return T, dev, call
+
+
 def peel_sweep_eps_workspace_bytes(p, ntrials, adj16):
     """Bytes of workspace peel_sweep_eps needs for ntrials trials (0: the CN words stay in LDS); ScldpcError for a shape the
     entry refuses.  Needs no device."""
@@ -732,19 +771,12 @@ def peel_sweep_eps(p, d_adj, d_levels, npoints, total_size, lost_lo=0, lost_hi=N
     out[k] is peel_sweep's block for the channel of point k ([0] #lost, [1] #lost_exp, [2] #blocks_failed_exp, [7] #erased;
     [5] the rounds of stage k, [6] its re-scans after a queue overflow) — and `lost` int32 [K, T, nw] or None (scldpc_peel_sweep_eps_device)."""
     _require_gpu()
-    T, K = d_adj.shape[0], int(npoints)
-    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
+    (T, dev, call), K = _walk_call("peel_sweep_eps", p, d_adj), int(npoints)
     assert d_levels.is_cuda and d_levels.dtype == torch.uint8 and d_levels.is_contiguous() and d_levels.shape == (T, p.n)
-    dev = d_adj.device
-    adj16 = _is_adj16(d_adj)
-    nbytes = peel_sweep_eps_workspace_bytes(p, T, adj16)                 # (also refuses the shape before anything is allocated)
     out = _uninit((max(K, 0), T, 8), dtype=torch.int32, device=dev)
     lost = _uninit((max(K, 0), T, p.nw), dtype=torch.int32, device=dev) if want_lost else None
-    ws = _uninit(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    fn = lib().scldpc_peel_sweep_eps_device_adj16 if adj16 else lib().scldpc_peel_sweep_eps_device
-    check(fn(C.byref(p), T, d_adj.data_ptr(), d_levels.data_ptr(), K, int(total_size), int(lost_lo),
-             int(total_size if lost_hi is None else lost_hi), out.data_ptr(), lost.data_ptr() if lost is not None else None,
-             ws.data_ptr() if ws is not None else None, nbytes, _stream_ptr(dev)))
+    call(d_levels.data_ptr(), K, int(total_size), int(lost_lo), int(total_size if lost_hi is None else lost_hi), out.data_ptr(),
+         _ptr(lost))
     return {"out": out, "lost": lost}
 
 
@@ -761,23 +793,14 @@ def full_bp_eps(p, d_adj, d_levels, npoints, is_term=True, want_erased=False, co
     accumulate_run reads — and `erased` int32 [K, T, nw] or None (scldpc_full_bp_eps_device).  counters: a contiguous int32
     [K, T, 8] tensor to write into."""
     _require_gpu()
-    T, K = d_adj.shape[0], int(npoints)
-    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
-    assert tuple(d_adj.shape[1:]) == (p.n, p.dv)
+    (T, dev, call), K = _walk_call("full_bp_eps", p, d_adj), int(npoints)
     assert d_levels.is_cuda and d_levels.dtype == torch.uint8 and d_levels.is_contiguous() and d_levels.shape == (T, p.n)
-    dev = d_adj.device
-    adj16 = _is_adj16(d_adj)
-    nbytes = full_bp_eps_workspace_bytes(p, T, adj16)                    # (also refuses the shape before anything is allocated)
     shape = (max(K, 0), T, NCOUNTERS)
     if counters is None:
         counters = _uninit(shape, dtype=torch.int32, device=dev)
     assert counters.is_cuda and counters.is_contiguous() and counters.dtype == torch.int32 and tuple(counters.shape) == shape
     erased = _uninit((max(K, 0), T, p.nw), dtype=torch.int32, device=dev) if want_erased else None
-    ws = _uninit(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    fn = lib().scldpc_full_bp_eps_device_adj16 if adj16 else lib().scldpc_full_bp_eps_device
-    check(fn(C.byref(p), T, d_adj.data_ptr(), d_levels.data_ptr(), K, 1 if is_term else 0, counters.data_ptr(),
-             erased.data_ptr() if erased is not None else None, ws.data_ptr() if ws is not None else None, nbytes,
-             _stream_ptr(dev)))
+    call(d_levels.data_ptr(), K, 1 if is_term else 0, counters.data_ptr(), _ptr(erased))
     return {"counters": counters, "erased": erased}
 
 
@@ -811,22 +834,14 @@ def frame_threshold(p, d_adj, d_keys, t_lo, t_hi, is_term=True, want_bits=False,
     _require_gpu()
     if not 0 <= int(t_lo) <= 0xFFFFFFFF or not 0 <= int(t_hi) <= 0xFFFFFFFF:
         raise ValueError("frame_threshold: the thresholds are unsigned 32-bit integers (got t_lo = %d, t_hi = %d)" % (t_lo, t_hi))
-    T = d_adj.shape[0]
-    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
-    assert tuple(d_adj.shape[1:]) == (p.n, p.dv)
+    T, dev, call = _walk_call("frame_threshold", p, d_adj)
     assert d_keys.is_cuda and d_keys.dtype == torch.int32 and d_keys.is_contiguous() and d_keys.shape == (T, p.n)
-    dev = d_adj.device
-    adj16 = _is_adj16(d_adj)
-    nbytes = frame_threshold_workspace_bytes(p, T, adj16)               # (also refuses the shape before anything is allocated)
     shape = (T, _lib.THRESH_NCOLS)
     if rows is None:
         rows = _uninit(shape, dtype=torch.int32, device=dev)
     assert rows.is_cuda and rows.is_contiguous() and rows.dtype == torch.int32 and tuple(rows.shape) == shape
     bits = _uninit((T, p.nw), dtype=torch.int32, device=dev) if want_bits else None
-    ws = _uninit(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    fn = lib().scldpc_frame_threshold_device_adj16 if adj16 else lib().scldpc_frame_threshold_device
-    check(fn(C.byref(p), T, d_adj.data_ptr(), d_keys.data_ptr(), int(t_lo), int(t_hi), 1 if is_term else 0, rows.data_ptr(),
-             bits.data_ptr() if bits is not None else None, ws.data_ptr() if ws is not None else None, nbytes, _stream_ptr(dev)))
+    call(d_keys.data_ptr(), int(t_lo), int(t_hi), 1 if is_term else 0, rows.data_ptr(), _ptr(bits))
     return {"rows": rows, "bits": bits}
 
 
@@ -852,13 +867,8 @@ def vn_threshold(p, d_adj, d_keys, t_lo, t_hi, grid=(), is_term=True, want_tau=F
     if any(not 0 <= t <= 0xFFFFFFFF for t in g):
         raise ValueError("vn_threshold: the grid's thresholds are unsigned 32-bit integers")
     garr = np.ascontiguousarray(g, dtype=np.uint32)
-    T, K = d_adj.shape[0], garr.size
-    assert d_adj.is_cuda and d_adj.dtype in (torch.int32, torch.int16) and d_adj.is_contiguous()
-    assert tuple(d_adj.shape[1:]) == (p.n, p.dv)
+    (T, dev, call), K = _walk_call("vn_threshold", p, d_adj), garr.size
     assert d_keys.is_cuda and d_keys.dtype == torch.int32 and d_keys.is_contiguous() and d_keys.shape == (T, p.n)
-    dev = d_adj.device
-    adj16 = _is_adj16(d_adj)
-    nbytes = vn_threshold_workspace_bytes(p, T, adj16)                  # (also refuses the shape before anything is allocated)
     shape = (T, _lib.VNT_NCOLS)
     if rows is None:
         rows = _uninit(shape, dtype=torch.int32, device=dev)
@@ -866,11 +876,8 @@ def vn_threshold(p, d_adj, d_keys, t_lo, t_hi, grid=(), is_term=True, want_tau=F
     pos = _uninit((T, p.L), dtype=torch.int32, device=dev)
     counts = _uninit((T, K), dtype=torch.int32, device=dev) if K else None
     tau = _uninit((T, p.n), dtype=torch.int32, device=dev) if want_tau else None
-    ws = _uninit(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    fn = lib().scldpc_vn_threshold_device_adj16 if adj16 else lib().scldpc_vn_threshold_device
-    check(fn(C.byref(p), T, d_adj.data_ptr(), d_keys.data_ptr(), int(t_lo), int(t_hi), 1 if is_term else 0, K,
-             garr.ctypes.data if K else None, rows.data_ptr(), pos.data_ptr(), counts.data_ptr() if counts is not None else None,
-             tau.data_ptr() if tau is not None else None, ws.data_ptr() if ws is not None else None, nbytes, _stream_ptr(dev)))
+    call(d_keys.data_ptr(), int(t_lo), int(t_hi), 1 if is_term else 0, K, garr.ctypes.data if K else None, rows.data_ptr(),
+         pos.data_ptr(), _ptr(counts), _ptr(tau))
     return {"rows": rows, "pos_thresh": pos, "counts": counts, "tau": tau}
 
 

@@ -35,6 +35,7 @@ import torch
 
 from . import engine as E
 from .engine import uncoupled_supported as _unc_first_ok, uncoupled_wide_supported as _unc_wide_ok     # shape rules: no device
+from .engine import gather_frames as _gather_frames                 # host plumbing over torch.distributed: no device call
 
 
 # ------------------------------------------------------------------------------------------------
@@ -424,13 +425,7 @@ def _simulate_sc_ldpc(e, l, r, L, M, is_terminated, is_protograph, is_bounded, i
         else:
             res = E.peel_sweep(p, d_adj, d_ch, g.total_size, g.sweep_start, g.lost_lo, g.lost_hi, **lost_kw)
         d_out, d_lost = res["out"], res.get("lost")
-        if world > 1:
-            m = max(offs[r + 1] - offs[r] for r in range(world))
-            pad = torch.zeros((m, d_out.shape[1]), dtype=d_out.dtype, device=d_out.device)
-            pad[:mine] = d_out
-            parts = [torch.empty_like(pad) for _ in range(world)]
-            dist.all_gather(parts, pad)
-            d_out = torch.cat([parts[r][:offs[r + 1] - offs[r]] for r in range(world)], dim=0).contiguous()
+        d_out = _gather_frames(dist, d_out, [offs[r + 1] - offs[r] for r in range(world)])
         E.accumulate_peel(d_out, run, max_fuckups)
         fuckups_bound += nb
         if fuckups_bound < max_fuckups and states is None:
@@ -571,13 +566,7 @@ def simulate_sc_ldpc_curve(es, l, r, L, M, is_terminated, is_protograph, is_boun
             for pos, alpha in doping_points.items():
                 d_lev[:, pos * M: pos * M + int(alpha * M)] = 0
         d_out = E.peel_sweep_eps(p, d_adj, d_lev, len(live), g.total_size, g.lost_lo, g.lost_hi)["out"]
-        if world > 1:
-            m = max(offs[r + 1] - offs[r] for r in range(world))
-            pad = torch.zeros((len(live), m, 8), dtype=d_out.dtype, device=d_out.device)
-            pad[:, :mine] = d_out
-            parts = [torch.empty_like(pad) for _ in range(world)]
-            dist.all_gather(parts, pad)
-            d_out = torch.cat([parts[r][:, :offs[r + 1] - offs[r]] for r in range(world)], dim=1).contiguous()
+        d_out = _gather_frames(dist, d_out, [offs[r + 1] - offs[r] for r in range(world)], dim=1)
         for i, k in enumerate(live):
             E.accumulate_peel(d_out[i], run[k], max_fuckups)
             bound[k] += nb

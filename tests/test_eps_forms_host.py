@@ -27,7 +27,7 @@ WIDE = {(4, 8, 6, 1026): 4104, (3, 6, 6, 1366): 4098, (5, 10, 6, 820): 4100}    
 PACKED = {(4, 8, 6, 1024): 4096, (3, 6, 6, 1364): 4092, (5, 10, 6, 818): 4090}        # the last N on its Packed side
 # (dv, dc, L, N) -> (n, nk): the smallest even N at which peel_sweep_eps, full_bp_eps and frame_threshold go to the workspace
 WIDE_G = {(4, 8, 6, 8044): (48264, 36198), (3, 6, 6, 8966): (53796, 35864), (5, 10, 6, 7296): (43776, 36480)}
-# ... and vn_threshold, whose LDS carve is its own (csrc/vn_threshold.hip, the `carve` lambda: the grid, the count differences
+# ... and vn_threshold, whose LDS carve is its own (csrc/vn_threshold.hip, the floor it gives pos_b: the grid, the count differences
 # and the candidate list where the siblings keep R and the level counts): the same N at (4,8) and (3,6), earlier at (5,10)
 VN_FIRST_WIDE_G = {(4, 8, 6): 8044, (3, 6, 6): 8966, (5, 10, 6): 7276}
 SHIPPED_WIDE = (5, 10, 50, 1000)
@@ -49,11 +49,17 @@ def form(shape, adj16, kernel="full_bp_eps"):
 
 
 def test_the_packed_rule_is_the_one_the_launches_apply():
-    """The arithmetic of this file is the launches': 2-byte rows and dv * vns_pos <= 4096, in the three files that choose the
-    words of the four kernels."""
+    """The arithmetic of this file is the launches': 2-byte rows and dv * vns_pos <= 4096, once, in the front that chooses the
+    words of the four kernels (walk_launch, eps_stages.h), which every launch goes through and none repeats."""
     rule = "adj16 && (int64_t)p->dv * p->vns_pos <= %d, carve" % PACK_LIMIT
+    assert open(os.path.join(CSRC, "eps_stages.h")).read().count(rule) == 1
     for name in ("eps_stages.h", "frame_threshold.hip", "vn_threshold.hip"):
-        assert open(os.path.join(CSRC, name)).read().count(rule) == 1, name
+        text = open(os.path.join(CSRC, name)).read()
+        assert text.count("walk_launch<") == 1, name
+        assert name == "eps_stages.h" or "flood_choose_words" not in text, name
+    for name in ("peel_sweep_eps.hip", "full_bp_eps.hip"):
+        text = open(os.path.join(CSRC, name)).read()
+        assert text.count("eps_walk_launch<") == 1 and "flood_choose_words" not in text, name
 
 
 @pytest.mark.parametrize("shape", list(WIDE), ids=lambda s: "%d_%d_L%d_N%d" % s)
@@ -122,7 +128,8 @@ def test_the_shipped_shapes():
     """What production runs (the drivers set adj16 = cns_pos <= 65536, so always the 2-byte rows)."""
     from fl_scaling_sc_ldpc_amd import bp_decoding as BP
     src = open(os.path.join(ROOT, "fl_scaling_sc_ldpc_amd", "bp_decoding.py")).read()
-    assert src.count("adj16 = p.cns_pos <= 65536") >= 3                  # run_grid_fused, run_thresholds, run_vn_thresholds
+    assert src.count("adj16 = p.cns_pos <= 65536") == 1                  # the code buffers of the rounds the three drivers share
+    assert src.count("rounds = _CodeRounds(p, ") == 3                     # run_grid_fused, run_thresholds, run_vn_thresholds
     for kernel in QUERIES:
         assert form(SHIPPED_WIDE, True, kernel) == ("Wide", "A16", "generic"), kernel
         assert form(SHIPPED_WIDE_G, True, kernel) == ("WideG", "A16", "DV4"), kernel
