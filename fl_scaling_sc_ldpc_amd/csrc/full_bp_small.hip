@@ -606,6 +606,9 @@ constexpr int kPerCu = 7;               // workgroups per CU the LDS carve aims 
 constexpr int kSwitchWidth = 128;       // frontier entries below which the waves go private
 constexpr int kBlockWide = 1024;        // the wide form: one workgroup per CU, four waves per SIMD
 constexpr int kWideMinQueue = 1024;     // entries per queue below which the wide form is not worth selecting
+// floor of SCLDPC_DEBUG_DECODER_QCAP: every queue store is guarded by idx < qcap and a scan round takes min(found, qcap)
+// entries, so a queue of one entry stays in bounds and still makes progress
+constexpr int kMinDebugQcap = 1;
 static_assert(kSwitchWidth <= 64 * (kBlockSmall / 64), "a wave takes at most one frontier entry per lane into its private queue");
 
 // The degree pairs with instances (kernel_of): their index, or -1
@@ -685,7 +688,9 @@ struct Form {
     bool sock;          // the CN table holds sockets instead of global VN ids
     bool wide;          // 32-bit queue entries, one 1024-thread workgroup per CU (LEVEL, TRAJ or CAPS with sockets only)
     bool deg = false;   // the _deg entry points: the degree pair of the parameters picks the instance (sockets only)
-    // the A/B knobs SCLDPC_DEBUG_DECODER_KSWITCH, SCLDPC_DEBUG_GRID_DECODER and SCLDPC_DEBUG_LDS_PAD_DECODER act on these forms only
+    // the A/B knobs SCLDPC_DEBUG_GRID_DECODER and SCLDPC_DEBUG_LDS_PAD_DECODER act on these forms only.  The two knobs of the
+    // tests act wherever they mean something (launch): SCLDPC_DEBUG_DECODER_QCAP shortens the queues of every form, and
+    // SCLDPC_DEBUG_DECODER_KSWITCH moves the switch-over width of every fixpoint instance, the _deg ones included.
     bool knobs() const { return mode != M_CAPS && !wide && !deg; }
 };
 
@@ -790,9 +795,24 @@ int launch(const char *who, const Form &f, const Call &c)
     a.kswitch = kSwitchWidth;
     int grid = c.ntrials;
     size_t lds_bytes = 4u * (size_t)a.total;
-    if (f.knobs()) {
-        // A/B only; a wave takes at most one entry per lane into its private queue, so the width is capped at 64 entries per wave
+    // tests and A/B only; a wave takes at most one entry per lane into its private queue, so the width is capped at 64 entries
+    // per wave.  Only the fixpoint instances read it.
+    if (f.mode == M_FIX)
         if (const char *v = getenv("SCLDPC_DEBUG_DECODER_KSWITCH")) a.kswitch = std::min(atoi(v), 64 * (kBlockSmall / 64));
+    // tests only: shorter queues, so that small shapes clamp their scans, drop pushes and take their snapshots one queue-full
+    // at a time (a private half-queue below 64 entries keeps the fixpoint form's waves on the shared queue).  It only ever
+    // shrinks the queues; the LDS taken and its layout stay those of the full carve.
+    if (const char *v = getenv("SCLDPC_DEBUG_DECODER_QCAP")) {
+        a.qcap = std::max(kMinDebugQcap, std::min(atoi(v), a.qcap));
+        // the kernel's packed reduction, for this queue: a wave releases at most nk / waves + 64 (nk / qcap + 1) VNs per
+        // iteration, and never more than there are CNs (a CN is queued once per iteration)
+        const int64_t waves = (f.wide ? kBlockWide : kBlockSmall) / 64;
+        const int64_t r = std::min<int64_t>(a.nk, a.nk / waves + 64 * ((int64_t)a.nk / a.qcap + 1));
+        if (r > 32767 || c.p->dv * r >= (1 << 17))
+            return scldpc::set_error(SCLDPC_ERR_BAD_ARG, "%s: SCLDPC_DEBUG_DECODER_QCAP: with %d entries per queue a wave's releases "
+                                     "per iteration could exceed the packed reduction's 15 / 17 bits at this shape", who, a.qcap);
+    }
+    if (f.knobs()) {
         grid = scldpc::debug_grid("DECODER", c.ntrials);
         lds_bytes = std::min(lds_bytes + scldpc::debug_lds_pad("DECODER"), (size_t)scldpc::kMaxLdsBytes);
     }

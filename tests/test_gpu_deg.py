@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import require_gpu
+from small_queue_cases import front_overflows, natural_qcap
 
 pytestmark = pytest.mark.gpu
 
@@ -111,6 +112,8 @@ def test_deg_decoder_equals_the_first_generation_at_n_1000(E, dv, dc):
     assert E.full_bp_deg_supported(p)
     for eps in (0.2, 0.46, 0.49):
         a, cs, ch = _tables(E, p, 7, 3, 8, eps)
+        if eps == 0.2:                                       # the inputs do fill the queue: more degree-1 CNs than its entries
+            assert front_overflows(p, a.cpu().numpy(), ch.cpu().numpy(), max(natural_qcap(p, m, False) for m in ("level", "traj")))
         for cap in (0, 1, 40):
             for rows_cap in (0, 600):
                 ref = E.full_bp(p, a, ch, max_it=cap, rows_cap=rows_cap, want_erased=True)

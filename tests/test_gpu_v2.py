@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_names, load_golden, require_gpu
+from small_queue_cases import front_overflows, natural_qcap
 
 pytestmark = pytest.mark.gpu
 
@@ -242,6 +243,8 @@ def test_level_decoder_with_a_small_queue_takes_the_frontier_from_the_snapshot(E
     p = E.make_params(4, 8, 50, 1000)
     for eps in (0.2, 0.35, 0.6, 0.97):
         a, cn, ch = E.sample_philox_cn16(p, 79, 0, 64, eps)
+        if eps < 0.5:                                        # the inputs do fill the queue: more degree-1 CNs than its entries
+            assert front_overflows(p, a.cpu().numpy(), ch.cpu().numpy(), natural_qcap(p, "level", False)), eps
         ref = E.full_bp(p, a, ch, want_erased=True)
         lvl = E.full_bp_cn16(p, a, cn, ch, want_erased=True)
         torch.cuda.synchronize()

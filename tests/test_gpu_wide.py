@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_DIR, load_golden, require_gpu
+from small_queue_cases import front_overflows, natural_qcap
 
 pytestmark = pytest.mark.gpu
 
@@ -91,6 +92,8 @@ def test_wide_decoder_takes_frontiers_of_many_queue_fulls_from_the_snapshot(E):
     for eps in (0.2, 0.35, 0.6, 0.97):
         a, ch = E.sample_philox(p, 79, 0, 32, eps, adj16=True)
         cs = E.cn_sockets(p, a)
+        if eps < 0.5:                                        # the inputs do fill the queue: more degree-1 CNs than its entries
+            assert front_overflows(p, a.cpu().numpy(), ch.cpu().numpy(), natural_qcap(p, "traj", True)), eps
         ref = E.full_bp(p, a, ch, want_erased=True, rows_cap=64)
         out = E.full_bp_wide(p, a, cs, ch, want_erased=True, rows_cap=64)
         torch.cuda.synchronize()
